@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the QP-assembly hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1], SURVEY.md section 8d "C2"): the biped-LIPM walking
 formulation, N=16, 2 axes, 6 costs, 3 boxes (36 unknowns, 76 inequality rows in
@@ -16,13 +16,18 @@ by default ONE launch of mpcasm_assemble that builds the horizon matrices on chi
 rotate over --rotate buffer sets so that at B=4096 (140 MB per step) consecutive steps
 do not rewrite lines that still sit in the 256 MiB Infinity Cache.
 
-Prints ONE JSON line (rank 0): whole-job assemblies/s, the roofline object of the
-dominant kernel (one pair of hipEvents on the launch stream around the timed region: the
-same clock as ms_per_step), `fill` sub-records (K1 alone, timed after the main region, on
-the north-star shapes), an `extra` record at B=65536 (a working set far beyond the
+Prints ONE JSON line (rank 0): whole-job assemblies/s and ms_per_step of the K timed steps.
+A plain run does nothing else: it sets up, warms up, times the K steps, writes the outputs of
+the last one when --dump-outputs DIR is given and prints the line.
+
+--full adds what takes runs of its own after the timed region: the roofline object of the
+dominant kernel (one pair of hipEvents on the launch stream around the same steps once
+more), `fill` sub-records (K1 alone on the north-star shapes), the other C2 shapes and
+BASELINE configurations, an `extra` record at B=65536 (a working set far beyond the
 Infinity Cache), for N>1 a separately timed `gather` record (all-gather of the assembled
 QPs over RCCL, never part of `value`) and, at N=1, the CPU baseline (the numpy oracle --
-a port of the reference algorithm -- on this box's host cores, bounded sample).
+a port of the reference algorithm -- and its compiled twin on the host's cores, bounded
+sample); --no-extras and --no-cpu-baseline drop parts of it.
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL); the batch is
 sharded with no collective on the data path (weak scaling: B per GPU is fixed); the only
@@ -56,6 +61,8 @@ for path in (os.path.join(ROOT, "mpc-interface_amd"), ROOT):
 
 HBM_PEAK_GBPS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 METRIC = "QP assemblies/sec (P,q,G,h), biped N=16 batched"
+# --dump-outputs: instances written at most (C2: 33 KB of P, q, G, h each in fp64, 34 MB for 1024)
+DUMP_INSTANCES = 1024
 
 
 def parse_args(argv=None):
@@ -75,9 +82,16 @@ def parse_args(argv=None):
                          "the CUs the one before has already left instead of waiting for its last "
                          "workgroup and a launch gap (tools/two_streams.py: 30.4 -> 26.6 us per step); 1 = "
                          "one stream.  The roofline record is always taken on ONE stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the roofline and hipEvents passes, the sub-records "
+                         "and the CPU baseline, and the long form of the record on stderr and in a file; "
+                         "default: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write P, q, G, h of the last timed step (rank 0) as DIR/<name>.npy, float64, at "
+                         "most %d instances (a fixed, seeded sample of a larger batch)" % DUMP_INSTANCES)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the fill / B=65536 / gather sub-records (main line only)")
+                    help="with --full: skip the fill / B=65536 / gather sub-records")
     ap.add_argument("--two-kernels", action="store_true",
                     help="step = mpcasm_fill_su (S, U through HBM) + mpcasm_assemble instead of the "
                          "default single launch that builds the horizon matrices on chip")
@@ -666,7 +680,6 @@ def compact_line(rec):
     def short_kernel(name):
         return str(name).split(" ")[0]
 
-    r = rec["roofline"]
     out = {k: rec[k] for k in ("metric", "value", "unit", "n_gpus", "n_ranks_seen", "steps", "warmup",
                                "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     c = rec["config"]
@@ -674,9 +687,11 @@ def compact_line(rec):
                                  % (c["no"], c["nc"], "K1 on chip" if c["fused"] else "fill+assemble"),
                      "batch_per_gpu": c["batch_per_gpu"], "global_batch": c["global_batch"],
                      "streams": c["launch_streams"]}
-    out["roofline"] = {"kernel": short_kernel(r["kernel_name"]), "bound": r["bound"], "achieved": r["achieved"],
-                       "peak": r["peak"], "unit": r["unit"], "frac": r["frac"], "traffic": r["traffic"],
-                       "bytes": r["algorithmic_bytes_per_launch"], "avg_launch_ms": r["avg_launch_ms"]}
+    if "roofline" in rec:    # (--full)
+        r = rec["roofline"]
+        out["roofline"] = {"kernel": short_kernel(r["kernel_name"]), "bound": r["bound"], "achieved": r["achieved"],
+                           "peak": r["peak"], "unit": r["unit"], "frac": r["frac"], "traffic": r["traffic"],
+                           "bytes": r["algorithmic_bytes_per_launch"], "avg_launch_ms": r["avg_launch_ms"]}
     if "cpu_baseline" in rec:
         b = rec["cpu_baseline"]
         out["cpu_baseline"] = {"value": b["value"], "unit": b["unit"], "cores": b["cores"], "kind": b["kind"],
@@ -734,6 +749,22 @@ def tiled(x, times):
     return np.concatenate([x] * times) if times > 1 else x
 
 
+def dump_outputs(path, outputs, batch):
+    """--dump-outputs: each tensor of ``outputs`` (name -> [batch, ...]) as ``path/<name>.npy`` in
+    float64, the instances of ``instances.npy`` only: all of them, or DUMP_INSTANCES of a larger
+    batch picked by a fixed seed (the same rows in every run with the same arguments)."""
+    import torch
+
+    idx = np.arange(batch)
+    if batch > DUMP_INSTANCES:
+        idx = np.sort(np.random.default_rng(0).choice(batch, DUMP_INSTANCES, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "instances.npy"), idx.astype(np.float64))
+    for name, t in outputs.items():
+        rows = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(path, name + ".npy"), rows.to(torch.float64).cpu().numpy())
+
+
 # --------------------------------------------------------------------------
 # one rank
 # --------------------------------------------------------------------------
@@ -759,6 +790,8 @@ def run_stub(args, world, rank):
     for _ in range(args.steps):
         P.add_(0.0)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"P": P}, hi - lo)
     record = {"metric": METRIC, "unit": "assemblies/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "stub": True,
               "n_ranks_seen": dist.get_world_size() if use_dist else 1,
@@ -884,71 +917,11 @@ def run_rank(args):
     elapsed = time.perf_counter() - t0
     if dist is not None:
         elapsed = mdist.max_over_ranks(elapsed, device=dev)
-    # the same K steps once more with a pair of hipEvents around them (the first on stream 0, the
-    # others wait for it; the second on stream 0 after it has waited for the others): the device's own
-    # clock beside the wall clock, `timed_region.ms_per_step_hipEvents`; not what `value` comes from
-    e_begin, e_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e_begin.record(streams[0])
-    for s in streams[1:]:
-        s.wait_event(e_begin)
-    for k in range(args.steps):
-        step(k, streams[k % nstreams])
-    for s in streams[1:]:
-        streams[0].wait_stream(s)
-    e_end.record(streams[0])
-    sync_all()
-    region_ms = e_begin.elapsed_time(e_end) / args.steps
-
-    # the dominant kernel by itself, for the roofline record: the same steps once more on ONE
-    # stream (K1-fused: a step IS one kernel, so event time / steps = average launch duration,
-    # launch gaps included -- the conservative reading; rocprofv3's kernel time of the same
-    # command with --streams 1 is what it is compared with); --two-kernels adds a pair of events
-    # around the fill of every 8th step.
-    k_steps = max(min(args.steps, 1000), 200)      # (a short run of the driver's: still 200 launches behind the kernel's figure)
-    k_begin, k_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fill_ev = []
-    k_begin.record()
-    for k in range(k_steps):
-        if not fused:
-            if k % 8 == 0:
-                pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                pair[0].record()
-                engine.fill_su(A, Bm, N, out=SU)
-                pair[1].record()
-                fill_ev.append(pair)
-            else:
-                engine.fill_su(A, Bm, N, out=SU)
-        asm.assemble(given, out=outs[k % len(outs)])
-    k_end.record()
-    sync_all()
-    step_ms = k_begin.elapsed_time(k_end) / k_steps
-    fill_ms = float(np.mean([a.elapsed_time(b) for a, b in fill_ev])) if fill_ev else 0.0
-    asm_ms = step_ms - fill_ms
-
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed, before any later pass writes its buffers again
+        dump_outputs(args.dump_outputs, dict(zip("PqGh", outs[(args.steps - 1) % len(outs)])), B)
     no, ng, nc = asm.no, asm.ng, asm.nc
-    nparams = int(asm.params.shape[1])
-    bytes_fill = fill_bytes(3, 1, N, False)
-    bytes_out = 8 * (no * no + no + nc * no + nc)
-    bytes_asm = bytes_out + 8 * (ng + nparams) + (8 * (9 + 3) if fused else 8 * (N * 9 + N * N * 3))
     value = world * B * args.steps / elapsed
-
-    # dominant kernel = the assembly (K2-K4, K1 inside when fused); HBM-bound
-    achieved = bytes_asm * B / (asm_ms * 1e-3) / 1e9
-    # HBM bytes per launch from the PMC passes of the same command (rocprofv3 --pmc
-    # FETCH_SIZE / WRITE_SIZE in separate runs, tools/summarize_profile.py); only
-    # quoted when it was collected at this batch size
-    traffic = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-            pmc = json.load(f)
-        if pmc.get("batch_per_gpu") == B and pmc.get("k1_fused", False) == fused:
-            traffic = pmc["traffic_bytes_per_launch"]
-    except (OSError, ValueError, KeyError):
-        pass
-    # (which kernel really ran: the per-plan compiled one falls back to the ahead-of-time kernel
-    # when libhiprtc.so is missing or the compilation fails)
-    kernel_name = "mpcasm_assemble -> %s: %sK2 compose + K3 hessian_mfma + K4 constraint_stack in one " \
-                  "launch" % (asm.last_kernel(), "K1 horizon tables + " if fused else "")
     ranks_seen = dist.get_world_size() if dist is not None else 1
     devices = ["r%d cuda:%d %s" % (rank, local_rank, torch.cuda.get_device_name(local_rank).replace("AMD Instinct ", ""))]
     if dist is not None:
@@ -991,7 +964,75 @@ def run_rank(args):
             "step": "mpcasm_assemble, horizon matrices built on chip from per-instance (A,B) "
                     "(K1 fused)" if fused else "mpcasm_fill_su + mpcasm_assemble",
         },
-        "roofline": {
+    }
+
+    # --full: the timed region's figure beside the device's clock and the dominant kernel's roofline
+    # (runs of their own after the timed region), then the sub-records and the CPU baseline
+    if args.full:
+        # the same K steps once more with a pair of hipEvents around them (the first on stream 0, the
+        # others wait for it; the second on stream 0 after it has waited for the others): the device's own
+        # clock beside the wall clock, `timed_region.ms_per_step_hipEvents`; not what `value` comes from
+        e_begin, e_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_begin.record(streams[0])
+        for s in streams[1:]:
+            s.wait_event(e_begin)
+        for k in range(args.steps):
+            step(k, streams[k % nstreams])
+        for s in streams[1:]:
+            streams[0].wait_stream(s)
+        e_end.record(streams[0])
+        sync_all()
+        region_ms = e_begin.elapsed_time(e_end) / args.steps
+
+        # the dominant kernel by itself, for the roofline record: the same steps once more on ONE
+        # stream (K1-fused: a step IS one kernel, so event time / steps = average launch duration,
+        # launch gaps included -- the conservative reading; rocprofv3's kernel time of the same
+        # command with --streams 1 is what it is compared with); --two-kernels adds a pair of events
+        # around the fill of every 8th step.
+        k_steps = max(min(args.steps, 1000), 200)  # (a short run: still 200 launches behind the kernel's figure)
+        k_begin, k_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fill_ev = []
+        k_begin.record()
+        for k in range(k_steps):
+            if not fused:
+                if k % 8 == 0:
+                    pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    pair[0].record()
+                    engine.fill_su(A, Bm, N, out=SU)
+                    pair[1].record()
+                    fill_ev.append(pair)
+                else:
+                    engine.fill_su(A, Bm, N, out=SU)
+            asm.assemble(given, out=outs[k % len(outs)])
+        k_end.record()
+        sync_all()
+        step_ms = k_begin.elapsed_time(k_end) / k_steps
+        fill_ms = float(np.mean([a.elapsed_time(b) for a, b in fill_ev])) if fill_ev else 0.0
+        asm_ms = step_ms - fill_ms
+
+        nparams = int(asm.params.shape[1])
+        bytes_fill = fill_bytes(3, 1, N, False)
+        bytes_out = 8 * (no * no + no + nc * no + nc)
+        bytes_asm = bytes_out + 8 * (ng + nparams) + (8 * (9 + 3) if fused else 8 * (N * 9 + N * N * 3))
+
+        # dominant kernel = the assembly (K2-K4, K1 inside when fused); HBM-bound
+        achieved = bytes_asm * B / (asm_ms * 1e-3) / 1e9
+        # HBM bytes per launch from the PMC passes of the same command (rocprofv3 --pmc
+        # FETCH_SIZE / WRITE_SIZE in separate runs, tools/summarize_profile.py); only
+        # quoted when it was collected at this batch size
+        traffic = None
+        try:
+            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                pmc = json.load(f)
+            if pmc.get("batch_per_gpu") == B and pmc.get("k1_fused", False) == fused:
+                traffic = pmc["traffic_bytes_per_launch"]
+        except (OSError, ValueError, KeyError):
+            pass
+        # (which kernel really ran: the per-plan compiled one falls back to the ahead-of-time kernel
+        # when libhiprtc.so is missing or the compilation fails)
+        kernel_name = "mpcasm_assemble -> %s: %sK2 compose + K3 hessian_mfma + K4 constraint_stack in one " \
+                      "launch" % (asm.last_kernel(), "K1 horizon tables + " if fused else "")
+        record["roofline"] = {
             "kernel": kernel_name,
             "kernel_name": asm.last_kernel(),
             "bound": "hbm",
@@ -1009,20 +1050,19 @@ def run_rank(args):
             "clock": "hipEvents on ONE launch stream around %d launches of the same steps, right after the "
                      "timed region (launch gaps included); the timed region itself deals its launches to "
                      "%d stream(s), where consecutive launches overlap" % (k_steps, nstreams),
-        },
-        "timed_region": {"launch_streams": nstreams, "ms_per_step_hipEvents": region_ms,
-                         "one_stream_ms_per_step": step_ms},
-        "hbm_GBps_end_to_end": (bytes_asm + (0 if fused else bytes_fill)) * value / 1e9,
-    }
-    if not fused:
-        record["fill_in_step"] = {
-            "kernel": "mpcasm_fill_su (K1 toeplitz_fill)",
-            "algorithmic_bytes_per_system": bytes_fill,
-            "avg_launch_ms": fill_ms,
-            "achieved_GBps": bytes_fill * B / (fill_ms * 1e-3) / 1e9,
         }
+        record["timed_region"] = {"launch_streams": nstreams, "ms_per_step_hipEvents": region_ms,
+                                "one_stream_ms_per_step": step_ms}
+        record["hbm_GBps_end_to_end"] = (bytes_asm + (0 if fused else bytes_fill)) * value / 1e9
+        if not fused:
+            record["fill_in_step"] = {
+                "kernel": "mpcasm_fill_su (K1 toeplitz_fill)",
+                "algorithmic_bytes_per_system": bytes_fill,
+                "avg_launch_ms": fill_ms,
+                "achieved_GBps": bytes_fill * B / (fill_ms * 1e-3) / 1e9,
+            }
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # optional final gather of the assembled QPs: all-gather over RCCL/xGMI
         if dist is not None:
             P, q, G, h = outs[(args.steps - 1) % len(outs)]
@@ -1099,7 +1139,7 @@ def run_rank(args):
             del asm_big, SU_big, out_big, Ab, Bb, gb
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         rate1, count1, secs1 = cpu_baseline(work, 5.0)
         rate, count, procs = cpu_baseline_all_cores(8.0)
         try:
@@ -1133,7 +1173,7 @@ def run_rank(args):
                                 % (count, procs, count1, secs1),
                 "sample": numpy_line["sample"], "compiled_port": "unavailable: %s" % exc,
                 "compiled_fill_single_thread": compiled}
-    if rank == 0:
+    if rank == 0 and args.full:
         # the long form beside the line: a file (gpurun_out/ travels back from a GPU box) and stderr
         full_dir = os.path.join(ROOT, "gpurun_out")
         try:
@@ -1146,6 +1186,7 @@ def run_rank(args):
         except OSError:
             record["full_record"] = "stderr"
         print(json.dumps(record), file=sys.stderr, flush=True)
+    if rank == 0:
         print(json.dumps(compact_line(record)), flush=True)
     if dist is not None:
         dist.barrier()

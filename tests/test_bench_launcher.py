@@ -41,6 +41,19 @@ def test_single_rank_needs_no_launcher():
     assert rec["n_gpus"] == 1 and "gather" not in rec
 
 
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR: the outputs of the timed path as DIR/<name>.npy in float64, with the
+    instances they belong to (the whole batch when it is small)."""
+    import numpy as np
+
+    proc = _run(["--gpus", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert proc.returncode == 0, proc.stderr
+    P = np.load(tmp_path / "out" / "P.npy")
+    idx = np.load(tmp_path / "out" / "instances.npy")
+    assert P.dtype == np.float64 and P.shape == (8, 36, 36) and np.all(P == 0.0)
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.arange(8))
+
+
 def test_a_failed_rank_fails_the_run():
     proc = _run(["--gpus", "2", "--stub-fail-rank", "1"], timeout=120)
     assert proc.returncode != 0

@@ -22,7 +22,7 @@ def test_rccl_with_one_rank():
         env.pop(k, None)
     proc = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--dist-at-world-1", "--backend", "nccl",
-         "--steps", "50", "--warmup", "5", "--batch", "1024", "--no-cpu-baseline"],
+         "--steps", "50", "--warmup", "5", "--batch", "1024", "--no-cpu-baseline", "--full"],
         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     rec = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
