@@ -11,7 +11,9 @@ centres, extremes, horizon matrices) stay outside, as device buffers.
 This module is host logic only (numpy / scipy.sparse); it never evaluates a
 preview matrix or a QP block -- that is the kernels' job.
 """
+import collections
 import hashlib
+from types import SimpleNamespace
 
 import numpy as np
 import scipy.sparse as sp
@@ -485,10 +487,7 @@ def _preview_program(b, rowptr, entbase, entk, entcoef, pmrows):
     empty = dict(nfd=0, map=z, fd_ptr=z, ops=z, pool=np.zeros(0))
     if pmrows * W > PM_MAX_MAP or pmrows == 0 or len(b.sources) > 254:
         return empty
-    segs_of_base = [[] for _ in b.base_rows]
-    for bid, colseg in enumerate(b.colseg):
-        for sg in sorted(set(int(x) for x in colseg if x >= 0)):
-            segs_of_base[bid].append(b.segments[sg])
+    segs_of_base = _segments_of_base(b)
     dst, sid_l, off_l, coef = [], [], [], []
     nops = 0
     for r in range(pmrows):
@@ -546,10 +545,7 @@ def _fused_program(b, rowptr, entbase, entk, entcoef, rtot, ldv):
                  fd_ptr=np.zeros(1, np.int32), ops=np.zeros(0, np.int32),
                  coefpool=np.zeros(0), row_tiles=row_tiles)
 
-    segs_of_base = [[] for _ in b.base_rows]
-    for bid, colseg in enumerate(b.colseg):
-        for sg in sorted(set(int(x) for x in colseg if x >= 0)):
-            segs_of_base[bid].append(b.segments[sg])
+    segs_of_base = _segments_of_base(b)
 
     dst, src, gidx, coef = [], [], [], []
     for r in range(rtot):
@@ -658,33 +654,6 @@ class Workspace:
 
     def holds_block(self, r, blk):
         return self.c0[r] <= 4 * blk and 4 * blk + 4 <= self.c0[r] + self.w[r]
-
-
-def _resident_rows(limit_recs, lax_recs, nparams, ws):
-    """Per row of the stacked G, 16 words: workspace index (:meth:`Workspace.rowstart`) of every axis' row [4], arrow
-    param of every axis [4], center param of every axis [4], naxes, extreme param, then
-    the first two axes once more, packed: voff0 | voff1 << 16, arrow0 | arrow1 << 16 (zero
-    where that does not fit); a missing axis points at workspace row 0 with the always-zero
-    parameter slot ``nparams``."""
-    rows = []
-    for out0, nrows, naxes, lax0, p_a, a_rows, p_c, c_rows, p_e, e_rows, _, _ in limit_recs:
-        for r in range(nrows):
-            tail = [naxes, p_e + (0 if e_rows == 1 else r), 0, 0]
-            voff, ap, cp = [], [], []
-            for ax in range(RS_AXMAX):
-                if ax < naxes:
-                    off, rs = lax_recs[lax0 + ax]
-                    voff.append(ws.rowstart(off + (0 if rs == 1 else r)))
-                    ap.append(p_a + (0 if a_rows == 1 else r) * naxes + ax)
-                    cp.append(p_c + (0 if c_rows == 1 else r) * naxes + ax)
-                else:
-                    voff.append(0)
-                    ap.append(nparams)
-                    cp.append(nparams)
-            if naxes <= 2 and max(voff) < 65536 and nparams < 65536:
-                tail[2:] = [voff[0] | (voff[1] << 16), ap[0] | (ap[1] << 16)]
-            rows.append(voff + ap + cp + tail)
-    return np.asarray(rows, dtype=np.int64).astype(np.uint32).view(np.int32).reshape(-1)
 
 
 def _lti_groups(form, sources, names):
@@ -1116,7 +1085,7 @@ def _column_tables(b, groups, nop):
     """``ci[base][column][2]`` over the columns ``[given | unknowns padded to nop]``
     (csrc/plan_tables.h, H_T_CI_OK): element offset for base row 0 and ``rs | stream << 24``.
     Offsets into the stream that is the plan's dtab are relative to the delta table here
-    (``compile_plan`` adds its position).  Also returns the delta table and ok."""
+    (``_column_sections`` adds its position).  Also returns the delta table and ok."""
     ng, no = b.ng, b.no
     nbase = len(b.base_rows)
     L = max([seg[5] for seg in b.segments if seg[6] == SEG_IDENTITY] + [0])
@@ -1182,7 +1151,7 @@ def _row_tile_masks(b, rowptr, entbase, entk, rtot, causal):
     return masks
 
 
-def _tiled_program(b, form, gterms, rowptr, entbase, entk, entcoef, rtot, groups, rr_ok, g_rows):
+def _tiled_program(b, form, gterms, rowptr, entbase, entk, entcoef, rtot, groups, rr_ok, gr):
     """Tables of the tiled kernel (csrc/tiled.hip): the column tables, the stage list of the
     Hessian / gradient terms with their structural tile masks, and the groups of horizon
     tables a pre-pass generates from per-instance (A, B)."""
@@ -1215,11 +1184,10 @@ def _tiled_program(b, form, gterms, rowptr, entbase, entk, entcoef, rtot, groups
         return n
 
     # rows of G that are arrow * (one workspace row): they ride on the first stage whose A rows
-    # hold that row (g_rows: per row of G the workspace rows of its axes)
+    # hold that row (gr: the G-row table, _g_rows)
     riders = {}
-    for R, axes in enumerate(g_rows):
-        if len(axes) == 1:
-            riders.setdefault(axes[0][0], []).append((R, axes[0][1]))
+    for R in np.flatnonzero(gr["naxes"] == 1):
+        riders.setdefault(int(gr["row"][R, 0]), []).append((int(R), int(gr["arrow"][R, 0])))
     stages, srow, scoef, pig = [], [], [], []
     for g in gterms:
         aoff, boff, nrows, wparam, doff, aimparam, flags = g[:7]
@@ -1285,7 +1253,7 @@ def _tiled_program(b, form, gterms, rowptr, entbase, entk, entcoef, rtot, groups
     stages = [stages[i] for i in order]
     srow, scoef, pig = ([x[i] for i in order] for x in (srow, scoef, pig))
     riding = {int(R) for pg in pig for R in pg[:, :, 0].ravel() if R >= 0}
-    grest = np.asarray([R for R in range(len(g_rows)) if R not in riding], dtype=np.int64)
+    grest = np.asarray([R for R in range(gr["naxes"].size) if R not in riding], dtype=np.int64)
     d_len = rtot + (rtot & 1)
     work = d_len
     lti, ids = [], []
@@ -1307,7 +1275,7 @@ def _tiled_program(b, form, gterms, rowptr, entbase, entk, entcoef, rtot, groups
                 lti_ids=np.asarray(ids, dtype=np.int64), work=work)
 
 
-def _scan_tables(b, gterms, rowptr, entbase, entk, entcoef, groups, g_rows, tiled, nparams):
+def _scan_tables(b, gterms, rowptr, entbase, entk, entcoef, groups, gr, tiled, nparams):
     """Tables of the tiled kernel's *scan form* (csrc/tiled.hip ``toeplitz_scan_kernel``,
     plan_tables.h T_SCAN*).
 
@@ -1323,7 +1291,7 @@ def _scan_tables(b, gterms, rowptr, entbase, entk, entcoef, groups, g_rows, tile
     coefficients, and per row of G ``(i m N + k, arrow slot)`` with its coefficient when the row is
     ``arrow * c * (row k of state i)`` (else -1: the row is composed through the column tables behind
     the rest)."""
-    nc, no, ng = len(g_rows), b.no, b.ng
+    nc, no, ng = gr["naxes"].size, b.no, b.ng
     off = dict(ok=0, K=0, blk=np.zeros((0, 2), np.int64), gt=np.zeros((0, T_SCAN_GT_WORDS), np.int64),
                gc=np.zeros(0), grow=np.zeros((0, 2), np.int64), gcoef=np.zeros(0),
                grest=np.zeros(0, np.int64), colblk=np.zeros(0, np.int64), nother=0, fused=0)
@@ -1381,12 +1349,12 @@ def _scan_tables(b, gterms, rowptr, entbase, entk, entcoef, groups, g_rows, tile
     if not 1 <= len(blk) <= T_SCAN_BLKMAX:
         return off
     grow, gcoef, grest = -np.ones((nc, 2), dtype=np.int64), np.zeros(nc), []
-    for R, axes in enumerate(g_rows):
-        x = state_row(axes[0][0]) if len(axes) == 1 else None
+    for R in range(nc):
+        x = state_row(gr["row"][R, 0]) if gr["naxes"][R] == 1 else None
         if x is None:
             grest.append(R)
             continue
-        grow[R] = (x[0] * m * N + x[1], axes[0][1])
+        grow[R] = (x[0] * m * N + x[1], gr["arrow"][R, 0])
         gcoef[R] = x[2]
     # Fused set-up (H_T_SCAN_FUSED): the kernel can make its own table and its own d = Mg given -- no pre-pass, no
     # scratch -- when `given` is exactly the group's initial state in order (every state reads S at
@@ -1554,7 +1522,7 @@ def _sweep_tables(b, gterms, limit_recs, lax_recs, rowptr, entbase, entk, entcoe
                 col=col, cvec=cv.reshape(-1)), None
 
 
-def _structural_patterns(form, b, fused, gterms, limit_recs, lax_recs, rtot, ldv, no, nc, groups=()):
+def _structural_patterns(form, b, fused, gterms, gr, rtot, ldv, groups=()):
     """Which entries of P (no x no) and of the stacked G (nc x no) can be non-zero at all:
     from the structurally non-zero elements of the workspace (an element with at least one
     op whose source is not a known zero -- ``U_j[k][l]`` above the diagonal l > k is zero
@@ -1562,6 +1530,7 @@ def _structural_patterns(form, b, fused, gterms, limit_recs, lax_recs, rtot, ldv
     None when the op lists were not built (huge plans)."""
     if rtot and fused["fd_idx"].size == 0:
         return None, None
+    no, nc = b.no, gr["naxes"].size
     ops = fused["ops"].view(np.uint32).reshape(-1, 2)
     arena = fused["arena"].reshape(-1, 2)
     zero_src = np.zeros(int(fused["arena_total"]) + 1, dtype=bool)
@@ -1589,11 +1558,8 @@ def _structural_patterns(form, b, fused, gterms, limit_recs, lax_recs, rtot, ldv
             bb = Vo[g[1]:g[1] + g[2]].astype(np.int64)
             Pnz |= (a.T @ bb) > 0
     Gnz = np.zeros((nc, no), dtype=bool)
-    for out0, nrows, naxes, lax0, *_ in limit_recs:
-        for r in range(nrows):
-            for ax in range(naxes):
-                off, rs = lax_recs[lax0 + ax]
-                Gnz[out0 + r] |= Vo[off + (0 if rs == 1 else r)]
+    for rows in gr["row"].T:                                     # every axis of the rows of G
+        Gnz[rows >= 0] |= Vo[rows[rows >= 0]]
     return Pnz, Gnz
 
 
@@ -1611,40 +1577,72 @@ def csc_pattern(mask, upper=False):
     return indptr, rows_sorted.astype(np.int32), flat
 
 
-def compile_plan(form, costs=None, limits=None, lti=(), csc=None, workspace="auto", ltv=()):
-    """Compile ``form`` (an up-to-date Formulation: sizes and IDs current).
 
-    ``costs``: dict name -> Cost to include (default ``form.goals``);
-    ``limits``: list of Constraint in stacking order (default: every limit of
-    ``form.constraints`` then of ``form.constraint_boxes``, body.py:306-315);
-    ``lti``: names of ExtendedSystem dynamics whose horizon matrices the assembly kernel
-    generates on chip from per-instance ``(A, B)`` instead of reading ``S, U`` (K1 fused into
-    the assembly; only the persistent kernel can run such a plan);
-    ``ltv``: ONE name of an ExtendedSystem whose dynamics differ from step to step and instance to
-    instance, ``x+ = A_k x + B_k u`` (BASELINE config C5): the sweep kernel (csrc/sweep.hip) takes
-    ``A (N, n, n)``, ``B (N, n, m)`` per instance and assembles without forming a horizon matrix
-    (:func:`_sweep_tables` states what the formulation has to be for that; ValueError otherwise).
-    The reference has no such path (``dynamics.py:222-231`` re-extends ONE pair per tick): pinned to
-    it where all steps share one pair;
-    ``csc``: ``"upper"`` or ``"full"`` -- the plan's assembly writes, instead of dense P and G,
-    the ``data`` arrays of their CSC forms on the structural pattern (P: its upper triangle /
-    all of it), what ``scipy.sparse.csc_matrix(Q)``, ``csc_matrix(A)`` hand the solver in
-    biped_mpc_loop.py:57-58: ``P`` becomes ``(B, plan.csc["pnnz"])``, ``G``
-    ``(B, plan.csc["gnnz"])``; ``plan.csc["P"]``, ``plan.csc["G"]`` hold ``(indptr, indices)``.
-    Only the persistent kernel writes this form: ValueError when the plan cannot run there.
-    """
-    b = _Builder(form)
-    b.flatten_definitions()
-    no = b.no
 
-    if costs is None:
-        costs = form.goals
-    if limits is None:
-        limits = [l for group in form.constraints.values() for l in group]
-        limits += [l for box in form.constraint_boxes.values() for l in box.constraints]
+def _g_rows(limit_recs, lax_recs, nparams):
+    """The G-row table: per row of the stacked G and per axis the workspace row, the arrow's and the
+    centre's parameter slot (a missing axis: row -1, the always-zero parameter slot ``nparams``), and
+    per row the number of axes and the extreme's slot.  At least RS_AXMAX axes wide."""
+    nc = sum(rec[1] for rec in limit_recs)
+    width = max([RS_AXMAX] + [rec[2] for rec in limit_recs])
+    gr = dict(row=-np.ones((nc, width), dtype=np.int64), arrow=np.full((nc, width), nparams, dtype=np.int64),
+              center=np.full((nc, width), nparams, dtype=np.int64), naxes=np.zeros(nc, dtype=np.int64),
+              extreme=np.zeros(nc, dtype=np.int64))
+    for out0, nrows, naxes, lax0, p_a, a_rows, p_c, c_rows, p_e, e_rows, _, _ in limit_recs:
+        R, r = slice(out0, out0 + nrows), np.arange(nrows)
+        gr["naxes"][R], gr["extreme"][R] = naxes, p_e + (e_rows != 1) * r
+        for ax in range(naxes):
+            off, rs = lax_recs[lax0 + ax]
+            gr["row"][R, ax] = off + (rs != 1) * r
+            gr["arrow"][R, ax] = p_a + (a_rows != 1) * r * naxes + ax
+            gr["center"][R, ax] = p_c + (c_rows != 1) * r * naxes + ax
+    return gr
 
-    # ---- costs -> terms (body.py:266-302) ----------------------------------------
-    terms = []
+
+def _voff(gr, ws):
+    """Per row of G and axis :meth:`Workspace.rowstart` of the axis' row, 0 for a missing axis."""
+    return np.where(gr["row"] >= 0, ws.rowstart(gr["row"]), 0)
+
+
+def _resident_rows(gr, ws, nparams):
+    """Per row of the stacked G, 16 words: workspace index (:meth:`Workspace.rowstart`) of every axis' row [4], arrow
+    param of every axis [4], center param of every axis [4], naxes, extreme param, then
+    the first two axes once more, packed: voff0 | voff1 << 16, arrow0 | arrow1 << 16 (zero
+    where that does not fit); a missing axis points at workspace row 0 with the always-zero
+    parameter slot ``nparams``."""
+    voff, ap = _voff(gr, ws)[:, :RS_AXMAX], gr["arrow"][:, :RS_AXMAX]
+    packed = (gr["naxes"] <= 2) & (voff.max(axis=1) < 65536) & (nparams < 65536)
+    tail = np.stack([gr["naxes"], gr["extreme"], np.where(packed, voff[:, 0] | (voff[:, 1] << 16), 0),
+                     np.where(packed, ap[:, 0] | (ap[:, 1] << 16), 0)], axis=1)
+    rows = np.concatenate([voff, ap, gr["center"][:, :RS_AXMAX], tail], axis=1)
+    return rows.astype(np.uint32).view(np.int32).reshape(-1)
+
+
+def _g_pieces(gr, ws, nparams):
+    """Whether G can go by 16-byte pieces of at most two axes: no row of G has more, and the
+    workspace indices and parameter slots of a piece fit 16 bits."""
+    return bool((gr["naxes"] <= 2).all() and (ws.row0 + ws.rtot + 8) * ws.ldv < 65536 and nparams < 65535)
+
+
+def _written(fe):
+    """Per element of the dense workspace: whether anything is composed into it (every other
+    element is an exact zero)."""
+    nz = np.zeros(max(fe.rtot, 1) * fe.ldv, dtype=bool)
+    nz[fe.fused["fd_idx"]] = True
+    return nz
+
+
+def _live_first(c0, c1, *pairs):
+    """The (first axis, second axis) ``pairs`` of G's pieces, swapped where only the second axis can
+    be non-zero (``c0``, ``c1``: which can): the axis that can goes first."""
+    swap = c1 & ~c0
+    return [(np.where(swap, y, x), np.where(swap, x, y)) for x, y in pairs]
+
+
+def _cost_terms(b, costs):
+    """Costs -> gterm records (body.py:266-302; a workspace row is a row-set id until
+    place_rowsets) and the coefficients of the diagonal ones."""
+    gterms, diag_coefs = [], []
     for name, cost in costs.items():
         p_w = b.param(("cost", name, "weight"), lambda c=cost: [[float(c.weight)]])
         aim = np.asarray(cost.aim, dtype=np.float64)
@@ -1667,11 +1665,27 @@ def compile_plan(form, costs=None, limits=None, lti=(), csc=None, workspace="aut
                 raise ValueError(
                     "cost '{}': {} rows of '{}' against {} rows of '{}'".format(
                         name, nv, cost.variable + axis, ncr, cost.cross + axis))
-            diag = b.diagonal_rowset(va) if (not crossed and va == ca) else None
-            terms.append(dict(va=va, ca=ca, n=nv, w=p_w, aim=p_aim + i, caim=p_caim + i,
-                              plain=(not crossed and va == ca), diag=diag))
+            plain = not crossed and va == ca
+            diag = b.diagonal_rowset(va) if plain else None
+            if diag is not None:
+                # P[c][c] += (w coef) coef,  q[c] += w (coef (0 - aim))  on c = col0 .. col0 + n - 1
+                col0, coefs = diag
+                gterms.append([col0, sum(len(c) for c in diag_coefs), nv, p_w, 0, p_aim + i,
+                               GT_FLAG_DIAG, 0, 0, 0])
+                diag_coefs.append(coefs)
+            elif plain:
+                #  q += w V^T (Vg g - aim)
+                gterms.append([va, va, nv, p_w, va, p_aim + i, GT_FLAG_P, 0, 0, 0])
+            else:
+                #  P += w V^T C ;  q += w/2 V^T (Cg g - cross_aim) + w/2 C^T (Vg g - aim)
+                gterms.append([va, ca, nv, p_w, ca, p_caim + i, GT_FLAG_P | GT_FLAG_HALF, 0, 0, 0])
+                gterms.append([ca, -1, nv, p_w, va, p_aim + i, GT_FLAG_HALF, 0, 0, 0])
+    return gterms, (np.concatenate(diag_coefs) if diag_coefs else np.zeros(0))
 
-    # ---- limits (body.py:236-264, restrictions.py:147-199) -----------------------
+
+def _limit_records(b, limits):
+    """Limits -> limit records, their axes' (row-set id, rows) records, the limit of every row of G
+    and ``(first row, rows)`` of every limit (body.py:236-264, restrictions.py:147-199)."""
     limit_recs, lax_recs, rowlimit, limit_rows = [], [], [], []
     out0 = 0
     for idx, limit in enumerate(limits):
@@ -1708,312 +1722,343 @@ def compile_plan(form, costs=None, limits=None, lti=(), csc=None, workspace="aut
         rowlimit.extend([idx] * nrows)
         limit_rows.append((out0, nrows))
         out0 += nrows
-    nc = out0
+    return limit_recs, lax_recs, rowlimit, limit_rows
 
-    # ---- place the row-sets some kernel reads; build the gterms -----------------------
-    needed = set(rec[0] for rec in lax_recs)
-    for t in terms:
-        if t["diag"] is None:
-            needed.update((t["va"], t["ca"]))
-    where = b.place_rowsets(needed)
+
+def _front_end(form, costs, limits):
+    """What every kernel reads: the terms of the costs and the records of the limits, the row-sets
+    some kernel reads placed in the workspace, the gterms with their structural tile masks, the CSR
+    tables of the workspace (``csr``) and of the preview matrices (``pm``), the program of the
+    per-instance fused kernel and the G-row table (``gr``, :func:`_g_rows`).  Also the header words,
+    sections and Plan attributes of all that."""
+    b = _Builder(form)
+    b.flatten_definitions()
+    no = b.no
+    gterms, diag_coefs = _cost_terms(b, costs)
+    limit_recs, lax_recs, rowlimit, limit_rows = _limit_records(b, limits)
+    # ---- place the row-sets some kernel reads ----------------------------------------
+    rowsets = [g for g in gterms if not g[6] & GT_FLAG_DIAG]
+    where = b.place_rowsets({rec[0] for rec in lax_recs} | {g[0] for g in rowsets} | {g[4] for g in rowsets})
     for rec in lax_recs:
         rec[0] = where[rec[0]]
-    gterms, diag_coefs = [], []
-    for t in terms:
-        if t["diag"] is not None:
-            # P[c][c] += (w coef) coef,  q[c] += w (coef (0 - aim))  on c = col0 .. col0 + n - 1
-            col0, coefs = t["diag"]
-            gterms.append([col0, sum(len(c) for c in diag_coefs), t["n"], t["w"], 0, t["aim"],
-                           GT_FLAG_DIAG, 0, 0, 0])
-            diag_coefs.append(coefs)
-        elif t["plain"]:
-            #  q += w V^T (Vg g - aim)
-            va = where[t["va"]]
-            gterms.append([va, va, t["n"], t["w"], va, t["aim"], GT_FLAG_P, 0, 0, 0])
-        else:
-            #  P += w V^T C ;  q += w/2 V^T (Cg g - cross_aim) + w/2 C^T (Vg g - aim)
-            va, ca = where[t["va"]], where[t["ca"]]
-            gterms.append([va, ca, t["n"], t["w"], ca, t["caim"], GT_FLAG_P | GT_FLAG_HALF,
-                           0, 0, 0])
-            gterms.append([ca, -1, t["n"], t["w"], va, t["aim"], GT_FLAG_HALF, 0, 0, 0])
-    diag_coefs = np.concatenate(diag_coefs) if diag_coefs else np.zeros(0)
-
+    for g in rowsets:
+        g[0], g[1], g[4] = where[g[0]], (where[g[1]] if g[1] >= 0 else -1), where[g[4]]
+    gr = _g_rows(limit_recs, lax_recs, len(b.params))
+    nc = gr["naxes"].size
     # ---- tables ---------------------------------------------------------------------
-    rowptr, entbase, entk, entcoef, rtot = _csr_tables(
-        b.placed_blocks, b.base_row0, b.base_rows, b.total_base_rows)
+    *csr, rtot = _csr_tables(b.placed_blocks, b.base_row0, b.base_rows, b.total_base_rows)
     assert rtot == b.rtot
     ldv = no + 2              # columns: the unknowns, d = Mg . given, a column of ones (persistent kernel)
     ldv += (2 - ldv) % 4      # = 2 mod 4
-    fused = _fused_program(b, rowptr, entbase, entk, entcoef, rtot, ldv)
+    fused = _fused_program(b, *csr, rtot, ldv)
     # structural tile masks of the gterm operands (exact zeros of the workspace)
     tiles = fused["row_tiles"]
     for rec in gterms:
-        if rec[6] & GT_FLAG_DIAG:
-            continue
-
-        def mask(off, n):
-            m = 0
-            for r in range(off, off + n):
-                m |= int(tiles[r])
-            return m
-        rec[7] = mask(rec[0], rec[2])
-        rec[8] = mask(rec[1], rec[2]) if rec[1] >= 0 else 0
-    groups = _lti_groups(form, b.sources, lti)
-    sweep = None
-    if ltv:
-        if len(tuple(ltv)) != 1 or lti or csc is not None:
-            raise ValueError("ltv: one dynamics name, without lti= or csc=")
-        sweep, why = _sweep_tables(b, gterms, limit_recs, lax_recs, rowptr, entbase, entk, entcoef,
-                                   _lti_groups(form, b.sources, ltv)[0], len(b.params))
-        if sweep is None:
-            raise ValueError("dynamics %r cannot be assembled step by step: %s" % (tuple(ltv)[0], why))
-    image = _resident_image(b.sources, b.ng, len(b.params), groups)
-    # The persistent kernel's workspace: dense, or -- a wide problem whose row-sets each live in a
-    # part of the columns -- compact, when that is what lets a second workgroup share the CU's LDS.
-    # (Compact needs the 16-byte-piece paths of G: an even width, rows of at most two axes, no CSC.)
-    ws = Workspace.dense(rtot, no, ldv)
-    packed_like = csc is None and no % 2 == 0 and nc > 0 and all(rec[2] <= 2 for rec in limit_recs)
-    if workspace not in ("auto", "dense", "compact"):
-        raise ValueError("workspace: 'auto', 'dense' or 'compact'")
-    if _os.environ.get("MPCASM_NO_COMPACT"):              # (A/B aids: tools/ab_workspace.py)
-        workspace = "dense"
-    elif _os.environ.get("MPCASM_COMPACT") and workspace == "auto":
-        workspace = "compact"
-    if packed_like and rtot > 0 and workspace != "dense" and (workspace == "compact"
-                                                 or 8 * ws.doubles > RS_COMPACT_FROM_BYTES):
-        cand = Workspace.windows(rtot, no, b.spans, fused["fd_idx"] // ldv, fused["fd_idx"] % ldv)
-        if ((workspace == "compact" or 3 * cand.doubles <= 2 * ws.doubles)
-                and (cand.row0 + rtot + 8) * cand.ldv < 65536 and len(b.params) < 65535):
-            ws = cand
-    resident = _resident_program(fused, gterms, no, ldv, ws, image, b.ng, len(b.params), nc)
-    rs_rr = _resident_rows(limit_recs, lax_recs, len(b.params), ws)
-    # per row of G the windows of its (at most two) axes, in column pairs: first | count << 8 of the
-    # first axis, the same << 16 of the second (compact workspace only; a missing axis: 0 | 0)
-    rs_rrwin = np.zeros(0, dtype=np.int32)
-    if ws.compact:
-        win = []
-        for out0, nrows, naxes, lax0, *_ in limit_recs:
-            for r in range(nrows):
-                word = 0
-                for ax in range(naxes):
-                    off, rs = lax_recs[lax0 + ax]
-                    row = off + (0 if rs == 1 else r)
-                    word |= (int(ws.c0[row]) // 2 | (int(ws.w[row]) // 2) << 8) << (16 * ax)
-                win.append(word)
-        rs_rrwin = np.asarray(win, dtype=np.int64).astype(np.uint32).view(np.int32)
-    if any(rec[2] > RS_AXMAX for rec in limit_recs):
-        rs_rr = np.zeros(0, dtype=np.int32)      # too many axes: no resident kernel
+        if not rec[6] & GT_FLAG_DIAG:
+            rec[7] = int(np.bitwise_or.reduce(tiles[rec[0]:rec[0] + rec[2]]))
+            rec[8] = int(np.bitwise_or.reduce(tiles[rec[1]:rec[1] + rec[2]])) if rec[1] >= 0 else 0
     pm_blocks, pm_rows, r0 = [], {}, 0
     for var in form.definitions.keys():
         M = b.var_matrix[var]
         pm_blocks.append(M)
         pm_rows[var] = (r0, M.shape[0])
         r0 += M.shape[0]
-    pm_rowptr, pm_entbase, pm_entk, pm_entcoef, pmrows = _csr_tables(
-        pm_blocks, b.base_row0, b.base_rows, b.total_base_rows)
+    *pm, pmrows = _csr_tables(pm_blocks, b.base_row0, b.base_rows, b.total_base_rows)
+    rowptr, entbase, entk, entcoef = csr
+    words = dict(NG=b.ng, NO=no, NC=nc, NPARAMS=len(b.params), NSRC=len(b.sources),
+                 NBASE=len(b.base_rows), NSEG=len(b.segments), RTOT=rtot, NENT=entcoef.size,
+                 NGTERM=len(gterms), NLIMIT=len(limit_recs), NLAX=len(lax_recs), LDV=ldv,
+                 FUSED_OK=fused["ok"], ARENA_TOTAL=fused["arena_total"], NFD=fused["fd_idx"].size,
+                 NOPS=fused["ops"].size // 2, NCOEF=fused["coefpool"].size, NDIAGCOEF=diag_coefs.size)
+    sections = dict(
+        OFF_SEG=np.asarray(b.segments, dtype=np.int32).reshape(-1),
+        OFF_COLSEG=(np.concatenate(b.colseg) if b.colseg else np.zeros(0)).astype(np.int32),
+        OFF_ROWPTR=rowptr, OFF_ENTBASE=entbase, OFF_ENTK=entk,
+        OFF_GTERM=np.asarray(gterms, dtype=np.int32).reshape(-1),
+        OFF_LIMIT=np.asarray(limit_recs, dtype=np.int32).reshape(-1),
+        OFF_LAX=np.asarray(lax_recs, dtype=np.int32).reshape(-1),
+        OFF_ROWLIMIT=np.asarray(rowlimit, dtype=np.int32),
+        OFF_ARENA=fused["arena"], OFF_FD_IDX=fused["fd_idx"], OFF_FD_PTR=fused["fd_ptr"], OFF_OP=fused["ops"],
+        DOFF_ENTCOEF=entcoef, DOFF_COEFPOOL=fused["coefpool"], DOFF_DIAGCOEF=diag_coefs)
+    attrs = dict(ng=b.ng, no=no, nc=nc, sources=b.sources, params=np.asarray(b.params, dtype=np.float64),
+                 param_slots=b.param_slots, param_getters=b.param_getters, rtot=rtot, ldv=ldv,
+                 limit_rows=limit_rows, n_gterms=len(gterms), pm_rows=pm_rows, pmrows=pmrows,
+                 optim_ID={v: form.optim_ID[v] for v in form.optim_variables},
+                 given_ID={v: form.given_ID[v] for v in form.given_variables})
+    return SimpleNamespace(b=b, gterms=gterms, limit_recs=limit_recs, lax_recs=lax_recs, nc=nc, gr=gr,
+                           csr=csr, rtot=rtot, ldv=ldv, fused=fused, diag_coefs=diag_coefs, pm=pm,
+                           words=words, sections=sections, attrs=attrs)
 
-    sections = [
-        ("OFF_SEG", np.asarray(b.segments, dtype=np.int32).reshape(-1)),
-        ("OFF_COLSEG", (np.concatenate(b.colseg) if b.colseg else np.zeros(0)).astype(np.int32)),
-        ("OFF_ROWPTR", rowptr),
-        ("OFF_ENTBASE", entbase),
-        ("OFF_ENTK", entk),
-        ("OFF_GTERM", np.asarray(gterms, dtype=np.int32).reshape(-1)),
-        ("OFF_LIMIT", np.asarray(limit_recs, dtype=np.int32).reshape(-1)),
-        ("OFF_LAX", np.asarray(lax_recs, dtype=np.int32).reshape(-1)),
-        ("OFF_ROWLIMIT", np.asarray(rowlimit, dtype=np.int32)),
-        ("OFF_PM_ROWPTR", pm_rowptr),
-        ("OFF_PM_ENTBASE", pm_entbase),
-        ("OFF_PM_ENTK", pm_entk),
-        ("OFF_ARENA", fused["arena"]),
-        ("OFF_FD_IDX", fused["fd_idx"]),
-        ("OFF_FD_PTR", fused["fd_ptr"]),
-        ("OFF_OP", fused["ops"]),
-        ("OFF_RS_PROG", _packed_program(resident)),
-        ("OFF_RS_SRC", resident["src"]),
-        ("OFF_RS_GIDX", resident["gidx"]),
-        ("OFF_RS_DST", resident["dst"]),
-        ("OFF_RS_TRIP", resident["trips"]),
-        ("OFF_RS_WTRIP", resident["wtrip"]),
-        ("OFF_RS_SPLIT", resident["split"]),
-        ("OFF_RS_ZBLK", resident["zblk"]),
-        ("OFF_RS_RR", rs_rr),
-        ("OFF_RS_INMETA", image["meta"]),
-        ("OFF_RS_ABMETA", image["ab_meta"]),
-        ("OFF_RS_LTI", np.asarray(
-            [[g["n"], g["m"], g["N"], g["img_a"], g["img_b"], g["tab_a"], g["tab_b"], g["tab_p"]]
-             for g in groups], dtype=np.int32).reshape(-1)),
-    ]
-    # what the persistent kernel would otherwise derive once per workgroup, ready to copy:
-    # per column of the unknowns the (weight, aim) slots and coefficients of the (at most
-    # RS_DIAG_MAX = 2) diagonal gterms on it (free slots: the always-zero parameter), ...
-    rs_dpar = np.full((no, 2 * RS_DIAG_MAX), len(b.params), dtype=np.int32)
+
+def _sweep_back_end(form, fe, lti, ltv, csc):
+    """The sweep kernel's tables for a plan compiled with ``ltv=`` (:func:`_sweep_tables`), empty
+    otherwise."""
+    sweep, b = None, fe.b
+    if ltv:
+        if len(tuple(ltv)) != 1 or lti or csc is not None:
+            raise ValueError("ltv: one dynamics name, without lti= or csc=")
+        sweep, why = _sweep_tables(b, fe.gterms, fe.limit_recs, fe.lax_recs, *fe.csr,
+                                   _lti_groups(form, b.sources, ltv)[0], len(b.params))
+        if sweep is None:
+            raise ValueError("dynamics %r cannot be assembled step by step: %s" % (tuple(ltv)[0], why))
+    sw = sweep or collections.defaultdict(lambda: np.zeros(0))
+    sections = {name: np.asarray(sw[key]).astype(np.int32).reshape(-1) for name, key in (
+        ("OFF_SW_AXIS", "axes"), ("OFF_SW_TERM", "terms"), ("OFF_SW_LIM", "lims"), ("OFF_SW_COL", "col"),
+        ("OFF_SW_CPTR", "cptr"), ("OFF_SW_CENT", "cent"), ("OFF_SW_GPTR", "gptr"), ("OFF_SW_GENT", "gent"))}
+    sections["SW_DOFF_CVEC"] = np.asarray(sw["cvec"], dtype=np.float64)
+    words = dict(SW_NCVEC=np.asarray(sw["cvec"]).size // SW_NMAX)
+    if sweep is not None:
+        words.update(SW_OK=1, SW_N=sweep["n"], SW_M=sweep["m"], SW_HORIZON=sweep["N"],
+                     SW_NAXES=sweep["axes"].shape[0], SW_SRC_A=sweep["src_a"], SW_SRC_B=sweep["src_b"],
+                     SW_NTERM=sweep["terms"].shape[0], SW_NLIM=sweep["lims"].shape[0],
+                     SW_NCENT=sweep["cent"].size, SW_NGENT=sweep["gent"].shape[0])
+    ltv = ([dict(name=tuple(ltv)[0], n=sweep["n"], m=sweep["m"], N=sweep["N"],
+                 ids=[sweep["src_a"], sweep["src_b"]])] if sweep is not None else [])
+    return dict(words=words, sections=sections, attrs=dict(sweep=sweep, ltv=ltv))
+
+
+def _workspace(fe, workspace, csc):
+    """The persistent kernel's workspace: dense, or -- a wide problem whose row-sets each live in a
+    part of the columns -- compact, when that is what lets a second workgroup share the CU's LDS.
+    (Compact needs the 16-byte-piece paths of G: an even width, rows of at most two axes, no CSC.)"""
+    no, rtot, nparams = fe.b.no, fe.rtot, len(fe.b.params)
+    ws = Workspace.dense(rtot, no, fe.ldv)
+    if workspace not in ("auto", "dense", "compact"):
+        raise ValueError("workspace: 'auto', 'dense' or 'compact'")
+    if _os.environ.get("MPCASM_NO_COMPACT"):              # (A/B aids: tools/ab_workspace.py)
+        workspace = "dense"
+    elif _os.environ.get("MPCASM_COMPACT") and workspace == "auto":
+        workspace = "compact"
+    if (csc is None and no % 2 == 0 and fe.nc > 0 and rtot > 0 and workspace != "dense"
+            and (workspace == "compact" or 8 * ws.doubles > RS_COMPACT_FROM_BYTES)):
+        cand = Workspace.windows(rtot, no, fe.b.spans, fe.fused["fd_idx"] // fe.ldv, fe.fused["fd_idx"] % fe.ldv)
+        if (workspace == "compact" or 3 * cand.doubles <= 2 * ws.doubles) and _g_pieces(fe.gr, cand, nparams):
+            ws = cand
+    return ws
+
+
+def _g_descriptors(fe, ws, nparams):
+    """For small problems, the descriptor of every 16-byte piece of G a stream-wave thread owns:
+    piece e = t + u RS_GDESC_THREADS, columns 2cp, 2cp+1 of row R = e // (no/2):
+    Workspace.index(row0, 2cp) | Workspace.index(row1, 2cp) << 16, arrow0 | arrow1 << 16; and the
+    fixes and one-axis rounds (RS_GFIX, RS_GSINGLE).  Returns ``(gdesc, gfix, ngfix, gsingle)``."""
+    no, rtot, gr = fe.b.no, fe.rtot, fe.gr
+    e = np.arange(RS_GDESC_PIECES * RS_GDESC_THREADS)
+    live = e < fe.nc * (no // 2)
+    R = np.where(live, e // (no // 2), 0)
+    cp = np.where(live, e % (no // 2), 0)
+    # Which of a piece's (at most two) axes can be non-zero in its two columns at all: an
+    # element of the workspace nothing is composed into is an exact zero.  The axis that can
+    # goes first; where all 64 pieces of one wavefront's round have at most one such axis
+    # (the usual case: a variable per axis, columns partitioned by axis) the kernel reads one
+    # workspace row and one arrow instead of two (bit u * 4 + wave of RS_GSINGLE).
+    nz = _written(fe).reshape(-1, fe.ldv)
+
+    def can(row, col):
+        return nz[row, col] | nz[row, col + 1]
+
+    def inside(row, col):                            # (windows are whole 4-column blocks)
+        return (ws.c0[row] <= col) & (col + 2 <= ws.c0[row] + ws.w[row])
+
+    voff, rows = _voff(gr, ws)[R], np.maximum(gr["row"][R], 0)      # (a missing axis: row 0)
+    v0, v1, a0, a1 = voff[:, 0], voff[:, 1], gr["arrow"][R, 0], gr["arrow"][R, 1]
+    two = gr["naxes"][R] >= 2
+    r0, r1 = rows[:, 0], rows[:, 1]
+    c0, c1 = can(r0, 2 * cp), two & can(r1, 2 * cp)
+    # the piece in the row's window: its index; outside (compact workspace): row 0, zero arrow
+    in0, in1 = inside(r0, 2 * cp), two & inside(r1, 2 * cp)
+    p0 = np.where(in0, v0 + 2 * cp - ws.c0[r0], 0)
+    p1 = np.where(in1 | ~two, v1 + np.where(two, 2 * cp - ws.c0[r1], 0), 0)
+    a0, a1 = np.where(in0, a0, nparams), np.where(in1 | ~two, a1, nparams)
+    if not ws.compact:
+        p1 = v1 + 2 * cp                             # (a missing axis: row 0 + the piece's columns)
+    (p0, p1), (a0, a1) = _live_first(c0, c1, (p0, p1), (a0, a1))
+    single = ~(c0 & c1) | ~live
+    word0 = p0 | (p1 << 16)                          # Workspace.index(row, 2 cp)
+    word1 = a0 | (a1 << 16)
+    gdesc = np.stack([word0, word1], axis=1).astype(np.uint32).view(np.int32).reshape(-1)
+    # A few pieces with two live axes among many with one (the biped's 34-wide phase: x ends
+    # and y begins inside one piece of every two-axis row) would turn every round they sit in
+    # into a two-axis round.  Instead the round stays a one-axis round and adds the second axis
+    # for that lane alone; a thread holds the second axis of at most one of its pieces (RS_GFIX).
+    # (Writing such pieces apart, behind the rounds, leaves 16-byte holes in the lines the
+    # rounds write: partial lines cost the write stream half its rate, tools/run_variant.py.)
+    gfix, ngfix = np.zeros(0, dtype=np.int32), 0
+    both = np.flatnonzero(~single)
+    in_mixed_rounds = int((~single.reshape(-1, 64).all(axis=1)).sum()) * 64
+    owners = both % RS_GDESC_THREADS
+    if (both.size and 4 * both.size <= in_mixed_rounds and np.unique(owners).size == both.size
+            and not _os.environ.get('MPCASM_NO_GFIX')):            # (A/B aid: tools/run_variant.py)
+        fix = np.zeros((RS_GDESC_THREADS, 2), dtype=np.int64)
+        fix[:, 0], fix[:, 1] = RS_GFIX_NONE << 16, nparams
+        fix[owners, 0] = p1[both] | ((both // RS_GDESC_THREADS) << 16)
+        fix[owners, 1] = a1[both]
+        gfix, ngfix = fix.astype(np.uint32).view(np.int32).reshape(-1), int(both.size)
+        single = np.ones_like(single)
+    rounds = single.reshape(RS_GDESC_PIECES, RS_GDESC_THREADS // 64, 64).all(axis=2)
+    gsingle = int(sum(1 << (u * (RS_GDESC_THREADS // 64) + w)
+                      for u in range(RS_GDESC_PIECES) for w in range(RS_GDESC_THREADS // 64)
+                      if rounds[u, w]))
+    return gdesc, gfix, ngfix, gsingle
+
+
+def _persistent_back_end(fe, groups, workspace, csc):
+    """Tables of the persistent kernel: its workspace, the input image and the resident program,
+    the row records and windows of G, the diagonal parameters, the descriptors of G and their
+    fixes.  Whether the kernel can run the plan at all is decided here (RS_OK), and ``rr_ok``:
+    no row of G has more than RS_AXMAX axes."""
+    b, gr, nc, no, nparams = fe.b, fe.gr, fe.nc, fe.b.no, len(fe.b.params)
+    image = _resident_image(b.sources, b.ng, nparams, groups)
+    ws = _workspace(fe, workspace, csc)
+    resident = _resident_program(fe.fused, fe.gterms, no, fe.ldv, ws, image, b.ng, nparams, nc)
+    rr_ok = bool((gr["naxes"] <= RS_AXMAX).all())
+    rs_rr = _resident_rows(gr, ws, nparams) if rr_ok else np.zeros(0, dtype=np.int32)
+    # per row of G the windows of its (at most two) axes, in column pairs: first | count << 8 of the
+    # first axis, the same << 16 of the second (compact workspace only; a missing axis: 0 | 0)
+    rs_rrwin = np.zeros(0, dtype=np.int32)
+    if ws.compact:
+        rows = np.maximum(gr["row"][:, :2], 0)
+        win = np.where(gr["row"][:, :2] >= 0, ws.c0[rows] // 2 | (ws.w[rows] // 2) << 8, 0)
+        rs_rrwin = (win[:, 0] | win[:, 1] << 16).astype(np.uint32).view(np.int32)
+    # per column of the unknowns the (weight, aim) slots and coefficients of the (at most RS_DIAG_MAX = 2)
+    # diagonal gterms on it (free slots: the always-zero parameter): ready to copy
+    rs_dpar = np.full((no, 2 * RS_DIAG_MAX), nparams, dtype=np.int32)
     rs_dcoef = np.zeros((no, RS_DIAG_MAX))
     taken = np.zeros(no, dtype=np.int64)
-    for g in gterms:
+    for g in fe.gterms:
         if g[6] & GT_FLAG_DIAG:
             for k in range(g[2]):
                 c, j = g[0] + k, int(taken[g[0] + k])
                 if j < RS_DIAG_MAX:
                     rs_dpar[c, 2 * j:2 * j + 2] = [g[3], g[5]]
-                    rs_dcoef[c, j] = diag_coefs[g[1] + k]
+                    rs_dcoef[c, j] = fe.diag_coefs[g[1] + k]
                 taken[c] += 1
-    # ... and, for small problems, the descriptor of every 16-byte piece of G a stream-wave
-    # thread owns: piece e = t + u RS_GDESC_THREADS, columns 2cp, 2cp+1 of row R = e // (no/2):
-    # Workspace.index(row0, 2cp) | Workspace.index(row1, 2cp) << 16, arrow0 | arrow1 << 16
-    rs_gdesc = rs_gfix = np.zeros(0, dtype=np.int32)
-    rs_ngfix = 0
-    rs_gsingle = 0
-    rr_ok = rs_rr.size == nc * RS_RR_WORDS
-    packed_ok = (rr_ok and no % 2 == 0 and nc > 0 and (ws.row0 + b.rtot + 8) * ws.ldv < 65536
-                 and len(b.params) < 65535
-                 and bool((rs_rr.reshape(nc, RS_RR_WORDS)[:, 12] <= 2).all()))
+    packed_ok = no % 2 == 0 and nc > 0 and _g_pieces(gr, ws, nparams)
     assert packed_ok or not ws.compact
-    if packed_ok and nc * (no // 2) <= RS_GDESC_PIECES * RS_GDESC_THREADS:
-        recs = rs_rr.reshape(nc, RS_RR_WORDS).astype(np.int64)
-        e = np.arange(RS_GDESC_PIECES * RS_GDESC_THREADS)
-        live = e < nc * (no // 2)
-        R = np.where(live, e // (no // 2), 0)
-        cp = np.where(live, e % (no // 2), 0)
-        # Which of a piece's (at most two) axes can be non-zero in its two columns at all: an
-        # element of the workspace nothing is composed into is an exact zero.  The axis that can
-        # goes first; where all 64 pieces of one wavefront's round have at most one such axis
-        # (the usual case: a variable per axis, columns partitioned by axis) the kernel reads one
-        # workspace row and one arrow instead of two (bit u * 4 + wave of RS_GSINGLE).
-        nz = np.zeros(max(rtot, 1) * ldv, dtype=bool)
-        nz[fused["fd_idx"]] = True
-        nz = nz.reshape(-1, ldv)
+    z = np.zeros(0, dtype=np.int32)
+    gdesc, gfix, ngfix, gsingle = (_g_descriptors(fe, ws, nparams)
+                                   if packed_ok and nc * (no // 2) <= RS_GDESC_PIECES * RS_GDESC_THREADS
+                                   else (z, z, 0, 0))
+    words = dict(RS_OK=int(resident["ok"] and rr_ok), RS_JC=resident["jc"], RS_SYM=resident["sym"],
+                 RS_NTRIP=resident["ntrip"], RS_NSPLIT=resident["split"].size, RS_NZBLK=resident["zblk"].size,
+                 RS_UNIT=image["unit"], RS_NCHUNK=image["nchunk"], RS_IMG=image["img"], RS_IMG_DMA=image["dma"],
+                 RS_IMG_GIVEN=image["given"], RS_IMG_PARAMS=image["params"], RS_AB=image["ab"],
+                 RS_NLTI=len(groups), RR_PACKED=int(packed_ok), RS_NGDESC=gdesc.size // 2, RS_NGFIX=ngfix,
+                 RS_GSINGLE=gsingle, RS_COMPACT=ws.compact, RS_LDV=ws.ldv, RS_VD=ws.vd, RS_VROW0=ws.row0)
+    sections = dict(
+        OFF_RS_PROG=_packed_program(resident), OFF_RS_SRC=resident["src"], OFF_RS_GIDX=resident["gidx"],
+        OFF_RS_DST=resident["dst"], OFF_RS_TRIP=resident["trips"], OFF_RS_WTRIP=resident["wtrip"],
+        OFF_RS_SPLIT=resident["split"], OFF_RS_ZBLK=resident["zblk"], OFF_RS_RR=rs_rr,
+        OFF_RS_INMETA=image["meta"], OFF_RS_ABMETA=image["ab_meta"],
+        OFF_RS_LTI=np.asarray(
+            [[g["n"], g["m"], g["N"], g["img_a"], g["img_b"], g["tab_a"], g["tab_b"], g["tab_p"]]
+             for g in groups], dtype=np.int32).reshape(-1),
+        OFF_RS_DPAR=rs_dpar.reshape(-1), OFF_RS_GDESC=gdesc, OFF_RS_GFIX=gfix, OFF_RS_RRWIN=rs_rrwin,
+        DOFF_RS_COEF=resident["coef"], DOFF_RS_CONST=np.array([1.0, 1.0, 0.0, 0.0]),
+        DOFF_RS_DCOEF=rs_dcoef.reshape(-1))
+    return dict(words=words, sections=sections, rr_ok=rr_ok, attrs=dict(workspace=ws, resident=resident))
 
-        def row_of(voff):                                # voff = Workspace.rowstart(row)
-            return np.clip(voff // ws.ldv - ws.row0, 0, max(rtot, 1) - 1)
 
-        def can(row, col):
-            return nz[row, col] | nz[row, col + 1]
+def _csc_back_end(form, fe, groups, csc, rs):
+    """The structural patterns of P and G and, for a plan compiled with ``csc=``, where the stored
+    entries sit (P: in the LDS copy of P, leading dimension no rounded up to even) and, per stored
+    entry (R, c) of G, what a 16-byte piece has for two columns: Workspace.index(row0, c) |
+    Workspace.index(row1, c) << 16, arrow0 | arrow1 << 16 (``rs``: the persistent back end)."""
+    b, gr, no, nc = fe.b, fe.gr, fe.b.no, fe.nc
+    P_pattern, G_pattern = _structural_patterns(form, b, fe.fused, fe.gterms, gr, fe.rtot, fe.ldv, groups)
+    z = np.zeros(0, dtype=np.int32)
+    out = dict(words={}, sections=dict(OFF_CSC_P=z, OFF_CSC_G=z),
+               attrs=dict(P_pattern=P_pattern, G_pattern=G_pattern, csc=None))
+    if csc is None:
+        return out
+    if csc not in ("upper", "full"):
+        raise ValueError("csc: 'upper', 'full' or None")
+    ws = rs["attrs"]["workspace"]                    # (dense: no compact workspace with CSC)
+    if not (rs["words"]["RS_OK"] and _g_pieces(gr, ws, len(b.params))):
+        raise ValueError("this plan does not run on the persistent kernel: assemble dense "
+                         "and convert with export_csc")
+    pm = np.ones((no, no), dtype=bool) if P_pattern is None else P_pattern
+    gm = np.ones((nc, no), dtype=bool) if G_pattern is None else G_pattern
+    p_indptr, p_indices, p_flat = csc_pattern(pm, csc == "upper")
+    g_indptr, g_indices, g_flat = csc_pattern(gm)
+    ldp = no + (no & 1)
+    csc_p = ((p_flat // no) * ldp + p_flat % no).astype(np.int32)
+    R, c = g_flat.astype(np.int64) // no, g_flat.astype(np.int64) % no
+    nz = _written(fe)
+    if fe.fused["fd_idx"].size == 0:
+        nz[:] = True
+    voff = _voff(gr, ws)[R]
+    v0, v1, a0, a1 = voff[:, 0], voff[:, 1], gr["arrow"][R, 0], gr["arrow"][R, 1]
+    c0, c1 = nz[v0 + c], (gr["naxes"][R] >= 2) & nz[v1 + c]
+    (v0, v1), (a0, a1) = _live_first(c0, c1, (v0, v1), (a0, a1))
+    csc_g = np.stack([(v0 + c) | ((v1 + c) << 16), a0 | (a1 << 16)], axis=1) \
+        .astype(np.uint32).view(np.int32).reshape(-1)
+    out["words"] = dict(CSC_PNNZ=csc_p.size, CSC_GNNZ=csc_g.size // 2, CSC_GSINGLE=int(bool((~(c0 & c1)).all())))
+    out["sections"] = dict(OFF_CSC_P=csc_p, OFF_CSC_G=csc_g)
+    out["attrs"]["csc"] = dict(kind=csc, pnnz=int(p_flat.size), gnnz=int(g_flat.size),
+                               P=(p_indptr, p_indices), G=(g_indptr, g_indices), p_flat=p_flat, g_flat=g_flat)
+    return out
 
-        def inside(row, col):                            # (windows are whole 4-column blocks)
-            return (ws.c0[row] <= col) & (col + 2 <= ws.c0[row] + ws.w[row])
 
-        v0, v1, a0, a1 = recs[R, 0], recs[R, 1], recs[R, 4], recs[R, 5]
-        two = recs[R, 12] >= 2
-        r0, r1 = row_of(v0), row_of(v1)
-        c0, c1 = can(r0, 2 * cp), two & can(r1, 2 * cp)
-        # the piece in the row's window: its index; outside (compact workspace): row 0, zero arrow
-        in0, in1 = inside(r0, 2 * cp), two & inside(r1, 2 * cp)
-        p0 = np.where(in0, v0 + 2 * cp - ws.c0[r0], 0)
-        p1 = np.where(in1 | ~two, v1 + np.where(two, 2 * cp - ws.c0[r1], 0), 0)
-        a0, a1 = np.where(in0, a0, len(b.params)), np.where(in1 | ~two, a1, len(b.params))
-        if not ws.compact:
-            p1 = v1 + 2 * cp                             # (a missing axis: row 0 + the piece's columns)
-        swap = c1 & ~c0                                  # only the second axis can: it goes first
-        p0, p1 = np.where(swap, p1, p0), np.where(swap, p0, p1)
-        a0, a1 = np.where(swap, a1, a0), np.where(swap, a0, a1)
-        single = ~(c0 & c1) | ~live
-        word0 = p0 | (p1 << 16)                          # Workspace.index(row, 2 cp)
-        word1 = a0 | (a1 << 16)
-        rs_gdesc = np.stack([word0, word1], axis=1).astype(np.uint32).view(np.int32).reshape(-1)
-        # A few pieces with two live axes among many with one (the biped's 34-wide phase: x ends
-        # and y begins inside one piece of every two-axis row) would turn every round they sit in
-        # into a two-axis round.  Instead the round stays a one-axis round and adds the second axis
-        # for that lane alone; a thread holds the second axis of at most one of its pieces (RS_GFIX).
-        # (Writing such pieces apart, behind the rounds, leaves 16-byte holes in the lines the
-        # rounds write: partial lines cost the write stream half its rate, tools/run_variant.py.)
-        both = np.flatnonzero(~single)
-        in_mixed_rounds = int((~single.reshape(-1, 64).all(axis=1)).sum()) * 64
-        owners = both % RS_GDESC_THREADS
-        if (both.size and 4 * both.size <= in_mixed_rounds and np.unique(owners).size == both.size
-                and not _os.environ.get('MPCASM_NO_GFIX')):            # (A/B aid: tools/run_variant.py)
-            fix = np.zeros((RS_GDESC_THREADS, 2), dtype=np.int64)
-            fix[:, 0], fix[:, 1] = RS_GFIX_NONE << 16, len(b.params)
-            fix[owners, 0] = p1[both] | ((both // RS_GDESC_THREADS) << 16)
-            fix[owners, 1] = a1[both]
-            rs_gfix, rs_ngfix = fix.astype(np.uint32).view(np.int32).reshape(-1), int(both.size)
-            single = np.ones_like(single)
-        rounds = single.reshape(RS_GDESC_PIECES, RS_GDESC_THREADS // 64, 64).all(axis=2)
-        rs_gsingle = int(sum(1 << (u * (RS_GDESC_THREADS // 64) + w)
-                             for u in range(RS_GDESC_PIECES) for w in range(RS_GDESC_THREADS // 64)
-                             if rounds[u, w]))
-    # ---- CSC hand-off: where the stored entries sit (P: in the LDS copy of P, leading
-    # dimension no rounded up to even) and, per stored entry (R, c) of G, what a 16-byte piece
-    # has for two columns: Workspace.index(row0, c) | Workspace.index(row1, c) << 16, arrow0 | arrow1 << 16
-    P_pattern, G_pattern = _structural_patterns(
-        form, b, fused, gterms, limit_recs, lax_recs, rtot, ldv, no, nc, groups)
-    csc_p = csc_g = np.zeros(0, dtype=np.int32)
-    csc_info, csc_gsingle = None, 0
-    if csc is not None:
-        if csc not in ("upper", "full"):
-            raise ValueError("csc: 'upper', 'full' or None")
-        two_axes = (rr_ok and (b.rtot + 8) * ldv < 65536 and len(b.params) < 65535
-                    and bool((rs_rr.reshape(nc, RS_RR_WORDS)[:, 12] <= 2).all()))
-        if not (resident["ok"] and two_axes):
-            raise ValueError("this plan does not run on the persistent kernel: assemble dense "
-                             "and convert with export_csc")
-        pm = np.ones((no, no), dtype=bool) if P_pattern is None else P_pattern
-        gm = np.ones((nc, no), dtype=bool) if G_pattern is None else G_pattern
-        p_indptr, p_indices, p_flat = csc_pattern(pm, csc == "upper")
-        g_indptr, g_indices, g_flat = csc_pattern(gm)
-        ldp = no + (no & 1)
-        csc_p = ((p_flat // no) * ldp + p_flat % no).astype(np.int32)
-        recs = rs_rr.reshape(nc, RS_RR_WORDS).astype(np.int64)
-        R, c = g_flat.astype(np.int64) // no, g_flat.astype(np.int64) % no
-        nz = np.zeros(max(rtot, 1) * ldv, dtype=bool)
-        nz[fused["fd_idx"]] = True
-        if fused["fd_idx"].size == 0:
-            nz[:] = True
-        v0, v1, a0, a1 = recs[R, 0], recs[R, 1], recs[R, 4], recs[R, 5]
-        c0, c1 = nz[v0 + c], (recs[R, 12] >= 2) & nz[v1 + c]
-        swap = c1 & ~c0                                  # only the second axis can be non-zero
-        v0, v1 = np.where(swap, v1, v0), np.where(swap, v0, v1)
-        a0, a1 = np.where(swap, a1, a0), np.where(swap, a0, a1)
-        csc_g = np.stack([(v0 + c) | ((v1 + c) << 16), a0 | (a1 << 16)], axis=1) \
-            .astype(np.uint32).view(np.int32).reshape(-1)
-        csc_gsingle = int(bool((~(c0 & c1)).all()))
-        csc_info = dict(kind=csc, pnnz=int(p_flat.size), gnnz=int(g_flat.size),
-                        P=(p_indptr, p_indices), G=(g_indptr, g_indices),
-                        p_flat=p_flat, g_flat=g_flat)
-    pmprog = _preview_program(b, pm_rowptr, pm_entbase, pm_entk, pm_entcoef, pmrows)
-    sections += [("OFF_CSC_P", csc_p), ("OFF_CSC_G", csc_g)]
-    # ---- column tables + tiled program (wide problems) ------------------------------------
-    g_rows = []           # per row of G: (workspace row, arrow's parameter slot) of every axis
-    for out0, nrows, naxes, lax0, p_a, a_rows, *_ in limit_recs:
-        for r in range(nrows):
-            g_rows.append([(lax_recs[lax0 + ax][0] + (0 if lax_recs[lax0 + ax][1] == 1 else r),
-                            p_a + (0 if a_rows == 1 else r) * naxes + ax) for ax in range(naxes)])
-    tiled = _tiled_program(b, form, gterms, rowptr, entbase, entk, entcoef, rtot, groups, rr_ok,
-                           g_rows)
-    scan = _scan_tables(b, gterms, rowptr, entbase, entk, entcoef, groups, g_rows, tiled, len(b.params))
-    tiled["scan"] = scan
-    ndt0 = (entcoef.size + pm_entcoef.size + fused["coefpool"].size + resident["coef"].size
-            + diag_coefs.size)
-    doff_delta = ndt0 + (ndt0 & 1) + 4 + rs_dcoef.size + pmprog["pool"].size
+def _preview_back_end(fe):
+    """Tables of the preview kernels: the CSR tables of the preview matrices and their element
+    program (:func:`_preview_program`)."""
+    pm_rowptr, pm_entbase, pm_entk, pm_entcoef = fe.pm
+    prog = _preview_program(fe.b, *fe.pm, fe.attrs["pmrows"])
+    words = dict(PMROWS=fe.attrs["pmrows"], PM_NENT=pm_entcoef.size, PM_NFD=prog["nfd"],
+                 PM_NOPS=prog["ops"].size // 2, PM_NPOOL=prog["pool"].size)
+    sections = dict(OFF_PM_ROWPTR=pm_rowptr, OFF_PM_ENTBASE=pm_entbase, OFF_PM_ENTK=pm_entk,
+                    OFF_PM_MAP=prog["map"], OFF_PM_FDPTR=prog["fd_ptr"], OFF_PM_OP=prog["ops"],
+                    DOFF_PM_ENTCOEF=pm_entcoef, DOFF_PM_POOL=prog["pool"])
+    return dict(words=words, sections=sections, attrs={})
+
+
+def _tiled_back_end(form, fe, groups, csc, rr_ok):
+    """Tables of the tiled kernel and of its scan form, but for the column tables, which point into
+    the plan's own dtab (:func:`_column_sections`)."""
+    b = fe.b
+    tiled = _tiled_program(b, form, fe.gterms, *fe.csr, fe.rtot, groups, rr_ok, fe.gr)
+    scan = tiled["scan"] = _scan_tables(b, fe.gterms, *fe.csr, groups, fe.gr, tiled, len(b.params))
+    t_grow = fe.gr["row"][:, :RS_AXMAX] if rr_ok else -np.ones((fe.nc, RS_AXMAX))
+    words = dict(T_CI_OK=tiled["ci_ok"], T_NOP=tiled["nop"], T_NDELTA=tiled["delta"].size, T_OK=tiled["ok"],
+                 T_NSTAGE=tiled["stages"].shape[0], T_NLTI=tiled["lti"].shape[0], T_WORK=tiled["work"],
+                 T_NGREST=tiled["grest"].size, T_TOEPLITZ=tiled["toeplitz"],
+                 T_SCAN=scan["K"] if scan["ok"] else 0, T_SCAN_NBLK=scan["blk"].shape[0],
+                 T_SCAN_NGREST=scan["grest"].size, T_SCAN_NOTHER=scan["nother"], T_SCAN_FUSED=scan["fused"])
+    sections = dict(
+        OFF_T_STAGE=tiled["stages"].astype(np.uint32).view(np.int32).reshape(-1),
+        OFF_T_LTI=tiled["lti"].astype(np.int32).reshape(-1), OFF_T_LTI_IDS=tiled["lti_ids"].astype(np.int32),
+        OFF_T_GROW=t_grow.astype(np.int32).reshape(-1), OFF_T_SROW=tiled["srow"].astype(np.int32),
+        OFF_T_PIG=tiled["pig"].astype(np.int32), OFF_T_GREST=tiled["grest"].astype(np.int32),
+        OFF_T_BROW0=np.asarray(list(b.base_row0) + [b.total_base_rows], dtype=np.int32),
+        OFF_T_SCAN_BLK=scan["blk"].astype(np.int32).reshape(-1), OFF_T_SCAN_GT=scan["gt"].astype(np.int32).reshape(-1),
+        OFF_T_SCAN_GROW=scan["grow"].astype(np.int32).reshape(-1), OFF_T_SCAN_GREST=scan["grest"].astype(np.int32),
+        OFF_T_SCAN_COLBLK=scan["colblk"].astype(np.int32),
+        T_DOFF_DELTA=tiled["delta"], T_DOFF_SCOEF=tiled["scoef"],
+        T_DOFF_SCAN_GC=scan["gc"], T_DOFF_SCAN_GCOEF=scan["gcoef"])
+    # Sources (U_j read from memory) whose zeros above the diagonal some table of this plan relies
+    # on -- the tile masks and stage classes of the tiled kernel, the CSC patterns: whatever is
+    # bound in their place must be causal too (Assembler.bind_source / rebind_sources check it).
+    generated = {i for g in groups for i in g["ids"]}
+    causal_assumed = sorted(i for i in tiled["causal"] if i not in generated) \
+        if (tiled["ok"] or csc is not None) else []
+    return dict(words=words, sections=sections, attrs=dict(tiled=tiled, causal_assumed=causal_assumed))
+
+
+def _column_sections(fe, tiled, doff_delta):
+    """The tiled kernel's column tables, their entries into the plan's own dtab moved to where the
+    delta table went (``doff_delta``), and f2 (preview.hip): the same column tables unrolled per
+    base row -- entry (element offset in its stream, column of [given | unknowns] | stream << 24)
+    for every covered column -- and, per entry of a definition's row, where its base row sits among
+    all base rows: what a workgroup copies into LDS once and then reads per instance with no table
+    look-up left."""
+    b = fe.b
     ci = tiled["ci"]
     own = (ci[:, :, 1] >> 24) == T_SID_CONST          # offsets into the plan's own dtab
     ci[:, :, 0] += np.where(own, doff_delta, 0)
     ci32 = ci.astype(np.uint32).view(np.int32) if ci.size else np.zeros((0, 0, 2), np.int32)
-    sections += [("OFF_T_CIG", np.ascontiguousarray(ci32[:, :b.ng]).reshape(-1)),
-                 ("OFF_T_CIO", np.ascontiguousarray(ci32[:, b.ng:]).reshape(-1)),
-                 ("OFF_T_STAGE", tiled["stages"].astype(np.uint32).view(np.int32).reshape(-1)),
-                 ("OFF_T_LTI", tiled["lti"].astype(np.int32).reshape(-1)),
-                 ("OFF_T_LTI_IDS", tiled["lti_ids"].astype(np.int32))]
-    t_grow = -np.ones((nc, RS_AXMAX), dtype=np.int32)
-    if rr_ok:
-        for out0, nrows, naxes, lax0, *_ in limit_recs:
-            for r in range(nrows):
-                for ax in range(naxes):
-                    off, rs = lax_recs[lax0 + ax]
-                    t_grow[out0 + r, ax] = off + (0 if rs == 1 else r)
-    sections += [("OFF_T_GROW", t_grow.reshape(-1)),
-                 ("OFF_T_SROW", tiled["srow"].astype(np.int32)),
-                 ("OFF_T_PIG", tiled["pig"].astype(np.int32)),
-                 ("OFF_T_GREST", tiled["grest"].astype(np.int32)),
-                 ("OFF_T_BROW0", np.asarray(list(b.base_row0) + [b.total_base_rows], dtype=np.int32))]
     # the columns some segment of every base variable covers (everywhere else its rows are zero)
     bcols = [np.flatnonzero(colseg >= 0) for colseg in b.colseg]
-    sections += [("OFF_T_BCOLPTR", np.cumsum([0] + [c.size for c in bcols]).astype(np.int32)),
-                 ("OFF_T_BCOLS", (np.concatenate(bcols) if bcols else np.zeros(0)).astype(np.int32))]
-    # f2 (preview.hip): the same column tables unrolled per base row -- entry (element offset in its
-    # stream, column of [given | unknowns] | stream << 24) for every covered column -- and, per entry of
-    # a definition's row, where its base row sits among all base rows: what a workgroup copies into LDS
-    # once and then reads per instance with no table look-up left
     p1ptr, p1ent = np.zeros(1, dtype=np.int64), []
     if tiled["ci_ok"]:
         for bid, cols in enumerate(bcols):
@@ -2029,165 +2074,119 @@ def compile_plan(form, costs=None, limits=None, lti=(), csc=None, workspace="aut
     p1_ok = bool(tiled["ci_ok"]) and (p1ent.size == 0 or (0 <= p1ent[:, 0].min() and p1ent[:, 0].max() < 1 << 31))
     if not p1_ok:
         p1ptr, p1ent = np.zeros(1, dtype=np.int64), np.zeros((0, 2), dtype=np.int64)
+    pm_entbase, pm_entk = fe.pm[1], fe.pm[2]
     p2y = (np.asarray(b.base_row0, dtype=np.int64)[pm_entbase] + pm_entk) if p1_ok and pm_entbase.size \
         else np.zeros(0, dtype=np.int64)
-    sections += [("OFF_T_P1PTR", np.asarray(p1ptr, dtype=np.int32)),
-                 ("OFF_T_P1ENT", p1ent.astype(np.uint32).view(np.int32).reshape(-1)),
-                 ("OFF_T_P2Y", p2y.astype(np.int32))]
-    sw_empty = dict(axes=np.zeros(0), terms=np.zeros(0), lims=np.zeros(0), col=np.zeros(0), cvec=np.zeros(0),
-                    cptr=np.zeros(0), cent=np.zeros(0), gptr=np.zeros(0), gent=np.zeros(0))
-    sw = sweep or sw_empty
-    sections += [("OFF_SW_AXIS", np.asarray(sw["axes"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_TERM", np.asarray(sw["terms"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_LIM", np.asarray(sw["lims"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_COL", np.asarray(sw["col"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_CPTR", np.asarray(sw["cptr"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_CENT", np.asarray(sw["cent"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_GPTR", np.asarray(sw["gptr"]).astype(np.int32).reshape(-1)),
-                 ("OFF_SW_GENT", np.asarray(sw["gent"]).astype(np.int32).reshape(-1))]
-    sections += [("OFF_T_SCAN_BLK", scan["blk"].astype(np.int32).reshape(-1)),
-                 ("OFF_T_SCAN_GT", scan["gt"].astype(np.int32).reshape(-1)),
-                 ("OFF_T_SCAN_GROW", scan["grow"].astype(np.int32).reshape(-1)),
-                 ("OFF_T_SCAN_GREST", scan["grest"].astype(np.int32)),
-                 ("OFF_T_SCAN_COLBLK", scan["colblk"].astype(np.int32))]
-    sections += [("OFF_RS_DPAR", rs_dpar.reshape(-1)), ("OFF_RS_GDESC", rs_gdesc),
-                 ("OFF_RS_GFIX", rs_gfix), ("OFF_RS_RRWIN", rs_rrwin),
-                 ("OFF_PM_MAP", pmprog["map"]), ("OFF_PM_FDPTR", pmprog["fd_ptr"]),
-                 ("OFF_PM_OP", pmprog["ops"])]
-    header = np.zeros(H_WORDS, dtype=np.int32)
-    parts, off = [header], H_WORDS
-    for name, arr in sections:
-        if name == "OFF_OP" and off & 1:          # the kernels read ops as 8-byte pairs
-            parts.append(np.zeros(1, dtype=np.int32))
-            off += 1
-        if name == "OFF_PM_OP" and off & 1:       # ... 8-byte pairs
-            parts.append(np.zeros(1, dtype=np.int32))
-            off += 1
-        if name in ("OFF_RS_RR", "OFF_RS_INMETA", "OFF_RS_ABMETA", "OFF_RS_DPAR", "OFF_RS_PROG",
-                    "OFF_RS_GDESC", "OFF_RS_GFIX", "OFF_CSC_G", "OFF_T_CIG", "OFF_T_CIO", "OFF_T_P1ENT",
-                    "OFF_T_STAGE", "OFF_T_GROW", "OFF_T_SROW", "OFF_T_PIG", "OFF_T_SCAN_BLK",
-                    "OFF_T_SCAN_GT", "OFF_T_SCAN_GROW", "OFF_SW_AXIS", "OFF_SW_TERM", "OFF_SW_LIM") and off & 3:   # ... 16-byte quads
-            pad = 4 - (off & 3)
-            parts.append(np.zeros(pad, dtype=np.int32))
-            off += pad
-        if name == "OFF_RS_TRIP" and off & 7:     # ... 32-byte records (one scalar load each)
-            pad = 8 - (off & 7)
-            parts.append(np.zeros(pad, dtype=np.int32))
-            off += pad
-        header[_H[name]] = off
-        parts.append(arr)
-        off += arr.size
-    dparts = [entcoef, pm_entcoef, fused["coefpool"], resident["coef"], diag_coefs]
-    ndt = sum(part.size for part in dparts)
-    dparts.append(np.zeros(ndt & 1))             # the constant stream starts 16-byte aligned
-    header[_H["DOFF_RS_CONST"]] = ndt + (ndt & 1)
-    dparts.append(np.array([1.0, 1.0, 0.0, 0.0]))
-    header[_H["DOFF_RS_DCOEF"]] = ndt + (ndt & 1) + 4
-    dparts.append(rs_dcoef.reshape(-1))
-    header[_H["RS_NGDESC"]] = rs_gdesc.size // 2
-    header[_H["RS_NGFIX"]] = rs_ngfix
-    header[_H["RS_COMPACT"]], header[_H["RS_LDV"]] = ws.compact, ws.ldv
-    header[_H["RS_VD"]], header[_H["RS_VROW0"]] = ws.vd, ws.row0
-    header[_H["DOFF_PM_POOL"]] = ndt + (ndt & 1) + 4 + rs_dcoef.size
-    dparts.append(pmprog["pool"])
-    header[_H["PM_NFD"]], header[_H["PM_NOPS"]] = pmprog["nfd"], pmprog["ops"].size // 2
-    header[_H["PM_NPOOL"]] = pmprog["pool"].size
-    assert sum(part.size for part in dparts) == doff_delta
-    dparts.append(tiled["delta"])
-    header[_H["T_DOFF_DELTA"]], header[_H["T_NDELTA"]] = doff_delta, tiled["delta"].size
-    header[_H["T_DOFF_SCOEF"]] = doff_delta + tiled["delta"].size
-    dparts.append(tiled["scoef"])
-    header[_H["T_DOFF_SCAN_GC"]] = doff_delta + tiled["delta"].size + tiled["scoef"].size
-    dparts.append(scan["gc"])
-    header[_H["T_DOFF_SCAN_GCOEF"]] = header[_H["T_DOFF_SCAN_GC"]] + scan["gc"].size
-    dparts.append(scan["gcoef"])
-    header[_H["SW_DOFF_CVEC"]] = header[_H["T_DOFF_SCAN_GCOEF"]] + scan["gcoef"].size
-    header[_H["SW_DOFF_CVEC"]] += header[_H["SW_DOFF_CVEC"]] & 1          # (read as 16-byte pairs)
-    dparts.append(np.zeros(int(header[_H["SW_DOFF_CVEC"]]) - sum(part.size for part in dparts)))
-    dparts.append(np.asarray(sw["cvec"], dtype=np.float64))
-    header[_H["SW_NCVEC"]] = np.asarray(sw["cvec"]).size // SW_NMAX
-    if sweep is not None:
-        header[_H["SW_OK"]], header[_H["SW_N"]], header[_H["SW_M"]] = 1, sweep["n"], sweep["m"]
-        header[_H["SW_HORIZON"]], header[_H["SW_NAXES"]] = sweep["N"], sweep["axes"].shape[0]
-        header[_H["SW_SRC_A"]], header[_H["SW_SRC_B"]] = sweep["src_a"], sweep["src_b"]
-        header[_H["SW_NTERM"]], header[_H["SW_NLIM"]] = sweep["terms"].shape[0], sweep["lims"].shape[0]
-        header[_H["SW_NCENT"]], header[_H["SW_NGENT"]] = sweep["cent"].size, sweep["gent"].shape[0]
-    header[_H["T_SCAN"]] = scan["K"] if scan["ok"] else 0
-    header[_H["T_SCAN_NBLK"]], header[_H["T_SCAN_NGREST"]] = scan["blk"].shape[0], scan["grest"].size
-    header[_H["T_SCAN_NOTHER"]] = scan["nother"]
-    header[_H["T_SCAN_FUSED"]] = scan["fused"]
-    header[_H["T_NGREST"]] = tiled["grest"].size
-    header[_H["T_CI_OK"]], header[_H["T_NOP"]] = tiled["ci_ok"], tiled["nop"]
-    header[_H["T_OK"]], header[_H["T_NSTAGE"]] = tiled["ok"], tiled["stages"].shape[0]
-    header[_H["T_NLTI"]], header[_H["T_WORK"]] = tiled["lti"].shape[0], tiled["work"]
-    header[_H["T_TOEPLITZ"]] = tiled["toeplitz"]
-    header[_H["T_NP1"]] = p1ent.shape[0] if p1_ok else -1
-    dtab = np.concatenate(dparts).astype(np.float64)
-    params = np.asarray(b.params, dtype=np.float64)
-    header[_H["MAGIC"]], header[_H["VERSION"]] = PLAN_MAGIC, PLAN_VERSION
-    header[_H["NG"]], header[_H["NO"]], header[_H["NC"]] = b.ng, no, nc
-    header[_H["NPARAMS"]] = params.size
-    header[_H["NSRC"]], header[_H["NBASE"]] = len(b.sources), len(b.base_rows)
-    header[_H["NSEG"]], header[_H["RTOT"]], header[_H["NENT"]] = len(b.segments), rtot, entcoef.size
-    header[_H["NGTERM"]], header[_H["NLIMIT"]] = len(gterms), len(limit_recs)
-    header[_H["NLAX"]], header[_H["PMROWS"]] = len(lax_recs), pmrows
-    header[_H["PM_NENT"]], header[_H["LDV"]] = pm_entcoef.size, ldv
-    header[_H["DOFF_ENTCOEF"]], header[_H["DOFF_PM_ENTCOEF"]] = 0, entcoef.size
-    header[_H["FUSED_OK"]], header[_H["ARENA_TOTAL"]] = fused["ok"], fused["arena_total"]
-    header[_H["NFD"]], header[_H["NOPS"]] = fused["fd_idx"].size, fused["ops"].size // 2
-    header[_H["NCOEF"]] = fused["coefpool"].size
-    header[_H["DOFF_COEFPOOL"]] = entcoef.size + pm_entcoef.size
-    header[_H["RS_OK"]], header[_H["RS_JC"]] = resident["ok"], resident["jc"]
-    header[_H["RS_SYM"]] = resident["sym"]
-    header[_H["RS_NTRIP"]] = resident["ntrip"]
-    header[_H["RS_GSINGLE"]] = rs_gsingle
-    header[_H["CSC_PNNZ"]], header[_H["CSC_GNNZ"]] = csc_p.size, csc_g.size // 2
-    header[_H["CSC_GSINGLE"]] = csc_gsingle
-    header[_H["RS_NZBLK"]] = resident["zblk"].size
-    header[_H["RS_NSPLIT"]] = resident["split"].size
-    header[_H["RS_UNIT"]], header[_H["RS_NCHUNK"]] = image["unit"], image["nchunk"]
-    header[_H["RS_IMG"]] = image["img"]
-    header[_H["RS_IMG_DMA"]] = image["dma"]
-    header[_H["RS_NLTI"]] = len(groups)
-    header[_H["RS_AB"]] = image["ab"]
-    header[_H["RS_IMG_GIVEN"]], header[_H["RS_IMG_PARAMS"]] = image["given"], image["params"]
-    if rs_rr.size != nc * RS_RR_WORDS:
-        header[_H["RS_OK"]] = 0                  # a constraint with more than RS_AXMAX axes
-    else:                                        # G by 16-byte pieces from the packed words
-        header[_H["RR_PACKED"]] = int(packed_ok)
-    header[_H["DOFF_RS_COEF"]] = entcoef.size + pm_entcoef.size + fused["coefpool"].size
-    header[_H["DOFF_DIAGCOEF"]] = (entcoef.size + pm_entcoef.size + fused["coefpool"].size
-                                   + resident["coef"].size)
-    header[_H["NDIAGCOEF"]] = diag_coefs.size
-    header[_H["NITAB"]], header[_H["NDTAB"]] = off, dtab.size
+    sections = dict(OFF_T_CIG=np.ascontiguousarray(ci32[:, :b.ng]).reshape(-1),
+                    OFF_T_CIO=np.ascontiguousarray(ci32[:, b.ng:]).reshape(-1),
+                    OFF_T_BCOLPTR=np.cumsum([0] + [c.size for c in bcols]).astype(np.int32),
+                    OFF_T_BCOLS=(np.concatenate(bcols) if bcols else np.zeros(0)).astype(np.int32),
+                    OFF_T_P1PTR=np.asarray(p1ptr, dtype=np.int32),
+                    OFF_T_P1ENT=p1ent.astype(np.uint32).view(np.int32).reshape(-1),
+                    OFF_T_P2Y=p2y.astype(np.int32))
+    return dict(T_NP1=p1ent.shape[0] if p1_ok else -1), sections
 
-    plan = Plan()
-    plan.itab = np.concatenate(parts).astype(np.int32)
-    plan.dtab = dtab
-    plan.ng, plan.no, plan.nc = b.ng, no, nc
-    plan.sources = b.sources
-    plan.params = params
-    plan.param_slots = b.param_slots
-    plan.param_getters = b.param_getters
+
+# The sections of the two tables in order, each (header word of its offset, alignment in words
+# counted from the start of its table): the kernels read ops as 8-byte pairs, some tables as
+# 16-byte quads, the trip records as 32-byte records (one scalar load each); the constant stream
+# of the persistent kernel and the sweep's cvec start 16-byte aligned.
+_ITAB = [
+    ("OFF_SEG", 1), ("OFF_COLSEG", 1), ("OFF_ROWPTR", 1), ("OFF_ENTBASE", 1), ("OFF_ENTK", 1),
+    ("OFF_GTERM", 1), ("OFF_LIMIT", 1), ("OFF_LAX", 1), ("OFF_ROWLIMIT", 1),
+    ("OFF_PM_ROWPTR", 1), ("OFF_PM_ENTBASE", 1), ("OFF_PM_ENTK", 1),
+    ("OFF_ARENA", 1), ("OFF_FD_IDX", 1), ("OFF_FD_PTR", 1), ("OFF_OP", 2),
+    ("OFF_RS_PROG", 4), ("OFF_RS_SRC", 1), ("OFF_RS_GIDX", 1), ("OFF_RS_DST", 1), ("OFF_RS_TRIP", 8),
+    ("OFF_RS_WTRIP", 1), ("OFF_RS_SPLIT", 1), ("OFF_RS_ZBLK", 1), ("OFF_RS_RR", 4),
+    ("OFF_RS_INMETA", 4), ("OFF_RS_ABMETA", 4), ("OFF_RS_LTI", 1),
+    ("OFF_CSC_P", 1), ("OFF_CSC_G", 4),
+    ("OFF_T_CIG", 4), ("OFF_T_CIO", 4), ("OFF_T_STAGE", 4), ("OFF_T_LTI", 1), ("OFF_T_LTI_IDS", 1),
+    ("OFF_T_GROW", 4), ("OFF_T_SROW", 4), ("OFF_T_PIG", 4), ("OFF_T_GREST", 1), ("OFF_T_BROW0", 1),
+    ("OFF_T_BCOLPTR", 1), ("OFF_T_BCOLS", 1), ("OFF_T_P1PTR", 1), ("OFF_T_P1ENT", 4), ("OFF_T_P2Y", 1),
+    ("OFF_SW_AXIS", 4), ("OFF_SW_TERM", 4), ("OFF_SW_LIM", 4), ("OFF_SW_COL", 1), ("OFF_SW_CPTR", 1),
+    ("OFF_SW_CENT", 1), ("OFF_SW_GPTR", 1), ("OFF_SW_GENT", 1),
+    ("OFF_T_SCAN_BLK", 4), ("OFF_T_SCAN_GT", 4), ("OFF_T_SCAN_GROW", 4), ("OFF_T_SCAN_GREST", 1),
+    ("OFF_T_SCAN_COLBLK", 1),
+    ("OFF_RS_DPAR", 4), ("OFF_RS_GDESC", 4), ("OFF_RS_GFIX", 4), ("OFF_RS_RRWIN", 1),
+    ("OFF_PM_MAP", 1), ("OFF_PM_FDPTR", 1), ("OFF_PM_OP", 2),
+]
+_DTAB = [
+    ("DOFF_ENTCOEF", 1), ("DOFF_PM_ENTCOEF", 1), ("DOFF_COEFPOOL", 1), ("DOFF_RS_COEF", 1),
+    ("DOFF_DIAGCOEF", 1), ("DOFF_RS_CONST", 2), ("DOFF_RS_DCOEF", 1), ("DOFF_PM_POOL", 1),
+    ("T_DOFF_DELTA", 1), ("T_DOFF_SCOEF", 1), ("T_DOFF_SCAN_GC", 1), ("T_DOFF_SCAN_GCOEF", 1),
+    ("SW_DOFF_CVEC", 2),
+]
+
+
+def _layout(words, sections, late):
+    """``itab, dtab`` from the header words and the sections (named by the header word of their
+    offset): the dtab sections in _DTAB order, then the header and the itab sections in _ITAB
+    order, each on its alignment, zeros in between.  ``late(offsets)``, called once the dtab
+    offsets are known, returns the words and sections that depend on them."""
+    def place(order, start, dtype):
+        parts, off = [], start
+        for name, align in order:
+            parts.append(np.zeros(-off % align, dtype=dtype))
+            off += parts[-1].size
+            words[name] = off
+            parts.append(sections.pop(name))
+            off += parts[-1].size
+        return parts, off
+
+    dparts, words["NDTAB"] = place(_DTAB, 0, np.float64)
+    more_words, more_sections = late({name: words[name] for name, _ in _DTAB})
+    words.update(more_words)
+    sections.update(more_sections)
+    header = np.zeros(H_WORDS, dtype=np.int32)
+    iparts, words["NITAB"] = place(_ITAB, H_WORDS, np.int32)
+    assert not sections, "sections without a place: %s" % sorted(sections)
+    words.update(MAGIC=PLAN_MAGIC, VERSION=PLAN_VERSION)
+    for name, value in words.items():
+        header[_H[name]] = value
+    return np.concatenate([header] + iparts).astype(np.int32), np.concatenate(dparts).astype(np.float64)
+
+
+def compile_plan(form, costs=None, limits=None, lti=(), csc=None, workspace="auto", ltv=()):
+    """Compile ``form`` (an up-to-date Formulation: sizes and IDs current).
+
+    ``costs``: dict name -> Cost to include (default ``form.goals``);
+    ``limits``: list of Constraint in stacking order (default: every limit of
+    ``form.constraints`` then of ``form.constraint_boxes``, body.py:306-315);
+    ``lti``: names of ExtendedSystem dynamics whose horizon matrices the assembly kernel
+    generates on chip from per-instance ``(A, B)`` instead of reading ``S, U`` (K1 fused into
+    the assembly; only the persistent kernel can run such a plan);
+    ``ltv``: ONE name of an ExtendedSystem whose dynamics differ from step to step and instance to
+    instance, ``x+ = A_k x + B_k u`` (BASELINE config C5): the sweep kernel (csrc/sweep.hip) takes
+    ``A (N, n, n)``, ``B (N, n, m)`` per instance and assembles without forming a horizon matrix
+    (:func:`_sweep_tables` states what the formulation has to be for that; ValueError otherwise).
+    The reference has no such path (``dynamics.py:222-231`` re-extends ONE pair per tick): pinned to
+    it where all steps share one pair;
+    ``csc``: ``"upper"`` or ``"full"`` -- the plan's assembly writes, instead of dense P and G,
+    the ``data`` arrays of their CSC forms on the structural pattern (P: its upper triangle /
+    all of it), what ``scipy.sparse.csc_matrix(Q)``, ``csc_matrix(A)`` hand the solver in
+    biped_mpc_loop.py:57-58: ``P`` becomes ``(B, plan.csc["pnnz"])``, ``G``
+    ``(B, plan.csc["gnnz"])``; ``plan.csc["P"]``, ``plan.csc["G"]`` hold ``(indptr, indices)``.
+    Only the persistent kernel writes this form: ValueError when the plan cannot run there.
+    """
+    if costs is None:
+        costs = form.goals
+    if limits is None:
+        limits = [l for group in form.constraints.values() for l in group]
+        limits += [l for box in form.constraint_boxes.values() for l in box.constraints]
+    fe = _front_end(form, costs, limits)
+    groups = _lti_groups(form, fe.b.sources, lti)
+    sweep = _sweep_back_end(form, fe, lti, ltv, csc)
+    rs = _persistent_back_end(fe, groups, workspace, csc)
+    cs = _csc_back_end(form, fe, groups, csc, rs)
+    tiled = _tiled_back_end(form, fe, groups, csc, rs["rr_ok"])
+    plan, words, sections = Plan(), {}, {}
+    for part in (vars(fe), sweep, rs, cs, _preview_back_end(fe), tiled):
+        words.update(part["words"])
+        sections.update(part["sections"])
+        for name, value in part["attrs"].items():
+            setattr(plan, name, value)
+    plan.itab, plan.dtab = _layout(words, sections, lambda doff: _column_sections(
+        fe, plan.tiled, doff["T_DOFF_DELTA"]))
     plan.fingerprint = structure_fingerprint(costs, limits)
-    plan.pm_rows, plan.pmrows = pm_rows, pmrows
-    plan.rtot, plan.ldv, plan.workspace = rtot, ldv, ws
-    plan.limit_rows = limit_rows
-    plan.optim_ID = {v: form.optim_ID[v] for v in form.optim_variables}
-    plan.given_ID = {v: form.given_ID[v] for v in form.given_variables}
-    plan.n_gterms = len(gterms)
-    plan.resident = resident
-    plan.P_pattern, plan.G_pattern = P_pattern, G_pattern
-    plan.csc = csc_info
     plan.lti = [dict(name=g["name"], n=g["n"], m=g["m"], N=g["N"], ids=list(g["ids"])) for g in groups]
-    plan.ltv = ([dict(name=tuple(ltv)[0], n=sweep["n"], m=sweep["m"], N=sweep["N"],
-                      ids=[sweep["src_a"], sweep["src_b"]])] if sweep is not None else [])
-    plan.sweep = sweep
-    plan.tiled = tiled
-    # Sources (U_j read from memory) whose zeros above the diagonal some table of this plan relies
-    # on -- the tile masks and stage classes of the tiled kernel, the CSC patterns: whatever is
-    # bound in their place must be causal too (Assembler.bind_source / rebind_sources check it).
-    generated = {i for g in groups for i in g["ids"]}
-    plan.causal_assumed = sorted(i for i in tiled["causal"] if i not in generated) \
-        if (tiled["ok"] or csc is not None) else []
     return plan
