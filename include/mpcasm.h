@@ -367,6 +367,53 @@ int mpcasm_admm(int no, int nc, const double* d_P, const double* d_q, const doub
                 double sigma, double alpha, int iters, int warm, int batch, double* d_kinv, int kinv_valid,
                 void* stream);
 
+/* Per-instance outcome of mpcasm_qp_solve (OSQP's status values).  These are written to d_status on the
+ * device; they are not return codes of a library function. */
+enum {
+  MPCASM_QP_SOLVED = 1,               /* both residuals within eps_abs + eps_rel * their scale       */
+  MPCASM_QP_MAX_ITER = -2,            /* max_iter iterations without a verdict                        */
+  MPCASM_QP_PRIMAL_INFEASIBLE = -3,   /* the step of y certifies that no x has Gx <= h                */
+  MPCASM_QP_DUAL_INFEASIBLE = -4,     /* the step of x is a direction the cost falls along without end */
+  MPCASM_QP_NON_CVX = -7              /* P + sigma I + rho G'G not positive definite, or rho <= 0       */
+};
+
+/* The solve to tolerance: mpcasm_admm's iteration (same operands, same iterates) with OSQP's stopping
+ * rules and adaptive rho (Stellato et al. 2020, sections 3.4 and 5.2; no problem scaling, no polishing),
+ * every instance on its own and nothing read back to the host -- a tick of the walking loop can be
+ * captured in one graph.  After iteration k, when k % check_every == 0 or k == max_iter, with
+ * infinity norms and dx = x_k - x_{k-1}, dy = max(y_k - y_{k-1}, 0):
+ *   solved              |Gx - z| <= eps_abs + eps_rel max(|Gx|, |z|)  and
+ *                       |Px + q + G'y| <= eps_abs + eps_rel max(|Px|, |G'y|, |q|)
+ *   primal infeasible   |dy| > 1e-30, h'dy < -eps_prim_inf |dy|, |G'dy| < eps_prim_inf |dy|
+ *   dual infeasible     |dx| > 1e-30, q'dx < -eps_dual_inf |dx|, |P dx| < eps_dual_inf |dx|,
+ *                       max_i (G dx)_i < eps_dual_inf |dx|
+ * tested in that order; the first that holds ends the instance (MPCASM_QP_*; d_iters[b] = k).  None within
+ * max_iter: MPCASM_QP_MAX_ITER, d_iters[b] = max_iter.  All four eps may be 0 (no instance stops early).
+ * adaptive_rho_interval > 0 (a multiple of check_every): at a check with k % adaptive_rho_interval == 0 that
+ * decides nothing and is not the last iteration,
+ *   rho' = rho sqrt((r_p / (max(|Gx|, |z|) + 1e-30)) / (r_d / (max(|Px|, |G'y|, |q|) + 1e-30)))
+ * clipped to [1e-6, 1e6]; when rho' > 5 rho or rho' < rho / 5 the instance takes rho' (K formed, factored
+ * and inverted again; x, y, z carry over).
+ * d_rho [batch]: in, the step each instance starts with; out, the step it ended with.  A rho <= 0, or a
+ * K that is not positive definite (at the start or after a change of rho): MPCASM_QP_NON_CVX, NaNs in
+ * x, y, z, d_res and d_kinv.  d_status, d_iters [batch]; d_res (may be NULL) [batch][2]: |Gx - z| and
+ * |Px + q + G'y| of the returned iterate.  The other operands are mpcasm_admm's, except that d_P is
+ * read also with kinv_valid (the dual residual needs Px); with kinv_valid, d_kinv[b] must be the
+ * inverse for d_rho[b] as passed in.  d_kinv (may be NULL) holds the inverse for the final rho on return:
+ * the next tick on the same model passes d_kinv and d_rho back and factors nothing.
+ * MPCASM_ERR_ARG: an eps not finite or < 0, max_iter < 0, check_every < 1, an adaptive_rho_interval < 0
+ * or not a multiple of check_every, or what mpcasm_admm refuses; MPCASM_ERR_LIMIT as mpcasm_admm. */
+int mpcasm_qp_solve(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                    const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                    double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                    double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                    int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                    int kinv_valid, void* stream);
+/* Needs no device: the LDS bytes one instance of mpcasm_qp_solve (and of mpcasm_admm: the same layout)
+ * takes for no unknowns and nc limits (*out; MPCASM_ERR_LIMIT too when that exceeds what a workgroup
+ * may have). */
+int mpcasm_qp_solve_lds_bytes(int no, int nc, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,15 @@
 // iterates by rounding only.  LDS per instance: no (no|1) doubles for K^-1, max(nc, no) (no|1) for G (and,
 // before G is needed, L^-1), the vectors and the partial sums: 40 KB for the biped at N = 16 (no = 36,
 // nc = 76): four instances per CU.
+//
+// The solve mode (mpcasm_qp_solve, admm_kernel<true>) is the same kernel with OSQP's stopping rules on top:
+// every check_every iterations (and at the last) the instance tests "solved", "primal infeasible", "dual
+// infeasible" in that order on the iterate and its step (l = -inf, u = h; infinity norms; no scaling), one
+// decision per workgroup behind a barrier, and a finished workgroup retires.  Every adaptive_rho_interval
+// iterations rho moves to OSQP's rho * sqrt((r_p / scale_p) / (r_d / scale_d)) when that is 5x off: K is formed,
+// factored and inverted again in LDS with the same code.  The checks read P from global memory (it is not
+// in LDS after K is formed) and use the partial-sum buffers as scratch: the layout is the same as the plain
+// iteration's, so is the LDS an instance takes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -87,15 +96,27 @@ __device__ __forceinline__ double dot4(const double* a, int sa, const double* b,
   return (s0 + s1) + (s2 + s3);
 }
 
+// what the solve mode adds to the kernel's arguments (unused by the plain iteration)
+struct SolveArgs {
+  double* rho;        // [batch] in: the step an instance starts with; out: the one it ended with
+  int32_t* status;    // [batch] MPCASM_QP_*
+  int32_t* iters;     // [batch] the iterations an instance ran
+  double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
+  int check_every, adaptive_rho_interval;
+};
+
 // One workgroup of four wavefronts per instance.  Everything that is a sum over rows or columns is cut in
 // four -- wavefront w takes the terms i = w, w + 4, ... -- and the partial sums meet in LDS behind a barrier:
 // one wavefront per instance (the first version) had nothing to hide an LDS round trip behind and spent
 // 10 000 cycles per iteration on three matrix-vector products of 36 x 76.
+// SOLVE: `iters` is max_iter, rho is the instance's s.rho[inst] and the loop ends at the first check that
+// decides; the iterates of the plain iteration are the same as before.
+template <bool SOLVE>
 __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     int no, int nc, const double* __restrict__ P, const double* __restrict__ q,
     const double* __restrict__ G, const double* __restrict__ h, double* __restrict__ X,
     double* __restrict__ Y, double* __restrict__ Z, double* __restrict__ res, double rho, double sigma,
-    double alpha, int iters, int warm, int batch, double* __restrict__ Kinv, int kinv_valid) {
+    double alpha, int iters, int warm, int batch, double* __restrict__ Kinv, int kinv_valid, SolveArgs s) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -127,6 +148,7 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
   // ---- K = P + sigma I + rho G'G ------------------------------------------------------------------
   // (a caller whose P and G did not change since the last call -- the same model and structure, a new
   // `given` -- hands K^-1 back in: no factorisation, the larger part of a call of 25 iterations)
+  if constexpr (SOLVE) rho = s.rho[inst];
   const bool reuse = Kinv != nullptr && kinv_valid != 0;
   load_g();
   for (int e = tid; e < no; e += ADMM_BLOCK) {
@@ -140,23 +162,21 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     zs[e] = warm ? Z[(size_t)inst * nc + e] : fmin(0.0, hv);   // (a cold start: z = min(G x, h) with x = 0)
   }
   __syncthreads();
-  for (int e = tid; e < no * no; e += ADMM_BLOCK) {
-    const int a = e / no, b = e - a * no;
-    if (reuse) {
-      Mi[a * ld + b] = Kinv[(size_t)inst * no * no + e];
-      continue;
-    }
-    const double acc = dot4(Gs + a, ld, Gs + b, ld, nc, 0.0);
-    Mi[a * ld + b] = fma(rho, acc, Pb[e]) + (a == b ? sigma : 0.0);
-  }
-  __syncthreads();
 
-  bool ok = true;
-  if (!reuse) {
+  // K from G in LDS and P in memory, factored and inverted into Mi (false: K is not positive definite);
+  // the solve mode calls it again when rho moves
+  auto factor = [&]() -> bool {
+    for (int e = tid; e < no * no; e += ADMM_BLOCK) {
+      const int a = e / no, b = e - a * no;
+      const double acc = dot4(Gs + a, ld, Gs + b, ld, nc, 0.0);
+      Mi[a * ld + b] = fma(rho, acc, Pb[e]) + (a == b ? sigma : 0.0);
+    }
+    __syncthreads();
+    bool good = true;
     // ---- Cholesky, in place (the lower triangle): K = L L' ----------------------------------------
     for (int k = 0; k < no; ++k) {
       const double dkk = Mi[k * ld + k];
-      ok = ok && dkk > 0.0;
+      good = good && dkk > 0.0;
       const double d = sqrt(dkk > 0.0 ? dkk : 1.0);
       __syncthreads();
       for (int i = k + tid; i < no; i += ADMM_BLOCK) Mi[i * ld + k] = i == k ? d : Mi[i * ld + k] / d;
@@ -188,20 +208,37 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     __syncthreads();
     if (Kinv != nullptr)
       for (int e = tid; e < no * no; e += ADMM_BLOCK)
-        Kinv[(size_t)inst * no * no + e] = ok ? Mi[(e / no) * ld + e % no] : __builtin_nan("");
+        Kinv[(size_t)inst * no * no + e] = good ? Mi[(e / no) * ld + e % no] : __builtin_nan("");
     load_g();   // (the factorisation used G's place for L^-1)
     __syncthreads();
+    return good;
+  };
+
+  bool ok = true;
+  if (SOLVE && !(rho > 0.0)) {   // (no step to take: the solve calls the instance not convex)
+    ok = false;
+    if (Kinv != nullptr)
+      for (int e = tid; e < no * no; e += ADMM_BLOCK) Kinv[(size_t)inst * no * no + e] = __builtin_nan("");
+  } else if (reuse) {
+    for (int e = tid; e < no * no; e += ADMM_BLOCK) Mi[(e / no) * ld + e % no] = Kinv[(size_t)inst * no * no + e];
+    __syncthreads();
+  } else {
+    ok = factor();
   }
 
   // ---- the iterations: six short phases, a barrier behind each; every sum a strided inner product with
   // several reads in flight (dot4) -------------------------------------------------------------------------
-  const double inv_rho = 1.0 / rho;
+  double inv_rho = 1.0 / rho;
   // wavefront w's share of a sum over `count` terms: i = w, w + 4, ...
   const int rows_w = nc > wave ? (nc - wave + ADMM_WAVES - 1) / ADMM_WAVES : 0;
   const int cols_w = no > wave ? (no - wave + ADMM_WAVES - 1) / ADMM_WAVES : 0;
+  int status = ok ? MPCASM_QP_MAX_ITER : MPCASM_QP_NON_CVX, ran = ok ? iters : 0;
   for (int r = tid; r < nc; r += ADMM_BLOCK) vs[r] = fma(rho, zs[r], -ys[r]);
   __syncthreads();
-  for (int it = 0; it < iters; ++it) {
+  for (int it = 0; it < (SOLVE && !ok ? 0 : iters); ++it) {
+    // (solve mode: a check after this iteration -- it keeps the step dx in pb, dy in pa)
+    const int k = it + 1;
+    const bool due = SOLVE && (k % s.check_every == 0 || k == iters);
     // pa[w][c] = sum over this wavefront's rows of G[r][c] v[r]
     for (int c = lane; c < no; c += 64)
       pa[wave * lp + c] = dot4(Gs + wave * ld + c, ADMM_WAVES * ld, vs + wave, ADMM_WAVES, rows_w, 0.0);
@@ -215,8 +252,10 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     __syncthreads();
     for (int c = tid; c < no; c += ADMM_BLOCK) {
       const double xtc = (pbuf[c] + pbuf[no + c]) + (pbuf[2 * no + c] + pbuf[3 * no + c]);
+      const double xo = xs[c], xn = fma(alpha, xtc, (1.0 - alpha) * xo);
       xt[c] = xtc;
-      xs[c] = fma(alpha, xtc, (1.0 - alpha) * xs[c]);
+      xs[c] = xn;
+      if (due) pbuf[c] = xn - xo;   // (this thread's own column: no other thread reads it in this phase)
     }
     __syncthreads();
     // pa[w][r] = sum over this wavefront's c of G[r][c] xt[c]
@@ -227,12 +266,98 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
       const double zt = (pa[r] + pa[lp + r]) + (pa[2 * lp + r] + pa[3 * lp + r]);
       const double zr = fma(alpha, zt, (1.0 - alpha) * zs[r]);
       const double zn = fmin(fma(ys[r], inv_rho, zr), hs[r]);
-      const double yn = fma(rho, zr - zn, ys[r]);
+      const double yo = ys[r], yn = fma(rho, zr - zn, yo);
       ys[r] = yn;
       zs[r] = zn;
       vs[r] = fma(rho, zn, -yn);
+      if (due) pa[r] = fmax(yn - yo, 0.0);   // (dy projected on the normal cone of (-inf, h])
     }
     __syncthreads();
+    if constexpr (SOLVE) {
+      if (due) {
+        // one wavefront per test, each over all rows or columns: the verdicts need no partial sums
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = -INFINITY;
+        if (wave == 0) {          // r_p = |Gx - z|, its scale max(|Gx|, |z|)
+          for (int r = lane; r < nc; r += 64) {
+            const double gx = dot4(Gs + r * ld, 1, xs, 1, no, 0.0);
+            a0 = fmax(a0, fabs(gx - zs[r]));
+            a1 = fmax(a1, fmax(fabs(gx), fabs(zs[r])));
+          }
+        } else if (wave == 1) {   // r_d = |Px + q + G'y|, its scale max(|Px|, |G'y|, |q|)
+          for (int c = lane; c < no; c += 64) {
+            const double px = dot4(Pb + (size_t)c * no, 1, xs, 1, no, 0.0);
+            const double gty = dot4(Gs + c, ld, ys, 1, nc, 0.0);
+            a0 = fmax(a0, fabs(px + qs[c] + gty));
+            a1 = fmax(a1, fmax(fabs(px), fmax(fabs(gty), fabs(qs[c]))));
+          }
+        } else if (wave == 2) {   // |dy|, h'dy, |G'dy|
+          for (int r = lane; r < nc; r += 64) {
+            a0 = fmax(a0, pa[r]);
+            a1 = fma(hs[r], pa[r], a1);
+          }
+          for (int c = lane; c < no; c += 64) a2 = fmax(a2, fabs(dot4(Gs + c, ld, pa, 1, nc, 0.0)));
+        } else {                  // |dx|, q'dx, |P dx|, max(G dx)
+          for (int c = lane; c < no; c += 64) {
+            a0 = fmax(a0, fabs(pbuf[c]));
+            a1 = fma(qs[c], pbuf[c], a1);
+            a2 = fmax(a2, fabs(dot4(Pb + (size_t)c * no, 1, pbuf, 1, no, 0.0)));
+          }
+          for (int r = lane; r < nc; r += 64) a3 = fmax(a3, dot4(Gs + r * ld, 1, pbuf, 1, no, 0.0));
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+          const double b1 = __shfl_xor(a1, off, 64);
+          a0 = fmax(a0, __shfl_xor(a0, off, 64));
+          a1 = wave >= 2 ? a1 + b1 : fmax(a1, b1);
+          a2 = fmax(a2, __shfl_xor(a2, off, 64));
+          a3 = fmax(a3, __shfl_xor(a3, off, 64));
+        }
+        __syncthreads();   // (dx and dy read: their places take the verdicts)
+        if (lane == 0) {
+          if (wave == 0) pa[0] = a0, pa[1] = a1;
+          else if (wave == 1) pa[2] = a0, pa[3] = a1;
+          else if (wave == 2)
+            pbuf[0] = a0 > 1e-30 && a1 < -s.eps_prim_inf * a0 && a2 < s.eps_prim_inf * a0 ? 1.0 : 0.0;
+          else
+            pbuf[1] = a0 > 1e-30 && a1 < -s.eps_dual_inf * a0 && a2 < s.eps_dual_inf * a0 &&
+                      a3 < s.eps_dual_inf * a0 ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        const double rp = pa[0], sp = pa[1], rd = pa[2], sd = pa[3];
+        const int verdict = rp <= s.eps_abs + s.eps_rel * sp && rd <= s.eps_abs + s.eps_rel * sd ? MPCASM_QP_SOLVED
+                            : pbuf[0] != 0.0 ? MPCASM_QP_PRIMAL_INFEASIBLE
+                            : pbuf[1] != 0.0 ? MPCASM_QP_DUAL_INFEASIBLE : 0;
+        double rn = rho;   // (OSQP's step: the two residuals equally far from their tolerances; NaN: no move)
+        if (verdict == 0 && s.adaptive_rho_interval > 0 && k % s.adaptive_rho_interval == 0 && k < iters) {
+          rn = rho * sqrt((rp / (sp + 1e-30)) / (rd / (sd + 1e-30)));
+          rn = rn < 1e-6 ? 1e-6 : rn > 1e6 ? 1e6 : rn;
+        }
+        __syncthreads();   // (the verdicts read by every thread: the next phase writes over them)
+        if (verdict != 0) {
+          status = verdict;
+          ran = k;
+          break;
+        }
+        if (rn > 5.0 * rho || rn < rho / 5.0) {
+          rho = rn;
+          inv_rho = 1.0 / rho;
+          if (!factor()) {
+            ok = false;
+            status = MPCASM_QP_NON_CVX;
+            ran = k;
+            break;
+          }
+          for (int r = tid; r < nc; r += ADMM_BLOCK) vs[r] = fma(rho, zs[r], -ys[r]);
+          __syncthreads();
+        }
+      }
+    }
+  }
+  if constexpr (SOLVE) {
+    if (tid == 0) {
+      s.rho[inst] = rho;
+      s.status[inst] = status;
+      s.iters[inst] = ran;
+    }
   }
 
   // ---- results; OSQP's residuals |Gx - z|_inf, |Px + q + G'y|_inf -------------------------------
@@ -281,11 +406,30 @@ int launch_admm(int no, int nc, const double* P, const double* q, const double* 
   const size_t lds = admm_lds_bytes(no, nc);
   if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
   if (lds > 64 * 1024) {
-    *err = allow_whole_lds(reinterpret_cast<const void*>(admm_kernel));
+    *err = allow_whole_lds(reinterpret_cast<const void*>(admm_kernel<false>));
     if (*err != hipSuccess) return MPCASM_ERR_HIP;
   }
-  hipLaunchKernelGGL(admm_kernel, dim3((unsigned)batch), dim3(ADMM_BLOCK), lds, stream, no, nc, P, q, G,
-                     h, x, y, z, res, rho, sigma, alpha, iters, warm, batch, kinv, kinv_valid);
+  hipLaunchKernelGGL(admm_kernel<false>, dim3((unsigned)batch), dim3(ADMM_BLOCK), lds, stream, no, nc, P, q, G,
+                     h, x, y, z, res, rho, sigma, alpha, iters, warm, batch, kinv, kinv_valid, SolveArgs{});
+  *err = hipGetLastError();
+  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+}
+
+int launch_qp_solve(int no, int nc, const double* P, const double* q, const double* G, const double* h,
+                    double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
+                    double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
+                    int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
+                    int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err) {
+  const size_t lds = admm_lds_bytes(no, nc);   // (the solve mode's scratch lies in the same layout)
+  if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
+  if (lds > 64 * 1024) {
+    *err = allow_whole_lds(reinterpret_cast<const void*>(admm_kernel<true>));
+    if (*err != hipSuccess) return MPCASM_ERR_HIP;
+  }
+  const SolveArgs s{rho, status, iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
+                    adaptive_rho_interval};
+  hipLaunchKernelGGL(admm_kernel<true>, dim3((unsigned)batch), dim3(ADMM_BLOCK), lds, stream, no, nc, P, q, G,
+                     h, x, y, z, res, 0.0, sigma, alpha, max_iter, warm, batch, kinv, kinv_valid, s);
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

@@ -88,10 +88,16 @@ int launch_box_transform_ss(double* params, long long nparams, int batch, const 
                             hipError_t* err);
 int launch_gather(const double* src, long long src_stride, const int32_t* index, int nnz,
                   double* dst, int batch, hipStream_t stream, hipError_t* err);
+size_t admm_lds_bytes(int no, int nc);   // (one instance of mpcasm_admm or mpcasm_qp_solve)
 int launch_admm(int no, int nc, const double* P, const double* q, const double* G, const double* h,
                 double* x, double* y, double* z, double* res, double rho, double sigma, double alpha,
                 int iters, int warm, int batch, double* kinv, int kinv_valid, hipStream_t stream,
                 hipError_t* err);
+int launch_qp_solve(int no, int nc, const double* P, const double* q, const double* G, const double* h,
+                    double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
+                    double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
+                    int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
+                    int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err);
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err);
 

@@ -29,6 +29,15 @@ STATUS = {
     -4: "MPCASM_ERR_NODEVICE",
     -5: "MPCASM_ERR_LIMIT",
 }
+# per-instance outcomes of mpcasm_qp_solve (OSQP's values; written on the device, not return codes)
+QP_SOLVED, QP_MAX_ITER, QP_PRIMAL_INFEASIBLE, QP_DUAL_INFEASIBLE, QP_NON_CVX = 1, -2, -3, -4, -7
+QP_STATUS = {
+    1: "MPCASM_QP_SOLVED",
+    -2: "MPCASM_QP_MAX_ITER",
+    -3: "MPCASM_QP_PRIMAL_INFEASIBLE",
+    -4: "MPCASM_QP_DUAL_INFEASIBLE",
+    -7: "MPCASM_QP_NON_CVX",
+}
 
 # every symbol include/mpcasm.h declares: name -> (restype, argtypes)
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -81,6 +90,10 @@ SIGNATURES = {
                                                     _void_p, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_admm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 + [ctypes.c_double] * 3 +
                     [ctypes.c_int, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_qp_solve": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] +
+                        [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
+                        [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_qp_solve_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_gather": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p,
                                      ctypes.c_int, _void_p]),
     "mpcasm_box_transform": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p,

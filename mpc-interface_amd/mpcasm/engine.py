@@ -11,6 +11,7 @@ kernels of libmpcasm.so through the C ABI (``mpcasm.capi``).
 torch is used for memory, streams and ``data_ptr()`` only; nothing here
 computes on the host and nothing falls back to the CPU.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -104,18 +105,9 @@ def fill_su_numpy(A, B, N, ltv=False):
 OSQP_RHO, OSQP_SIGMA, OSQP_ALPHA = 0.1, 1e-6, 1.6     # OSQP's default steps
 
 
-def admm(P, q, G, h, x=None, y=None, z=None, iters=50, rho=OSQP_RHO, sigma=OSQP_SIGMA, alpha=OSQP_ALPHA,
-         residuals=True, stream=None, kinv=None, kinv_valid=False):
-    """``iters`` iterations of OSQP's ADMM on a batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h``
-    (``mpcasm_admm``) -- the solver call of the walking loop, ``osqp_solve_qp(P=Q, q=q, G=A, h=h)``
-    (biped_mpc_loop.py:60), on the device tensors :meth:`Assembler.assemble` returns: ``P (B, no, no)``,
-    ``q (B, no)``, ``G (B, nc, no)``, ``h (B, nc)``.  ``x, y, z``: the iterates of a warm start (all three,
-    device tensors, updated IN PLACE) or None for a cold start.  Returns ``x, y, z, res`` with
-    ``res (B, 2)`` = OSQP's primal and dual residuals (None when ``residuals`` is off).
-    ``kinv``: a ``(B, no, no)`` device tensor for the inverse of ``P + sigma I + rho G'G`` -- written by this call,
-    or, with ``kinv_valid``, read instead of factoring (``P``, ``G``, ``rho``, ``sigma`` unchanged since the call that
-    wrote it: a new ``given`` on the same model changes ``q`` and ``h`` only)."""
-    torch = require_device()
+def _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid):
+    """The checks :func:`admm` and :func:`solve_qp` share: ``batch, no, nc, warm, x, y, z`` with the
+    iterates of a cold start allocated."""
     for t in (P, q, G, h):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
             raise ValueError("P, q, G, h: contiguous float64 device tensors")
@@ -135,12 +127,28 @@ def admm(P, q, G, h, x=None, y=None, z=None, iters=50, rho=OSQP_RHO, sigma=OSQP_
         x = torch.empty((batch, no), dtype=torch.float64, device=P.device)
         y = torch.empty((batch, nc), dtype=torch.float64, device=P.device)
         z = torch.empty((batch, nc), dtype=torch.float64, device=P.device)
-    res = torch.empty((batch, 2), dtype=torch.float64, device=P.device) if residuals else None
     if kinv is not None and not (isinstance(kinv, torch.Tensor) and kinv.device == P.device and kinv.dtype == torch.float64
                                  and kinv.is_contiguous() and tuple(kinv.shape) == (batch, no, no)):
         raise ValueError("kinv: a contiguous float64 (B, no, no) tensor on P's device")
     if kinv_valid and kinv is None:
         raise ValueError("kinv_valid without kinv")
+    return batch, no, nc, warm, x, y, z
+
+
+def admm(P, q, G, h, x=None, y=None, z=None, iters=50, rho=OSQP_RHO, sigma=OSQP_SIGMA, alpha=OSQP_ALPHA,
+         residuals=True, stream=None, kinv=None, kinv_valid=False):
+    """``iters`` iterations of OSQP's ADMM on a batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h``
+    (``mpcasm_admm``) -- the solver call of the walking loop, ``osqp_solve_qp(P=Q, q=q, G=A, h=h)``
+    (biped_mpc_loop.py:60), on the device tensors :meth:`Assembler.assemble` returns: ``P (B, no, no)``,
+    ``q (B, no)``, ``G (B, nc, no)``, ``h (B, nc)``.  ``x, y, z``: the iterates of a warm start (all three,
+    device tensors, updated IN PLACE) or None for a cold start.  Returns ``x, y, z, res`` with
+    ``res (B, 2)`` = OSQP's primal and dual residuals (None when ``residuals`` is off).
+    ``kinv``: a ``(B, no, no)`` device tensor for the inverse of ``P + sigma I + rho G'G`` -- written by this call,
+    or, with ``kinv_valid``, read instead of factoring (``P``, ``G``, ``rho``, ``sigma`` unchanged since the call that
+    wrote it: a new ``given`` on the same model changes ``q`` and ``h`` only)."""
+    torch = require_device()
+    batch, no, nc, warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid)
+    res = torch.empty((batch, 2), dtype=torch.float64, device=P.device) if residuals else None
     with torch.cuda.device(P.device):
         rc = capi.load().mpcasm_admm(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
                                      x.data_ptr(), y.data_ptr(), z.data_ptr(),
@@ -150,6 +158,57 @@ def admm(P, q, G, h, x=None, y=None, z=None, iters=50, rho=OSQP_RHO, sigma=OSQP_
                                      _stream_handle(torch, stream))
     capi.check(rc, "mpcasm_admm")
     return x, y, z, res
+
+
+QP_SOLVED, QP_MAX_ITER, QP_PRIMAL_INFEASIBLE, QP_DUAL_INFEASIBLE, QP_NON_CVX = (
+    capi.QP_SOLVED, capi.QP_MAX_ITER, capi.QP_PRIMAL_INFEASIBLE, capi.QP_DUAL_INFEASIBLE, capi.QP_NON_CVX)
+QpSolution = collections.namedtuple("QpSolution", "x y z status iters res rho")
+
+
+def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
+             eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
+             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None):
+    """A batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h`` solved to tolerance on the device
+    (``mpcasm_qp_solve``): :func:`admm`'s iteration with OSQP's termination tests and adaptive rho, every
+    instance stopping on its own, nothing read back to the host (a tick can be captured in a graph).
+    Operands, warm start and ``kinv`` as for :func:`admm`, except that ``P`` is read also with ``kinv_valid``.
+    ``rho``: a float, or a ``(B,)`` float64 device tensor of per-instance steps, updated IN PLACE to the step
+    each instance ended with (``kinv`` then holds the inverse for it: pass both to the next tick).
+    The defaults are OSQP's, except ``adaptive_rho_interval``: OSQP picks its interval from timing, a fixed
+    one keeps the result deterministic (0: rho stays).  Returns a :class:`QpSolution`
+    ``(x, y, z, status, iters, res, rho)``: ``status`` and ``iters`` ``(B,)`` int32 (``QP_*``), ``res`` ``(B, 2)``
+    the primal and dual residuals of the returned iterate."""
+    torch = require_device()
+    batch, no, nc, warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid)
+    if isinstance(rho, torch.Tensor):
+        if not (rho.device == P.device and rho.dtype == torch.float64 and rho.is_contiguous()
+                and tuple(rho.shape) == (batch,)):
+            raise ValueError("rho: a float or a contiguous float64 (B,) tensor on P's device")
+    else:
+        rho = torch.full((batch,), float(rho), dtype=torch.float64, device=P.device)
+    status = torch.empty((batch,), dtype=torch.int32, device=P.device)
+    iters = torch.empty((batch,), dtype=torch.int32, device=P.device)
+    res = torch.empty((batch, 2), dtype=torch.float64, device=P.device)
+    with torch.cuda.device(P.device):
+        rc = capi.load().mpcasm_qp_solve(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
+                                         x.data_ptr(), y.data_ptr(), z.data_ptr(), 1 if warm else 0,
+                                         rho.data_ptr(), float(sigma), float(alpha), float(eps_abs),
+                                         float(eps_rel), float(eps_prim_inf), float(eps_dual_inf), int(max_iter),
+                                         int(check_every), int(adaptive_rho_interval), status.data_ptr(),
+                                         iters.data_ptr(), res.data_ptr(), batch,
+                                         kinv.data_ptr() if kinv is not None else None, 1 if kinv_valid else 0,
+                                         _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_qp_solve")
+    return QpSolution(x, y, z, status, iters, res, rho)
+
+
+def qp_solve_lds_bytes(no, nc):
+    """LDS bytes one instance of :func:`solve_qp` (and of :func:`admm`) takes; ``MpcasmError`` with
+    ``ERR_LIMIT`` when that is more than a workgroup may have (``mpcasm_qp_solve_lds_bytes``)."""
+    out = ctypes.c_int64()
+    rc = capi.load().mpcasm_qp_solve_lds_bytes(int(no), int(nc), ctypes.byref(out))
+    capi.check(rc, "mpcasm_qp_solve_lds_bytes")
+    return int(out.value)
 
 
 # --------------------------------------------------------------------------
