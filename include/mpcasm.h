@@ -219,7 +219,8 @@ int mpcasm_assemble(const mpcasm_plan* plan, const double* const* h_src,
  * and row b of everything else (parameters, per-instance sources; results to row b).  What a walker
  * fleet's structure bucket needs (biped_mpc_loop.py:41-56 for many walkers: the bucket's walkers are
  * scattered over the fleet-wide `given`): no gather pass in front of the assembly.  Persistent kernel
- * only: MPCASM_ERR_LIMIT for a plan that runs elsewhere (gather the rows and call mpcasm_assemble). */
+ * only: MPCASM_ERR_LIMIT for a plan that runs elsewhere (gather the rows and call mpcasm_assemble).
+ * Every d_given_index[b] must lie in [0, rows of d_given): the kernel does not check it. */
 int mpcasm_assemble_indexed(const mpcasm_plan* plan, const double* const* h_src,
                             const int64_t* h_src_stride, const double* d_params, const double* d_given,
                             const int32_t* d_given_index, double* d_P, double* d_q, double* d_G,
@@ -413,6 +414,47 @@ int mpcasm_qp_solve(int no, int nc, const double* d_P, const double* d_q, const 
  * takes for no unknowns and nc limits (*out; MPCASM_ERR_LIMIT too when that exceeds what a workgroup
  * may have). */
 int mpcasm_qp_solve_lds_bytes(int no, int nc, int64_t* out);
+
+/* f2 + the loop  the next tick's `given` from a solution ------------------------------------------------
+ * Replaces, for a batch of walkers, the end of every tick of the walking loop
+ *   preview_all + update_given_collector       biped_mpc_loop.py:62-65, 81-92
+ *   (Formulation.preview, body.py:209-219, of the rows the update reads, and arrange_given of the
+ *    next decide_actions, biped_mpc_loop.py:54)
+ * without the rows of the definitions ever leaving the chip and without a trip to the host.
+ *
+ * A *given map* says, per column c of `given`, what the column becomes:
+ *   h_rows[c] = r >= 0               row r of the plan's preview program (the rows mpcasm_preview_direct
+ *                                    writes: definition v at mpcasm/plan.py's pm_rows[v])
+ *   h_rows[c] = MPCASM_GIVEN_CONST   the constant h_values[c] (finite)
+ *   h_rows[c] = MPCASM_GIVEN_KEEP    left as it is
+ * mpcasm_given_map_compile turns that into the map's words for this plan (host only, no device call):
+ * the records plus the list of the base rows the named rows combine, worked out once.  *words = the
+ * number of int32 words; h_map == NULL asks for that number only, a smaller capacity is MPCASM_ERR_ARG.
+ * The caller copies the words to the device (d_map) and keeps them for as many ticks as it likes.
+ * MPCASM_ERR_ARG: ng is not the plan's, a row outside the preview program, a CONST without a finite
+ * value; MPCASM_ERR_LIMIT: a plan mpcasm_preview_direct refuses (compiled with ltv=[...], or whose
+ * column tables do not cover it). */
+enum { MPCASM_GIVEN_KEEP = -1, MPCASM_GIVEN_CONST = -2 };
+int mpcasm_given_map_compile(const mpcasm_plan* plan, const int32_t* h_rows, const double* h_values, int ng,
+                             int32_t* h_map, int64_t capacity, int64_t* words);
+
+/* For count instances b: the new values of the map's columns from row d_index[b] of d_given (rows x ng) and
+ * row b of d_optim (count x no), written IN PLACE into row d_index[b] of d_given -- the whole row is read
+ * before any of it is written.  Only the base rows the named rows combine are evaluated, on chip, in the
+ * order mpcasm_preview_direct evaluates them.  Sources, strides and d_work as for mpcasm_preview_direct
+ * (instance b reads row b of a per-instance source).
+ * d_index (count entries; NULL: instance b is row b, rows >= count): the entries of one call must be
+ * DISTINCT and lie in [0, rows).  The host that builds the index checks that (the kernel skips an entry
+ * outside [0, rows) but cannot see two instances writing one row).
+ * d_status (count entries, e.g. mpcasm_qp_solve's; NULL: all apply) and apply_mask: instance b writes only
+ * when bit MPCASM_QP_BIT(d_status[b]) of apply_mask is set; otherwise its row stays exactly as it was.
+ * d_map / map_words: the words of mpcasm_given_map_compile for THIS plan; a map that does not match the
+ * plan's sizes, or is not such a map, writes nothing.  MPCASM_ERR_LIMIT as mpcasm_given_map_compile. */
+#define MPCASM_QP_BIT(status) (1u << ((status) < 0 ? -(status) : (status)))
+int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                      double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
+                      const int32_t* d_status, uint32_t apply_mask, const int32_t* d_map, int64_t map_words,
+                      void* d_work, int count, void* stream);
 
 #ifdef __cplusplus
 }

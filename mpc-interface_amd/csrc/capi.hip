@@ -1098,7 +1098,7 @@ void plan_dev_from_tables(const int32_t* it, PlanDev* out) {
 
 extern "C" {
 
-int mpcasm_abi_version(void) { return 1001; }
+int mpcasm_abi_version(void) { return 1002; }
 
 int mpcasm_device_count(void) {
   int n = 0;
@@ -1466,6 +1466,56 @@ int mpcasm_preview_direct(const mpcasm_plan* plan, const double* const* h_src,
   if (rc != MPCASM_OK) return rc;
   rc = launch_preview_direct(d, eff, d_given, d_optim, d_out, batch, plan->num_cus,
                              static_cast<hipStream_t>(stream), &err, plan->h_itab.data());
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
+int mpcasm_given_map_compile(const mpcasm_plan* plan, const int32_t* h_rows, const double* h_values, int ng,
+                             int32_t* h_map, int64_t capacity, int64_t* words) {
+  if (!plan || !h_rows || !words || capacity < 0) return MPCASM_ERR_ARG;
+  const PlanDev& d = plan->dev;
+  if (ng != d.ng) return MPCASM_ERR_ARG;
+  if (d.sw_ok || !d.t_ci_ok) return MPCASM_ERR_LIMIT;  // (as mpcasm_preview_direct)
+  for (int c = 0; c < ng; ++c) {
+    const int r = h_rows[c];
+    if (r == MPCASM_GIVEN_CONST ? (!h_values || !std::isfinite(h_values[c]))
+                                : (r != MPCASM_GIVEN_KEEP && (r < 0 || r >= d.pmrows)))
+      return MPCASM_ERR_ARG;
+  }
+  std::vector<int32_t> map;
+  const int rc = compile_given_map(d, plan->h_itab.data(), h_rows, h_values, &map);
+  if (rc != MPCASM_OK) return rc;
+  *words = (int64_t)map.size();
+  if (h_map == nullptr) return MPCASM_OK;
+  if (capacity < (int64_t)map.size()) return MPCASM_ERR_ARG;
+  memcpy(h_map, map.data(), map.size() * sizeof(int32_t));
+  return MPCASM_OK;
+}
+
+int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                      double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
+                      const int32_t* d_status, uint32_t apply_mask, const int32_t* d_map, int64_t map_words,
+                      void* d_work, int count, void* stream) {
+  if (!plan || count < 0 || rows < 0 || map_words < 0) return MPCASM_ERR_ARG;
+  const PlanDev& d = plan->dev;
+  if (d.sw_ok || !d.t_ci_ok) return MPCASM_ERR_LIMIT;  // (as mpcasm_preview_direct)
+  if (count == 0 || d.ng == 0) return MPCASM_OK;
+  if (!d_given || !d_map || (d.no && !d_optim) || (d.nsrc && (!h_src || !h_src_stride))) return MPCASM_ERR_ARG;
+  if (!d_index && rows < count) return MPCASM_ERR_ARG;
+  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
+  {  // the plan's tables live on the device it was created on
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  }
+  SrcTable src, eff;
+  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  hipError_t err;
+  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), count, plan->h_itab.data(), &eff,
+                         static_cast<hipStream_t>(stream));
+  if (rc != MPCASM_OK) return rc;
+  rc = launch_next_given(d, eff, d_map, map_words, d_given, rows, d_optim, d_index, d_status, apply_mask, count,
+                         plan->num_cus, static_cast<hipStream_t>(stream), &err);
   if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
   return rc;
 }

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/mpcasm.h"
 #include "plan_dev.h"
 #include "plan_tables.h"
@@ -48,6 +50,13 @@ int launch_preview_goals(const PlanDev& p, const SrcTable& eff, const double* gi
                          const double* params, long long nparams, const int32_t* terms, int nterms,
                          int ngoals, double* out, int batch, int num_cus, hipStream_t stream,
                          hipError_t* err, const int32_t* h_itab);
+// the next tick's `given` (mpcasm_next_given): the map's rows / constants into the instances' rows
+int launch_next_given(const PlanDev& p, const SrcTable& eff, const int32_t* map, long long map_words,
+                      double* given, long long rows, const double* optim, const int32_t* index,
+                      const int32_t* status, unsigned apply_mask, int count, int num_cus, hipStream_t stream,
+                      hipError_t* err);
+int compile_given_map(const PlanDev& p, const int32_t* h_itab, const int32_t* rows, const double* values,
+                      std::vector<int32_t>* out);
 int launch_goal_distance(const double* preview, long long preview_stride, const double* params,
                          long long nparams, const int32_t* terms, int nterms, int ngoals,
                          double* out, int batch, hipStream_t stream, hipError_t* err);

@@ -38,6 +38,12 @@ QP_STATUS = {
     -4: "MPCASM_QP_DUAL_INFEASIBLE",
     -7: "MPCASM_QP_NON_CVX",
 }
+GIVEN_KEEP, GIVEN_CONST = -1, -2     # given-map records of mpcasm_given_map_compile (a row: its index >= 0)
+
+
+def qp_bit(status):
+    """Bit of ``status`` (a ``QP_*`` value) in the ``apply_mask`` of ``mpcasm_next_given``."""
+    return 1 << abs(int(status))
 
 # every symbol include/mpcasm.h declares: name -> (restype, argtypes)
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -94,6 +100,11 @@ SIGNATURES = {
                         [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
                         [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_qp_solve_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
+                                                ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
+                                         ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_uint32, _void_p,
+                                         ctypes.c_int64, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_gather": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p,
                                      ctypes.c_int, _void_p]),
     "mpcasm_box_transform": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p,

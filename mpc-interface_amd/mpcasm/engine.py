@@ -167,7 +167,7 @@ QpSolution = collections.namedtuple("QpSolution", "x y z status iters res rho")
 
 def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
              eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None):
+             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None):
     """A batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h`` solved to tolerance on the device
     (``mpcasm_qp_solve``): :func:`admm`'s iteration with OSQP's termination tests and adaptive rho, every
     instance stopping on its own, nothing read back to the host (a tick can be captured in a graph).
@@ -177,18 +177,33 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
     The defaults are OSQP's, except ``adaptive_rho_interval``: OSQP picks its interval from timing, a fixed
     one keeps the result deterministic (0: rho stays).  Returns a :class:`QpSolution`
     ``(x, y, z, status, iters, res, rho)``: ``status`` and ``iters`` ``(B,)`` int32 (``QP_*``), ``res`` ``(B, 2)``
-    the primal and dual residuals of the returned iterate."""
+    the primal and dual residuals of the returned iterate.
+    ``out``: for a COLD start, the caller's ``(x, y, z, status, iters, res)`` to write instead of new tensors
+    (``(B, no)``, ``(B, nc)``, ``(B, nc)``, ``(B,)`` int32 twice, ``(B, 2)``: a loop that replays a graph keeps
+    them at fixed addresses); ``x, y, z`` are not read."""
     torch = require_device()
+    if out is not None:
+        if x is not None or y is not None or z is not None:
+            raise ValueError("out is for a cold start: pass x, y, z for a warm one")
+        x, y, z, status, iters, res = out
+        batch = P.shape[0]
+        for t, dtype, shape in ((status, torch.int32, (batch,)), (iters, torch.int32, (batch,)),
+                                (res, torch.float64, (batch, 2))):
+            if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype
+                    and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError("out: status, iters (B,) int32 and res (B, 2) float64, contiguous, on P's device")
     batch, no, nc, warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid)
+    warm = warm and out is None
     if isinstance(rho, torch.Tensor):
         if not (rho.device == P.device and rho.dtype == torch.float64 and rho.is_contiguous()
                 and tuple(rho.shape) == (batch,)):
             raise ValueError("rho: a float or a contiguous float64 (B,) tensor on P's device")
     else:
         rho = torch.full((batch,), float(rho), dtype=torch.float64, device=P.device)
-    status = torch.empty((batch,), dtype=torch.int32, device=P.device)
-    iters = torch.empty((batch,), dtype=torch.int32, device=P.device)
-    res = torch.empty((batch, 2), dtype=torch.float64, device=P.device)
+    if out is None:
+        status = torch.empty((batch,), dtype=torch.int32, device=P.device)
+        iters = torch.empty((batch,), dtype=torch.int32, device=P.device)
+        res = torch.empty((batch, 2), dtype=torch.float64, device=P.device)
     with torch.cuda.device(P.device):
         rc = capi.load().mpcasm_qp_solve(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
                                          x.data_ptr(), y.data_ptr(), z.data_ptr(), 1 if warm else 0,
@@ -209,6 +224,59 @@ def qp_solve_lds_bytes(no, nc):
     rc = capi.load().mpcasm_qp_solve_lds_bytes(int(no), int(nc), ctypes.byref(out))
     capi.check(rc, "mpcasm_qp_solve_lds_bytes")
     return int(out.value)
+
+
+# every outcome but NON_CVX (whose iterates are NaN) / the solved ones and those out of iterations: the
+# apply_mask of Assembler.next_given under WalkerFleet's "apply" / "hold" rule
+APPLY_ALL = sum(capi.qp_bit(s) for s in (QP_SOLVED, QP_MAX_ITER, QP_PRIMAL_INFEASIBLE, QP_DUAL_INFEASIBLE))
+APPLY_SOLVED = capi.qp_bit(QP_SOLVED) | capi.qp_bit(QP_MAX_ITER)
+
+
+def given_map_records(plan, rules):
+    """The records of a given map (``mpcasm_given_map_compile``) for ``plan``: ``(rows, values)``, one entry
+    per column of ``given`` -- a row of the plan's preview program (``plan.pm_rows``), ``capi.GIVEN_CONST``
+    with the value in ``values``, or ``capi.GIVEN_KEEP``.  ``rules``: given variable (a key of
+    ``form.given_ID``) -> a list with one ``(definition, sample)`` pair per component of the variable (None:
+    that component is kept), or a float: every component becomes that constant.  Variables not named are
+    kept.  Host only: no device needed."""
+    rows = np.full(plan.ng, capi.GIVEN_KEEP, dtype=np.int32)
+    values = np.zeros(plan.ng, dtype=np.float64)
+    for var, rule in rules.items():
+        if var not in plan.given_ID:
+            raise KeyError("%r is not a given variable of this plan (%s)" % (var, ", ".join(plan.given_ID)))
+        cols = plan.given_ID[var]
+        if isinstance(rule, (int, float, np.floating, np.integer)):
+            if not np.isfinite(rule):
+                raise ValueError("%r: a constant must be finite" % var)
+            rows[cols.start:cols.stop] = capi.GIVEN_CONST
+            values[cols.start:cols.stop] = float(rule)
+            continue
+        rule = list(rule)
+        if len(rule) != len(cols):
+            raise ValueError("%r has %d components, the rule names %d" % (var, len(cols), len(rule)))
+        for c, pair in zip(cols, rule):
+            if pair is None:
+                continue
+            definition, sample = pair
+            if definition not in plan.pm_rows:
+                raise KeyError("%r is not a definition of this plan" % (definition,))
+            r0, n = plan.pm_rows[definition]
+            if not 0 <= int(sample) < n:
+                raise ValueError("%r has %d samples, the rule asks for sample %d" % (definition, n, sample))
+            rows[c] = r0 + int(sample)
+    return rows, values
+
+
+GivenMap = collections.namedtuple("GivenMap", "table words rows values plan")
+
+
+def checked_index(idx, rows):
+    """``idx`` as the int32 index of a launch that writes (or reads) rows of a ``rows``-row buffer by it:
+    ValueError unless its entries are distinct and in ``[0, rows)`` (mpcasm.h: the kernels do not check)."""
+    idx = np.asarray(idx)
+    if idx.size and (idx.min() < 0 or idx.max() >= rows or np.unique(idx).size != idx.size):
+        raise ValueError("an index of rows must hold distinct entries in [0, %d)" % rows)
+    return idx.astype(np.int32)
 
 
 # --------------------------------------------------------------------------
@@ -690,6 +758,67 @@ class Assembler:
                 _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_preview_direct")
         return out
+
+    def given_map(self, rules):
+        """The device table of a given map for this assembler's plan (``mpcasm_given_map_compile``; rules as
+        :func:`given_map_records`): what :meth:`next_given` reads.  A map belongs to one plan -- the buckets
+        of a fleet each build their own."""
+        torch = self._torch
+        rows, values = given_map_records(self.plan, rules)
+        lib, words = capi.load(), ctypes.c_int64()
+        args = (self._handle, rows.ctypes.data, values.ctypes.data, self.ng)
+        capi.check(lib.mpcasm_given_map_compile(*args, None, 0, ctypes.byref(words)), "mpcasm_given_map_compile")
+        host = np.zeros(max(words.value, 1), dtype=np.int32)
+        capi.check(lib.mpcasm_given_map_compile(*args, host.ctypes.data, host.size, ctypes.byref(words)),
+                   "mpcasm_given_map_compile")
+        return GivenMap(torch.as_tensor(host, device=self.device), int(words.value), rows, values, self.plan)
+
+    def next_given(self, given, optim, gmap, index=None, status=None, apply_mask=APPLY_SOLVED, count=None,
+                   stream=None):
+        """The next tick's ``given`` from a solution, IN PLACE (``mpcasm_next_given``; biped_mpc_loop.py:62-95):
+        instance ``b`` reads row ``index[b]`` of ``given`` (``(rows, ng)``, e.g. a whole fleet's) and row ``b``
+        of ``optim`` (``(>= count, no)``), evaluates the preview rows ``gmap`` (:meth:`given_map`) names and
+        writes them, and its constants, into row ``index[b]``; the columns the map keeps stay as they are.
+        ``index``: contiguous int32 device tensor, ``count`` DISTINCT entries in ``[0, rows)`` (None: instance
+        ``b`` is row ``b``) -- the caller that builds it vouches for that, nothing is read back to check it; an
+        index from the host (array or list) is checked (:func:`checked_index`) and copied to the device.
+        ``status`` (``(>= count,)`` int32, :func:`solve_qp`'s): an instance whose status has no bit in
+        ``apply_mask`` (``capi.qp_bit``; :data:`APPLY_SOLVED`, :data:`APPLY_ALL`) leaves its row untouched.
+        Returns ``given``."""
+        torch = self._torch
+        n = self.batch if count is None else int(count)
+        if not 0 <= n <= self.batch:         # (per-instance sources are sized for the batch)
+            raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
+        if not isinstance(gmap, GivenMap) or gmap.plan is not self.plan:
+            raise ValueError("gmap: a map this assembler's given_map built")
+        if not (torch.is_tensor(given) and given.dtype == torch.float64 and given.device == self.device
+                and given.is_contiguous() and given.dim() == 2 and given.shape[1] == self.ng):
+            raise ValueError("given: a contiguous float64 (rows, %d) tensor on %s (updated in place)"
+                             % (self.ng, self.device))
+        if not (torch.is_tensor(optim) and optim.dtype == torch.float64 and optim.device == self.device
+                and optim.is_contiguous() and optim.dim() == 2 and optim.shape[1] == self.no and optim.shape[0] >= n):
+            raise ValueError("optim: a contiguous float64 (>= %d, %d) tensor on %s" % (n, self.no, self.device))
+        if index is not None and not torch.is_tensor(index):
+            index = np.asarray(index)
+            if index.ndim != 1 or index.size < n:
+                raise ValueError("index: %d entries" % n)
+            index = torch.as_tensor(checked_index(index[:n], given.shape[0]), device=self.device)
+        for t, name in ((index, "index"), (status, "status")):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.int32 and t.device == self.device
+                                      and t.is_contiguous() and t.dim() == 1 and t.numel() >= n):
+                raise ValueError("%s: a contiguous int32 tensor of >= %d entries on %s" % (name, n, self.device))
+        if index is None and given.shape[0] < n:
+            raise ValueError("given must have %d rows, got %d" % (n, given.shape[0]))
+        ptrs, strides = self._src_args()
+        work = self._workspace()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_next_given(
+                self._handle, ptrs, strides, given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index),
+                ptr(status), int(apply_mask) & 0xFFFFFFFF, gmap.table.data_ptr(), gmap.words, work.data_ptr(), n,
+                _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_next_given")
+        return given
 
     def goal_terms(self, form):
         """Device table of ``mpcasm_goal_distance`` for ``form.goals`` (the plan's costs): one

@@ -12,10 +12,15 @@ the fleet is split into structure buckets (one compiled plan and one persistent
 assembly launch per bucket and tick); what differs between walkers of a bucket is
 numbers: the step indicator matrix ``E`` (a per-instance source), the stepping-area
 centres (per-instance parameters) and the given vector.
+
+:meth:`WalkerFleet.step` closes the loop on the device (biped_mpc_loop.py:50-95 for every walker):
+assemble, solve to tolerance, and write each walker's next ``given`` from its solution
+(:func:`biped_given_rules`, the reference's update_given_collector), with nothing read back.
 """
 import numpy as np
 
 from . import problems
+from .engine import checked_index  # noqa: F401  (the fleet's index of rows is checked where it is built)
 
 
 def steps_in_preview(step_times, N):
@@ -40,6 +45,22 @@ def stepping_centers(step_count, p, xy):
     out[:, :, 0] = xy[0]
     out[:, :, 1] = side[:, None] * alt[None, :] * xy[1]
     return out
+
+
+def biped_given_rules(form):
+    """The reference's ``update_given_collector`` (biped_mpc_loop.py:81-92) as the rules of a given map
+    (:meth:`mpcasm.engine.Assembler.given_map`): for every ``state, ID`` of the LIP,
+    ``x0<axis>[ID] <- state[sample 0]``; for the states of the steps, ``s0<axis>[ID] <- state[sample 1]``
+    (the support after the next sample); every bias column ``<- 0.0``."""
+    rules = {}
+    for dyn, prefix, sample in (("LIP", "x0", 0), ("steps", "s0", 1)):
+        for state, ID in form.dynamics[dyn].state_ID.items():
+            var = prefix + state[-2:]
+            rule = rules.setdefault(var, [None] * len(form.given_ID[var]))
+            rule[ID] = (state, sample)
+    for var in form.dynamics["bias"].domain:
+        rules[var] = 0.0
+    return rules
 
 
 class FleetClock:
@@ -68,11 +89,24 @@ class WalkerFleet:
     step cycle.  :meth:`tick` assembles the QPs of all walkers for the current tick and
     advances the clocks; it returns one entry per structure bucket:
     ``{"p": steps in preview, "index": walker ids, "P", "q", "G", "h": device tensors}``.
+
+    :meth:`step` is one closed tick of the walking loop on :meth:`given_buffer` (assemble, solve,
+    next ``given``) and :meth:`run` many of them.  ``on_unsolved`` is what happens to a walker whose QP
+    is not solved -- the reference has no rule (``osqp_solve_qp`` returns None and its loop stops):
+      * ``"hold"`` (default): only SOLVED and MAX_ITER solutions are applied; any other walker keeps its
+        ``given`` for that tick and tries again at the next one, its clock advancing as ever;
+      * ``"apply"``: every solution is applied except NON_CVX, whose iterates are NaN.
     """
 
-    def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False):
-        from .engine import Assembler, require_device
+    def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False,
+                 on_unsolved="hold"):
+        from .engine import APPLY_ALL, APPLY_SOLVED, Assembler, require_device
 
+        if on_unsolved not in ("hold", "apply"):
+            raise ValueError("on_unsolved: 'hold' or 'apply', got %r" % (on_unsolved,))
+        self.on_unsolved = on_unsolved
+        self._apply_mask = APPLY_SOLVED if on_unsolved == "hold" else APPLY_ALL
+        self._step_graphs = {}
         self._torch = require_device()
         self.conf = conf or problems.BipedConfig()
         self.api = api or problems.load_api("mpc_interface")
@@ -159,17 +193,17 @@ class WalkerFleet:
                 # tick copies nothing (only the centres change with the place in the cycle)
                 params = asm.params.clone()
                 params[:idx.size].index_copy_(1, bucket["center_cols"], centers.repeat(1, len(bucket["facets"])))
-                entry.append(dict(p=p, idx=idx, index=torch.as_tensor(idx, dtype=torch.int32, device=dev), E=E,
-                                  params=params))
+                index = torch.as_tensor(checked_index(idx, self.batch), device=dev)
+                entry.append(dict(p=p, idx=idx, index=index, index_long=index.long(), E=E, params=params))
             self._cache[key] = entry
         return self._cache[key]
 
-    def _launch(self, given, side_by_side=False):
+    def _launch(self, given, side_by_side=False, then=None):
         """This tick's launches for ``given`` (a device tensor): ONE assembly per structure bucket
         (its walkers' rows of ``given`` picked by index inside the kernel, the parameters of this place in
         the step cycle kept ready).  ``side_by_side``: every bucket on a stream of its own with its share
         of the workgroup slots (forked from and joined to the current stream: what a graph captures as
-        parallel branches)."""
+        parallel branches).  ``then(item, entry, stream)``: what follows a bucket's assembly on its stream."""
         from . import capi
         torch = self._torch
         items = self._bucket_inputs()
@@ -200,6 +234,8 @@ class WalkerFleet:
                                       stream=stream)
             out.append({"p": p, "index": idx, "P": P[:idx.size], "q": q[:idx.size],
                         "G": G[:idx.size], "h": h[:idx.size]})
+            if then is not None:
+                out[-1] = then(item, out[-1], stream)
         if side_by_side:
             for stream in self._side[:len(items) - 1]:
                 cur.wait_stream(stream)
@@ -240,4 +276,101 @@ class WalkerFleet:
             graph.replay()
         self.clock.tick()
         self._ticks += 1
+        return out
+
+    # ---- the closed loop ------------------------------------------------------------------
+    def start_at_rest(self):
+        """Every walker's row of :meth:`given_buffer` to the reference's start (biped_mpc_loop.py:26-33):
+        the preview of zero ``given`` and ``optim`` -- all zeros -- with ``x0_y[0] = s0_y[0] = strt_y``."""
+        form = next(iter(self.buckets.values()))["form"]
+        row = np.zeros(self.given_len)
+        for var in ("x0_y", "s0_y"):
+            row[form.given_ID[var][0]] = self.conf.strt_y
+        given = self.given_buffer()
+        given.copy_(self._torch.as_tensor(row, device=given.device).expand_as(given))
+        return given
+
+    def _closed_bucket(self, item, entry, stream):
+        """After a bucket's assembly, on its stream: a cold solve with OSQP's defaults into the bucket's own
+        solver buffers, then its walkers' next ``given`` from the solution, by the fleet's rule."""
+        from .engine import OSQP_RHO, solve_qp
+
+        bucket = self.buckets[item["p"]]
+        asm, n = bucket["asm"], item["idx"].size
+        qp = bucket.get("qp")
+        if qp is None:   # (once per bucket, at fixed addresses for every place of the cycle and every graph)
+            torch, f = self._torch, dict(dtype=self._torch.float64, device=asm.device)
+            i32 = dict(dtype=torch.int32, device=asm.device)
+            B = self.batch
+            qp = bucket["qp"] = dict(x=torch.zeros((B, asm.no), **f), y=torch.zeros((B, asm.nc), **f),
+                                     z=torch.zeros((B, asm.nc), **f), status=torch.zeros(B, **i32),
+                                     iters=torch.zeros(B, **i32), res=torch.zeros((B, 2), **f),
+                                     rho=torch.full((B,), OSQP_RHO, **f))
+            bucket["gmap"] = asm.given_map(biped_given_rules(bucket["form"]))
+        cur = self._torch.cuda.current_stream(asm.device) if stream is None else stream
+        with self._torch.cuda.stream(cur):
+            rho = qp["rho"][:n]
+            rho.fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
+            sol = solve_qp(entry["P"], entry["q"], entry["G"], entry["h"], rho=rho, stream=stream,
+                           out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")))
+            asm.next_given(self.given_buffer(), sol.x, bucket["gmap"], index=item["index"], status=sol.status,
+                           apply_mask=self._apply_mask, count=n, stream=stream)
+        return {"p": item["p"], "index": item["index"], "index_long": item["index_long"], "x": sol.x,
+                "status": sol.status, "iters": sol.iters}
+
+    def step(self):
+        """One closed tick of the walking loop on :meth:`given_buffer` (biped_mpc_loop.py:50-95 for every
+        walker): per structure bucket, the assembly of :meth:`tick`, a cold :func:`~mpcasm.engine.solve_qp`
+        with OSQP's defaults, and :meth:`~mpcasm.engine.Assembler.next_given` by the fleet's
+        ``on_unsolved`` rule; then the clocks advance.  Nothing is read back: returns per bucket
+        ``{"p", "index": walker ids, "x", "status", "iters"}`` (device tensors in the bucket's own buffers,
+        valid until the next step).  With ``graphs``, each place of the step cycle runs its whole closed
+        tick as one graph (captured the first time the place comes round, after running it as it is)."""
+        torch = self._torch
+        given = self.given_buffer()
+        if not self._use_graphs:
+            out = self._launch(given, then=self._closed_bucket)
+        else:
+            key = self._ticks % (2 * self.conf.step_samples)
+            if key not in self._step_graphs:
+                dev = given.device
+                out = self._launch(given, side_by_side=self._side_by_side, then=self._closed_bucket)
+                torch.cuda.synchronize(dev)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):     # (captured, not run: this tick is done)
+                    captured = self._launch(given, side_by_side=self._side_by_side, then=self._closed_bucket)
+                self._step_graphs[key] = (graph, captured)
+            else:
+                graph, out = self._step_graphs[key]
+                graph.replay()
+        self.clock.tick()
+        self._ticks += 1
+        return [{k: v for k, v in entry.items() if k != "index_long"} for entry in out]
+
+    def run(self, ticks, record=False):
+        """:meth:`step` ``ticks`` times; returns device tensors ``status`` and ``iters`` ``(ticks, batch)``
+        int32 in walker order and, with ``record``, ``given`` ``(ticks + 1, batch, ng)``: the fleet's
+        ``given`` before the first tick and after every tick."""
+        torch = self._torch
+        given = self.given_buffer()
+        i32 = dict(dtype=torch.int32, device=given.device)
+        status = torch.zeros((ticks, self.batch), **i32)
+        iters = torch.zeros((ticks, self.batch), **i32)
+        trail = torch.empty((ticks + 1,) + tuple(given.shape), dtype=given.dtype, device=given.device) \
+            if record else None
+        if record:
+            trail[0].copy_(given)
+        for t in range(ticks):
+            key = self._ticks % (2 * self.conf.step_samples)
+            self.step()
+            items = self._cache[key]
+            for item in items:
+                qp, n = self.buckets[item["p"]]["qp"], item["idx"].size
+                status[t].index_copy_(0, item["index_long"], qp["status"][:n])
+                iters[t].index_copy_(0, item["index_long"], qp["iters"][:n])
+            if record:
+                trail[t + 1].copy_(given)
+        out = {"status": status, "iters": iters}
+        if record:
+            out["given"] = trail
         return out
