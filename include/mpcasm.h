@@ -415,6 +415,31 @@ int mpcasm_qp_solve(int no, int nc, const double* d_P, const double* d_q, const 
  * may have). */
 int mpcasm_qp_solve_lds_bytes(int no, int nc, int64_t* out);
 
+/* The same solve for QPs whose matrices do not fit on chip (C3, C5, C4): replaces, like mpcasm_qp_solve,
+ *   self.optim = osqp_solve_qp(P=Q, q=q, G=A, h=h)      biped_mpc_loop.py:60
+ * with mpcasm_qp_solve's argument list, status codes, rules, iterates, warm start, d_rho, d_kinv /
+ * kinv_valid reuse and per-instance outputs, nothing read back to the host.  G is read in place from d_G
+ * once per iteration (not copied to LDS); K^-1 = (P + sigma I + rho G'G)^-1 lives in LDS when it fits
+ * beside the vectors, else in d_kinv (see mpcasm_qp_solve_wide_info).  The one difference in the operands:
+ * when K^-1 is not on chip for this (no, nc), d_kinv is REQUIRED (MPCASM_ERR_ARG if NULL) -- d_kinv[b] is then
+ * the kernel's factorisation workspace, and on return holds the inverse for the final rho as mpcasm_qp_solve
+ * promises.  The iterates equal mpcasm_qp_solve's up to rounding (sums in another order).
+ * Size limit: no <= 512 and (3 nc + 23 no + 64) doubles (+ no (no | 1) with K^-1 on chip) within 156 KB of
+ * LDS per instance -- every nc <= 2048 at no = 512, nc <= 2709 there; nc = 0 is allowed.  MPCASM_ERR_ARG as
+ * mpcasm_qp_solve; MPCASM_ERR_LIMIT beyond the limit; nothing is launched on a refusal. */
+int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                         const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                         double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                         double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                         int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                         int kinv_valid, void* stream);
+/* Needs no device: for one instance of mpcasm_qp_solve_wide with no unknowns and nc limits, the LDS bytes it
+ * takes (*lds_bytes) and whether K^-1 lives in LDS (*kinv_on_chip = 1) or in d_kinv (0).  K^-1 is on chip when
+ * no (no | 1) + 3 nc + 23 no + 64 doubles fit in 156 KB; the environment variable MPCASM_QP_WIDE_KINV, read at
+ * every call, overrides that: "global" keeps K^-1 in d_kinv always, "lds" puts it on chip wherever it fits.
+ * MPCASM_ERR_LIMIT beyond the size limit of mpcasm_qp_solve_wide (the other outputs still written). */
+int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
+
 /* f2 + the loop  the next tick's `given` from a solution ------------------------------------------------
  * Replaces, for a batch of walkers, the end of every tick of the walking loop
  *   preview_all + update_given_collector       biped_mpc_loop.py:62-65, 81-92

@@ -1098,7 +1098,7 @@ void plan_dev_from_tables(const int32_t* it, PlanDev* out) {
 
 extern "C" {
 
-int mpcasm_abi_version(void) { return 1002; }
+int mpcasm_abi_version(void) { return 1003; }
 
 int mpcasm_device_count(void) {
   int n = 0;
@@ -1641,6 +1641,39 @@ int mpcasm_qp_solve_lds_bytes(int no, int nc, int64_t* out) {
   if (no < 1 || nc < 0 || no > (1 << 12) || nc > (1 << 16) || !out) return MPCASM_ERR_ARG;
   *out = (int64_t)admm_lds_bytes(no, nc);
   return *out > RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
+}
+
+int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                         const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                         double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                         double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                         int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                         int kinv_valid, void* stream) {
+  for (double eps : {eps_abs, eps_rel, eps_prim_inf, eps_dual_inf})
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return MPCASM_ERR_ARG;
+  if (no < 1 || nc < 0 || batch < 0 || max_iter < 0 || check_every < 1 || adaptive_rho_interval < 0 ||
+      adaptive_rho_interval % check_every != 0 || !(sigma > 0.0) || !(alpha > 0.0) || !(alpha < 2.0) ||
+      no > (1 << 12) || nc > (1 << 16))
+    return MPCASM_ERR_ARG;
+  int32_t on_chip = 0;
+  const int limit = qp_solve_wide_info(no, nc, nullptr, &on_chip);
+  if (limit != MPCASM_OK) return limit;
+  if (batch == 0) return MPCASM_OK;
+  if (!d_P || !d_q || !d_x || !d_rho || !d_status || !d_iters || (nc > 0 && (!d_G || !d_h || !d_y || !d_z)))
+    return MPCASM_ERR_ARG;
+  if ((kinv_valid != 0 || on_chip == 0) && d_kinv == nullptr) return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_qp_solve_wide(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm != 0, d_rho, sigma, alpha,
+                                      eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
+                                      adaptive_rho_interval, d_status, d_iters, d_res, batch, d_kinv,
+                                      kinv_valid != 0, static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
+int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
+  if (no < 1 || nc < 0 || no > (1 << 12) || nc > (1 << 16) || !lds_bytes || !kinv_on_chip) return MPCASM_ERR_ARG;
+  return qp_solve_wide_info(no, nc, lds_bytes, kinv_on_chip);
 }
 
 int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_index, int nnz,

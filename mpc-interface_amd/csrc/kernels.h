@@ -107,6 +107,13 @@ int launch_qp_solve(int no, int nc, const double* P, const double* q, const doub
                     double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
                     int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
                     int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err);
+// admm_wide.hip: the solve to tolerance with G read in place and K^-1 in LDS or in d_kinv
+int qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
+int launch_qp_solve_wide(int no, int nc, const double* P, const double* q, const double* G, const double* h,
+                         double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
+                         double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
+                         int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
+                         int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err);
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err);
 

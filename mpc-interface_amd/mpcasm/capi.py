@@ -100,6 +100,11 @@ SIGNATURES = {
                         [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
                         [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_qp_solve_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_qp_solve_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] +
+                             [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
+                             [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_qp_solve_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
+                                                 ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,

@@ -181,6 +181,14 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
     ``out``: for a COLD start, the caller's ``(x, y, z, status, iters, res)`` to write instead of new tensors
     (``(B, no)``, ``(B, nc)``, ``(B, nc)``, ``(B,)`` int32 twice, ``(B, 2)``: a loop that replays a graph keeps
     them at fixed addresses); ``x, y, z`` are not read."""
+    return _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
+                     max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out)
+
+
+def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
+              adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False):
+    """:func:`solve_qp` and :func:`solve_qp_wide` through the C entry ``entry``; ``workspace``: allocate
+    ``kinv`` when it is None (the wide path's K^-1 off chip)."""
     torch = require_device()
     if out is not None:
         if x is not None or y is not None or z is not None:
@@ -204,8 +212,12 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
         status = torch.empty((batch,), dtype=torch.int32, device=P.device)
         iters = torch.empty((batch,), dtype=torch.int32, device=P.device)
         res = torch.empty((batch, 2), dtype=torch.float64, device=P.device)
+    if workspace and kinv is None:
+        lds, on = ctypes.c_int64(), ctypes.c_int32()
+        if capi.load().mpcasm_qp_solve_wide_info(no, nc, ctypes.byref(lds), ctypes.byref(on)) == 0 and not on.value:
+            kinv = torch.empty((batch, no, no), dtype=torch.float64, device=P.device)
     with torch.cuda.device(P.device):
-        rc = capi.load().mpcasm_qp_solve(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
+        rc = getattr(capi.load(), entry)(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
                                          x.data_ptr(), y.data_ptr(), z.data_ptr(), 1 if warm else 0,
                                          rho.data_ptr(), float(sigma), float(alpha), float(eps_abs),
                                          float(eps_rel), float(eps_prim_inf), float(eps_dual_inf), int(max_iter),
@@ -213,7 +225,7 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
                                          iters.data_ptr(), res.data_ptr(), batch,
                                          kinv.data_ptr() if kinv is not None else None, 1 if kinv_valid else 0,
                                          _stream_handle(torch, stream))
-    capi.check(rc, "mpcasm_qp_solve")
+    capi.check(rc, entry)
     return QpSolution(x, y, z, status, iters, res, rho)
 
 
@@ -224,6 +236,28 @@ def qp_solve_lds_bytes(no, nc):
     rc = capi.load().mpcasm_qp_solve_lds_bytes(int(no), int(nc), ctypes.byref(out))
     capi.check(rc, "mpcasm_qp_solve_lds_bytes")
     return int(out.value)
+
+
+def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
+                  eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
+                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None):
+    """:func:`solve_qp` for QPs whose matrices do not fit on chip (``mpcasm_qp_solve_wide``): the same
+    arguments, rules and :class:`QpSolution`, up to 512 unknowns and 2 048 limits (:func:`qp_solve_wide_info`).
+    ``G`` is read in place once per iteration; ``K^-1`` lives in LDS where it fits, else in ``kinv`` -- a
+    ``(B, no, no)`` workspace allocated here when the caller passes none (the environment variable
+    ``MPCASM_QP_WIDE_KINV`` = ``lds`` / ``global`` overrides where it lives)."""
+    return _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
+                     eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
+                     stream, out, workspace=True)
+
+
+def qp_solve_wide_info(no, nc):
+    """``(lds_bytes, kinv_on_chip)`` of one instance of :func:`solve_qp_wide`; ``MpcasmError`` with ``ERR_LIMIT``
+    past its size limit (``mpcasm_qp_solve_wide_info``)."""
+    lds, on = ctypes.c_int64(), ctypes.c_int32()
+    rc = capi.load().mpcasm_qp_solve_wide_info(int(no), int(nc), ctypes.byref(lds), ctypes.byref(on))
+    capi.check(rc, "mpcasm_qp_solve_wide_info")
+    return int(lds.value), bool(on.value)
 
 
 # every outcome but NON_CVX (whose iterates are NaN) / the solved ones and those out of iterations: the
