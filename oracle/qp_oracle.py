@@ -28,18 +28,19 @@ import numpy as np
 # --------------------------------------------------------------------------
 # a1  tools.extend_matrices                                   tools.py:14-33
 # --------------------------------------------------------------------------
-def extend_matrices(N, A, B):
+def extend_matrices(N, A, B, dtype=float):
     """``S[k, j, i] = (A^{k+1})[i, j]``, ``U[j][k, l, i] = (A^{k-l} B)[i, j]``.
 
     Same recurrence as tools.py:23-29 (left-multiply the previous block row by
     ``A``; no repeated squaring), written per block instead of per stacked row.
+    ``dtype``: the arithmetic (``np.longdouble`` for the tests' precise reference).
     """
-    A = np.asarray(A, dtype=float)
-    B = np.asarray(B, dtype=float)
+    A = np.asarray(A, dtype=dtype)
+    B = np.asarray(B, dtype=dtype)
     n, m = B.shape
 
-    S = np.zeros([N, n, n])
-    U = [np.zeros([N, N, n]) for _ in range(m)]
+    S = np.zeros([N, n, n], dtype=dtype)
+    U = [np.zeros([N, N, n], dtype=dtype) for _ in range(m)]
 
     power = A.copy()                     # A^{k+1}
     blocks = [B.copy()]                  # blocks[d] = A^d B, built by A.dot(previous)
@@ -55,7 +56,7 @@ def extend_matrices(N, A, B):
     return S, U
 
 
-def extend_matrices_ltv(N, A_steps, B_steps):
+def extend_matrices_ltv(N, A_steps, B_steps, dtype=float):
     """Per-step dynamics ``x_{k+1} = A_k x_k + B_k u_k``.
 
     ``S[k] = (A_k ... A_0)^T``, ``U[j][k, l, :] = (A_k ... A_{l+1} B_l)[:, j]``.
@@ -63,13 +64,13 @@ def extend_matrices_ltv(N, A_steps, B_steps):
     when all steps share one ``(A, B)`` (the only case the reference has,
     dynamics.py:222-231).
     """
-    A_steps = np.asarray(A_steps, dtype=float)
-    B_steps = np.asarray(B_steps, dtype=float)
+    A_steps = np.asarray(A_steps, dtype=dtype)
+    B_steps = np.asarray(B_steps, dtype=dtype)
     n, m = B_steps.shape[1:]
-    S = np.zeros([N, n, n])
-    U = [np.zeros([N, N, n]) for _ in range(m)]
-    row = np.zeros([N, n, m])            # row[l] = A_k..A_{l+1} B_l for the current k
-    power = np.eye(n)
+    S = np.zeros([N, n, n], dtype=dtype)
+    U = [np.zeros([N, N, n], dtype=dtype) for _ in range(m)]
+    row = np.zeros([N, n, m], dtype=dtype)   # row[l] = A_k..A_{l+1} B_l for the current k
+    power = np.eye(n, dtype=dtype)
     for k in range(N):
         power = A_steps[k].dot(power)
         S[k] = power.T
@@ -116,8 +117,19 @@ def qp_index_maps(domain, optim_variables):
 # --------------------------------------------------------------------------
 # a4  preview matrices                                      body.py:149-193
 # --------------------------------------------------------------------------
-def preview_matrices(form, maps=None):
-    """``PM[var] = (Mg, Mo)`` for every definition, in definition order."""
+def _datum(x, dtype, magnitude):
+    """``x`` in the arithmetic ``dtype``; its absolute value for the magnitude of the result."""
+    x = np.asarray(x, dtype=dtype)
+    return np.abs(x) if magnitude else x
+
+
+def preview_matrices(form, maps=None, dtype=float, magnitude=False):
+    """``PM[var] = (Mg, Mo)`` for every definition, in definition order.
+
+    ``dtype``: the arithmetic.  ``magnitude=True``: the same sums over the absolute values of the
+    coefficients (the componentwise bound of the rounding errors, with ``|S|``, ``|U|`` in the
+    dynamics' matrices).
+    """
     if maps is None:
         maps = qp_index_maps(form.domain, form.optim_variables)
     ng, no = maps["given_len"], maps["optim_len"]
@@ -125,8 +137,10 @@ def preview_matrices(form, maps=None):
     for var, combo in form.definitions.items():
         if var in form.of:                                  # body.py:158-177
             rows = form.dynamics[form.of[var]].all_variables[var]
-            Mg, Mo = np.zeros([rows, ng]), np.zeros([rows, no])
+            Mg, Mo = np.zeros([rows, ng], dtype=dtype), np.zeros([rows, no], dtype=dtype)
             for dep, coef in combo.items():
+                if magnitude:
+                    coef = np.abs(np.asarray(coef, dtype=dtype))
                 if dep in maps["given_variables"]:
                     Mg[:, maps["given_ID"][dep]] = coef
                 elif dep in maps["optim_variables"]:
@@ -139,7 +153,9 @@ def preview_matrices(form, maps=None):
         else:                                               # body.py:179-193
             Mg = Mo = None
             for dep, coef in combo.items():
-                c = np.array(coef)
+                c = np.array(coef) if dtype is float else np.array(coef, dtype=dtype)
+                if magnitude:
+                    c = np.array(np.abs(c))
                 tg, to = c.dot(PM[dep][0]), c.dot(PM[dep][1])
                 if Mg is None:
                     Mg, Mo = tg, to
@@ -175,21 +191,25 @@ def constraint_nlines(limit):
     return wide[0] if wide else None
 
 
-def constraint_coefficients(limit):
-    cols = [limit.arrow[:, i][:, None] for i in range(len(limit.axes))]
+def constraint_coefficients(limit, dtype=float, magnitude=False):
+    arrow = _datum(limit.arrow, dtype, magnitude)
+    cols = [arrow[:, i][:, None] for i in range(len(limit.axes))]
     if limit.L:
-        return [c * l for c, l in zip(cols, limit.L)]
+        return [c * _datum(l, dtype, magnitude) for c, l in zip(cols, limit.L)]
     return cols
 
 
-def constraint_bound(limit):
-    return limit.extreme + np.sum(limit.arrow * limit.center, axis=1).reshape([-1, 1])
+def constraint_bound(limit, dtype=float, magnitude=False):
+    arrow, center = _datum(limit.arrow, dtype, magnitude), _datum(limit.center, dtype, magnitude)
+    return _datum(limit.extreme, dtype, magnitude) + np.sum(arrow * center, axis=1).reshape([-1, 1])
 
 
 # --------------------------------------------------------------------------
 # a7  one constraint                                        body.py:236-264
 # --------------------------------------------------------------------------
-def qp_constraint(PM, limit, given):
+def qp_constraint(PM, limit, given, dtype=float, magnitude=False):
+    """``magnitude=True``: absolute values of the data, ``bound + cMg given`` (``PM`` and ``given``
+    of the magnitude too)."""
     Mg0 = PM[limit.variable + limit.axes[0]][0]
     rows = Mg0.shape[0]
     nlines = constraint_nlines(limit)
@@ -197,9 +217,9 @@ def qp_constraint(PM, limit, given):
     ng = Mg0.shape[1]
     no = PM[limit.variable + limit.axes[0]][1].shape[1]
 
-    cMg, cMo = np.zeros([out_rows, ng]), np.zeros([out_rows, no])
+    cMg, cMo = np.zeros([out_rows, ng], dtype=dtype), np.zeros([out_rows, no], dtype=dtype)
     picked = limit.schedule if limit.schedule else range(rows)
-    coefs = constraint_coefficients(limit)
+    coefs = constraint_coefficients(limit, dtype, magnitude)
     for i, axis in enumerate(limit.axes):
         Mg, Mo = PM[limit.variable + axis]
         if limit.L:
@@ -208,31 +228,42 @@ def qp_constraint(PM, limit, given):
         else:
             cMg += coefs[i] * Mg[picked]
             cMo += coefs[i] * Mo[picked]
-    return cMo, constraint_bound(limit) - cMg @ given
+    given = _datum(given, dtype, magnitude)
+    if magnitude:
+        return cMo, constraint_bound(limit, dtype, True) + cMg @ given
+    return cMo, constraint_bound(limit, dtype) - cMg @ given
 
 
 # --------------------------------------------------------------------------
 # a9  one cost                                              body.py:266-302
 # --------------------------------------------------------------------------
-def qp_cost(PM, cost, given):
+def qp_cost(PM, cost, given, dtype=float, magnitude=False):
+    """``magnitude=True``: absolute values of the data, both differences ``... given - aim`` as sums
+    (``PM`` and ``given`` of the magnitude too)."""
     first = PM[cost.variable + cost.axes[0]]
     rows, no = first[0].shape[0], first[1].shape[1]
-    Q, q = np.zeros([no, no]), np.zeros([no, 1])
+    Q, q = np.zeros([no, no], dtype=dtype), np.zeros([no, 1], dtype=dtype)
     picked = cost.schedule if cost.schedule else range(rows)
+    given = _datum(given, dtype, magnitude)
+    weight = cost.weight if dtype is float and not magnitude else _datum(cost.weight, dtype, magnitude)
+    aim, cross_aim = _datum(cost.aim, dtype, magnitude), _datum(cost.cross_aim, dtype, magnitude)
+    sign = 1 if magnitude else -1
 
     for i, axis in enumerate(cost.axes):
         vMg, vMo = (M[picked] for M in PM[cost.variable + axis])
         cMg, cMo = (M[picked] for M in PM[cost.cross + axis])
         if cost.L:
-            vMg, vMo = cost.L[i] @ vMg, cost.L[i] @ vMo
+            L = _datum(cost.L[i], dtype, magnitude)
+            vMg, vMo = L @ vMg, L @ vMo
         if cost.cross_L:
-            cMg, cMo = cost.cross_L[i] @ cMg, cost.cross_L[i] @ cMo
+            L = _datum(cost.cross_L[i], dtype, magnitude)
+            cMg, cMo = L @ cMg, L @ cMo
 
-        Q += cost.weight * vMo.T @ cMo                       # (w vMo^T) @ cMo
+        Q += weight * vMo.T @ cMo                            # (w vMo^T) @ cMo
         q += (
-            cost.weight
-            * (vMo.T @ (cMg @ given - cost.cross_aim[:, i])
-               + cMo.T @ (vMg @ given - cost.aim[:, i]))
+            weight
+            * (vMo.T @ (cMg @ given + sign * cross_aim[:, i])
+               + cMo.T @ (vMg @ given + sign * aim[:, i]))
             / 2
         )
     return Q, q
@@ -248,30 +279,37 @@ def all_limits(form):
     return limits
 
 
-def qp_all_constraints(form, PM, given):
-    parts = [qp_constraint(PM, limit, given) for limit in all_limits(form)]
+def qp_all_constraints(form, PM, given, dtype=float, magnitude=False):
+    parts = [qp_constraint(PM, limit, given, dtype, magnitude) for limit in all_limits(form)]
     return np.vstack([p[0] for p in parts]), np.vstack([p[1] for p in parts])
 
 
-def qp_all_costs(form, PM, given):
-    parts = [qp_cost(PM, cost, given) for cost in form.goals.values()]
+def qp_all_costs(form, PM, given, dtype=float, magnitude=False):
+    parts = [qp_cost(PM, cost, given, dtype, magnitude) for cost in form.goals.values()]
     return (np.add.reduce([p[0] for p in parts]),
             np.add.reduce([p[1] for p in parts]))
 
 
-def assemble(form, given, PM=None, maps=None):
-    """``(A, h, Q, q)`` = qpsolvers ``(G, h, P, q)`` (body.py:333-348)."""
+def assemble(form, given, PM=None, maps=None, dtype=float, magnitude=False):
+    """``(A, h, Q, q)`` = qpsolvers ``(G, h, P, q)`` (body.py:333-348).
+
+    ``dtype``: the arithmetic.  ``magnitude=True``: the componentwise magnitude of every result,
+    the same sums over the absolute values of every datum with the three differences as sums.
+    """
     if maps is None:
         maps = qp_index_maps(form.domain, form.optim_variables)
     if PM is None:
-        PM = preview_matrices(form, maps)
-    A, h = qp_all_constraints(form, PM, given)
-    Q, q = qp_all_costs(form, PM, given)
+        PM = preview_matrices(form, maps, dtype, magnitude)
+    A, h = qp_all_constraints(form, PM, given, dtype, magnitude)
+    Q, q = qp_all_costs(form, PM, given, dtype, magnitude)
     return A, h, Q, q
 
 
-def preview(PM, given, optim, variable, axes=None):
-    """``Mg @ given + Mo @ optim`` (body.py:209-219)."""
+def preview(PM, given, optim, variable, axes=None, dtype=float, magnitude=False):
+    """``Mg @ given + Mo @ optim`` (body.py:209-219); ``magnitude=True``: over absolute values."""
+    if dtype is not float or magnitude:
+        given, optim = _datum(given, dtype, magnitude), _datum(optim, dtype, magnitude)
+        PM = {v: (_datum(Mg, dtype, magnitude), _datum(Mo, dtype, magnitude)) for v, (Mg, Mo) in PM.items()}
     if axes is None:
         Mg, Mo = PM[variable]
         return Mg @ given + Mo @ optim

@@ -5,7 +5,7 @@ the kernel follows the reference recurrence, so the observed error is ~1e-16.
 import numpy as np
 import pytest
 
-from helpers import RTOL, RTOL_TIGHT, assert_close, golden
+from helpers import LD, RTOL, RTOL_TIGHT, assert_close, assert_componentwise, golden, kappa
 from oracle import qp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -145,6 +145,11 @@ def test_ltv_lipm_config_c5(eng, gpu_api):
     So, Uo = orc.extend_matrices_ltv(100, A, B)
     assert_close(S[0], So, RTOL)
     assert_close(U[0], np.stack(Uo), RTOL)
+    # element by element against extended precision
+    S1, U1 = orc.extend_matrices_ltv(100, A, B, dtype=LD)
+    S2, U2 = orc.extend_matrices_ltv(100, np.abs(A), np.abs(B), dtype=LD)
+    assert_componentwise(S[0], S1, S2, kappa(100, 3), "S")
+    assert_componentwise(U[0], np.stack(U1), np.stack(U2), kappa(100, 3), "U")
 
 
 def test_full_size_properties_c2_and_c4(eng):

@@ -7,7 +7,7 @@ Tolerance: 1e-10 relative (north star) where stated, else the tight regression b
 import numpy as np
 import pytest
 
-from helpers import RTOL, RTOL_TIGHT, assert_close
+from helpers import LD, RTOL, RTOL_TIGHT, assert_close, assert_componentwise, kappa
 from mpcasm import problems
 from oracle import qp_oracle as orc
 
@@ -129,6 +129,11 @@ def test_c5_ltv_fill_at_2048_systems(gpu_api, torch_gpu):
         So, Uo = orc.extend_matrices_ltv(N, A[b], Bm[b])
         assert_close(S[b].cpu().numpy(), So, RTOL_TIGHT)
         assert_close(U[b].cpu().numpy(), np.stack(Uo), RTOL_TIGHT)
+        # element by element against extended precision
+        S1, U1 = orc.extend_matrices_ltv(N, A[b], Bm[b], dtype=LD)
+        S2, U2 = orc.extend_matrices_ltv(N, np.abs(A[b]), np.abs(Bm[b]), dtype=LD)
+        assert_componentwise(S[b].cpu().numpy(), S1, S2, kappa(N, 3), "S of system %d" % b)
+        assert_componentwise(U[b].cpu().numpy(), np.stack(U1), np.stack(U2), kappa(N, 3), "U of system %d" % b)
 
 
 def test_ltv_fill_feeds_the_assembly(gpu_api, torch_gpu):

@@ -5,7 +5,7 @@ the reference, against the ``lti`` path where all steps share one pair."""
 import numpy as np
 import pytest
 
-from helpers import RTOL, RTOL_TIGHT, assert_close, lti_tracking_problem
+from helpers import RTOL, RTOL_TIGHT, assert_close, assert_componentwise, kappa, lti_tracking_problem, precise_reference
 from mpcasm import problems
 from mpcasm.plan import _H
 from oracle import qp_oracle as orc
@@ -84,6 +84,10 @@ def test_c5_assembly_at_2048_instances(gpu_api, torch_gpu):
                                         g0[b].cpu().numpy())
             assert_close(P[b].cpu().numpy(), Qo, RTOL), assert_close(q[b].cpu().numpy(), qo.ravel(), RTOL)
             assert_close(G[b].cpu().numpy(), Ao, RTOL), assert_close(h[b].cpu().numpy(), ho.ravel(), RTOL)
+            # element by element against extended precision (the block measure cannot see the small elements)
+            ref = precise_reference(form, "LIP", A[b], Bm[b], g0[b].cpu().numpy(), ltv=True)
+            for key, x in zip("PqGh", (P, q, G, h)):
+                assert_componentwise(x[b].cpu().numpy(), *ref[key], kappa(N, 3), "instance %d %s" % (b, key))
     finally:
         goal.update(weight=w0)
     # q, h affine in given; P, G independent of it
@@ -130,6 +134,11 @@ def test_all_steps_one_pair_is_the_lti_path(gpu_api, torch_gpu):
         Pb, qb, Gb, hb = (t[b].cpu().numpy() for t in mine)
         assert_close(Pb, Qo, RTOL_TIGHT), assert_close(qb, qo.ravel(), RTOL_TIGHT)
         assert_close(Gb, Ao, RTOL_TIGHT), assert_close(hb, ho.ravel(), RTOL_TIGHT)
+        # element by element against extended precision, the sweep kernel and the lti path alike
+        ref = precise_reference(form, "LIP", A[b], Bm[b], given[b].cpu().numpy())
+        for route, results in (("sweep", mine), ("lti", theirs)):
+            for key, x in zip("PqGh", results):
+                assert_componentwise(x[b].cpu().numpy(), *ref[key], kappa(N, 3), "%s, instance %d %s" % (route, b, key))
     # the nominal pair of the formulation itself, before any bind_ltv: the drop-in's own numbers
     fresh = engine.Assembler(form, batch=2, ltv=["LIP"])
     Ao, ho, Qo, qo = orc.assemble(form, given[0].cpu().numpy().reshape(-1, 1))
