@@ -182,6 +182,19 @@ __device__ __forceinline__ void dma4(const void* gsrc, unsigned lds_base) {
       : "memory");
 }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// ... for all but the last `later` loads of this wave (wave-uniform; vector loads, LDS-DMA ones
+// included, return in the order of their issue).  `later` must not exceed what the wave has really
+// issued since the loads it waits for: too small a number only waits longer, and so does any load or
+// store the compiler adds in between.  One s_waitcnt when `later` is a constant.
+__device__ __forceinline__ void dma_wait_but(int later) {
+  switch (later) {
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+  }
+}
 
 // Row of a 16-row trip that lane row lk feeds to k-step 0 (k-step u: that row + u).  The two
 // lane rows one 32-lane LDS read serves (lk = 0, 1 and 2, 3) lie 8 rows apart: with
@@ -318,8 +331,10 @@ __device__ __forceinline__ void resident_body(
   // written to the otherwise unused workspace; no result depends on them
   unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = 0;
   // ... and, behind those of all workgroups, cycles since the kernel's start at the stations
-  // of the set-up (0 stream tables in LDS, 1 first barrier, 2 compose program in registers,
-  // 3 first tables generated, 4 structure tables copied, 5 barrier, 6 first image landed)
+  // of the set-up (0 wave 0: fetch tables in LDS, first (A, B) and image asked for, 1 first barrier,
+  // 2 per-lane fetch addresses worked out (wave 0: before it asks for the image), 3 structure tables
+  // copied, 4 wave 0: first (A, B) landed, 5 wave 0: first tables generated, 6 barrier, 7 first image
+  // landed: the loop starts)
   const unsigned long long t_begin = STAMPS ? __builtin_amdgcn_s_memtime() : 0;
 #define SETUP_STAMP(k)                                                                  \
   if (STAMPS && stamps != nullptr && lane == 0)                                         \
@@ -355,105 +370,6 @@ __device__ __forceinline__ void resident_body(
   // LDS byte address of the image double buffer (the low half of a flat LDS address)
   const unsigned img_lds = (unsigned)(uintptr_t)(lds + L.img);  // (rs_img doubles each, rs_img_dma of them loaded)
   const int unit = p.rs_unit, nchunk = p.rs_nchunk;
-
-  // ---- once per workgroup, first: what the input fetch needs (stream table, per-lane load
-  // tables), so that the first instance's image is on its way while the rest is set up
-  {
-    const int2* t2 = reinterpret_cast<const int2*>(plan_itab + p.off_rs_abmeta);
-    for (int i = tid; i < p.rs_ab * 2; i += NT) abmeta[i] = t2[i];
-    t2 = reinterpret_cast<const int2*>(plan_itab + p.off_rs_inmeta);
-    for (int i = tid; i < nchunk * 64; i += NT) meta[i] = t2[i];
-    for (int i = tid; i < p.rs_nlti * RS_LTI_WORDS; i += NT) lti[i] = (plan_itab + p.off_rs_lti)[i];
-    // input streams: the sources, then given, params, the plan's constants
-    // (wave-uniform index into the kernel's arguments: scalar loads out of the argument segment, which
-    // the scalar cache already holds -- indexed by the lane, the table would be fetched by vector
-    // loads from wherever the runtime keeps kernel arguments, and the first barrier would wait for it)
-    if (wave == 0)
-      for (int t = 0; t < p.nsrc + 3; ++t) {
-        const int s = t - p.nsrc;
-        const double* base = s < 0 ? src.ptr[t]
-                                   : (s == 0 ? given : (s == 1 ? params : plan_dtab + p.doff_rs_const));
-        const long long stride =
-            s < 0 ? src.stride[t] : (s == 0 ? (long long)p.ng : (s == 1 ? (long long)p.nparams : 0));
-        if (lane == 0) {
-          reinterpret_cast<const double**>(strm)[2 * t] = base;
-          reinterpret_cast<long long*>(strm)[2 * t + 1] = stride * (long long)sizeof(double);
-        }
-      }
-  }
-  SETUP_STAMP(0)
-  lds_barrier();
-  SETUP_STAMP(1)
-  // The matrix waves fetch instance `inst`'s image into buffer `buf` (chunks dealt round
-  // robin).  With registers to spare (FK > 0) a lane keeps the address of its piece of the
-  // first FK chunks of its wave -- pointer into instance 0 and bytes per instance -- so that
-  // a load costs one multiply-add; further chunks look their stream up in LDS.
-#ifdef MPCASM_SPEC
-  constexpr int FK = JC <= 5 ? 3 : 0;
-#else
-  constexpr int FK = 0;  // (the ahead-of-time kernel has no registers to spare: it looks the streams up)
-#endif
-  // The `given` rows of a launch may be picked by an index (mpcasm_assemble_indexed: a fleet's bucket takes
-  // its walkers' rows out of the fleet-wide array, no gather pass): the table travels in the last,
-  // unused slot of the source table, marked by a stride of -1; instance b reads row gix[b] of `given`
-  // and row b of everything else.
-  const int32_t* gix = src.stride[MAX_SOURCES - 1] == -1
-                           ? reinterpret_cast<const int32_t*>(src.ptr[MAX_SOURCES - 1]) : nullptr;
-  const char* f_base[FK > 0 ? FK : 1];
-  int f_stride[FK > 0 ? FK : 1];
-  bool f_isg[FK > 0 ? FK : 1];   // the lane's piece of the chunk comes out of `given`
-  // A chunk whose every lane reads a stream shared by the whole batch (stride 0: one model
-  // for all instances, the constants) holds the same bytes for every instance: once both
-  // halves of the double buffer have it, it is not fetched again.
-  bool f_shared[FK > 0 ? FK : 1];
-  bool f_fast = FK > 0;
-  if (FK > 0 && wave < MW) {
-#pragma unroll
-    for (int j = 0; j < FK; ++j) {
-      const int k = wave + j * MW;
-      const int2 m = meta[(k < nchunk ? k : 0) * 64 + lane];
-      const long long stride = reinterpret_cast<const long long*>(strm)[2 * m.x + 1];
-      f_base[j] = reinterpret_cast<const char* const*>(strm)[2 * m.x] + m.y;
-      f_stride[j] = (int)stride;
-      f_isg[j] = m.x == p.nsrc;
-      f_shared[j] = __all(stride == 0);
-      f_fast = f_fast && stride >= 0 && stride < (1ll << 31);
-    }
-  }
-  f_fast = __builtin_amdgcn_readfirstlane(__all(f_fast));
-  // `settled`: both image buffers have been filled once by this workgroup
-  auto fetch_image = [&](long inst, int buf, bool settled) {
-    const unsigned dst0 = img_lds + (unsigned)buf * (unsigned)p.rs_img * 8u;
-    const long ginst = gix != nullptr ? (long)gix[inst] : inst;   // (wave-uniform: one scalar load)
-    int kfirst = wave;
-    if (FK > 0 && f_fast) {
-#pragma unroll
-      for (int j = 0; j < FK; ++j) {
-        const int k = wave + j * MW;
-        if (k < nchunk && !(settled && f_shared[j])) {
-          const char* a = f_base[j] + (unsigned long long)(f_isg[j] ? ginst : inst) * (unsigned)f_stride[j];
-          const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + (unsigned)(k * 64 * unit));
-          if (unit == 16)
-            dma16(a, dst);
-          else
-            dma4(a, dst);
-        }
-      }
-      kfirst = wave + FK * MW;
-    }
-    for (int k = kfirst; k < nchunk; k += MW) {
-      const int2 m = meta[k * 64 + lane];
-      const char* base = reinterpret_cast<const char* const*>(strm)[2 * m.x];
-      const long long stride = reinterpret_cast<const long long*>(strm)[2 * m.x + 1];
-      if (settled && __all(stride == 0)) continue;
-      const char* a = base + (m.x == p.nsrc ? ginst : inst) * stride + m.y;
-      const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + (unsigned)(k * 64 * unit));
-      if (unit == 16)
-        dma16(a, dst);
-      else
-        dma4(a, dst);
-    }
-  };
   const int lx = lane & 3, lg = (lane >> 2) & 3, lk = lane >> 4;
   // K1 on chip: the horizon matrices of an LTI system, as the tables the compose ops read
   // (TA[k][i][j] = (A^{k+1})[i][j], TB[d][i][j] = (A^d B)[i][j]; tools.py:14-33), from the
@@ -584,17 +500,43 @@ __device__ __forceinline__ void resident_body(
   auto instance_at = [&](int n) -> long {
     return ((((long)(n >> run_shift) * gridDim.x + vblock)) << run_shift) + (n & ((1 << run_shift) - 1));
   };
-  if (wave < MW) {  // the first instance's inputs start their trip now
-    fetch_image(instance_at(0), 0, false);
-    if (wave == 0 && (GEN && p.rs_nlti != 0)) {
-      fetch_ab(instance_at(0), 0);
-      if (instance_at(1) < batch) fetch_ab(instance_at(1), 1);
-    }
+  // ---- once per workgroup: the set-up, ordered by what the FIRST instance waits for -- its (A, B),
+  // the tables built from them, its image.  Wave 0 goes a way of its own.  It is the fetch wave: it alone
+  // copies what the input fetch needs (the per-lane load tables, the records of the generated systems,
+  // the stream table; all loads first, then the stores), asks for the first (A, B) and the whole first
+  // image BEFORE the first barrier -- it reads only what it wrote itself -- and builds the first
+  // instance's horizon tables while the other seven, behind that barrier, ask for the compose program
+  // and the structure tables, zero the workspace and copy the tables.
+  // Two branches and not one body with tests of the wave index: the compiler places its waits for
+  // loads by what may be in flight on ANY path, so in one body wave 0 waited for the other waves'
+  // table loads, and the other waves, at the first barrier, for nearly all of their own.
+  // (Before: every wave copied a share of the fetch tables table by table -- load, wait, store: wave 0
+  // made three such trips before the first barrier, the others one, and everything behind waited.)
+  const bool gen = GEN && p.rs_nlti != 0;
+  const int ct = tid - 64, CT = NT - 64;  // wave 0 takes no part in the table copies
+  // P handed over block by block (L.p_direct): the blocks no term reaches are written as zeros
+  // after barrier C, 16 bytes per thread and piece (block, row, half of the row).  A thread's
+  // first ZK pieces are the same for every instance: where they go is worked out once (zoff, below
+  // the set-up: element offset in P | 1 << 30 one 16-byte store | 1 << 29 two elements; -1 nothing)
+  // from the block list's words, which are asked for here with everything else -- read from the
+  // table per instance, the load's trip to L2 and back sat on the stream waves' way to barrier A,
+  // and read between the set-up's last barrier and the loop, it was a trip of its own there.
+#ifdef MPCASM_SPEC
+  constexpr int ZK = 2;
+#else
+  constexpr int ZK = 0;  // (ahead of time: from the table, no registers held)
+#endif
+  int v_zb[ZK > 0 ? ZK : 1];
+  const int zt0 = tid >= MW * 64 ? tid - MW * 64 : tid + WT;  // (the order of the P / q phase)
+#pragma unroll
+  for (int k = 0; k < ZK; ++k) {
+    const int e = zt0 + k * NT;
+    v_zb[k] = L.p_direct && e < p.rs_nzblk * 8 ? (plan_itab + p.off_rs_zblk)[e >> 3] : 0;
   }
-  // ---- once per workgroup: the compose program into registers ------------------
+  // the compose program into registers
   int c_sg[JC], c_dst[JC];  // c_sg: image offset of the source | of the given value << 16
   double c_coef[JC];
-  {
+  auto load_program = [&]() __attribute__((always_inline)) {
     // one 16-byte record per op (H_OFF_RS_PROG): a quarter of the load instructions of the four tables
     // it is packed from -- the set-up of a launch is bound by how many loads 512 workgroups issue at once
     const int4* prog = reinterpret_cast<const int4*>(plan_itab + p.off_rs_prog);
@@ -606,42 +548,204 @@ __device__ __forceinline__ void resident_body(
       c_dst[j] = w.y;
       c_coef[j] = __hiloint2double(w.w, w.z);
     }
-  }
-  SETUP_STAMP(2)
-  if (wave == 0 && (GEN && p.rs_nlti != 0)) {
-    // wave 0 builds the first instance's tables as soon as its (A, B) are there, while the
-    // other waves copy the structure tables
-    dma_wait();
-    SETUP_STAMP(2)   // (wave 0: its station 2 is "the first (A, B) have landed")
-    generate_sources(0, 0);
-  }
-  const bool w0_busy = GEN && p.rs_nlti != 0;  // wave 0 takes no part in the table copies
-  const int ct = w0_busy ? tid - 64 : tid, CT = w0_busy ? NT - 64 : NT;
-  SETUP_STAMP(3)
-  // ---- once per workgroup: structure tables into LDS, workspace zeroed -----------
-  {
-    // All loads from the plan first (every one a trip to L2), then the LDS stores: table
-    // by table the latencies would add up.
+  };
+  // The matrix waves fetch instance `inst`'s image into buffer `buf` (chunks dealt round
+  // robin).  With registers to spare (FK > 0) a lane keeps the address of its piece of the
+  // first FK chunks of its wave -- pointer into instance 0 and bytes per instance -- so that
+  // a load costs one multiply-add; further chunks look their stream up in LDS.
+#ifdef MPCASM_SPEC
+  constexpr int FK = JC <= 5 ? 3 : 0;
+#else
+  constexpr int FK = 0;  // (the ahead-of-time kernel has no registers to spare: it looks the streams up)
+#endif
+  // The `given` rows of a launch may be picked by an index (mpcasm_assemble_indexed: a fleet's bucket takes
+  // its walkers' rows out of the fleet-wide array, no gather pass): the table travels in the last,
+  // unused slot of the source table, marked by a stride of -1; instance b reads row gix[b] of `given`
+  // and row b of everything else.
+  const int32_t* gix = src.stride[MAX_SOURCES - 1] == -1
+                           ? reinterpret_cast<const int32_t*>(src.ptr[MAX_SOURCES - 1]) : nullptr;
+  const char* f_base[FK > 0 ? FK : 1];
+  int f_stride[FK > 0 ? FK : 1];
+  bool f_isg[FK > 0 ? FK : 1];   // the lane's piece of the chunk comes out of `given`
+  // A chunk whose every lane reads a stream shared by the whole batch (stride 0: one model
+  // for all instances, the constants) holds the same bytes for every instance: once both
+  // halves of the double buffer have it, it is not fetched again.
+  bool f_shared[FK > 0 ? FK : 1];
+  bool f_fast = FK > 0;
+  // Compiled for one plan, wave 0 asks for its part of the program first of all and holds it across
+  // the set-up; the ahead-of-time kernel has no registers for that (it spills) and asks late.
+#ifdef MPCASM_SPEC
+  constexpr bool prog_early = true;
+#else
+  constexpr bool prog_early = false;
+#endif
+  auto prepare_fetch = [&]() __attribute__((always_inline)) {
+    if (FK > 0 && wave < MW) {
+#pragma unroll
+      for (int j = 0; j < FK; ++j) {
+        const int k = wave + j * MW;
+        const int2 m = meta[(k < nchunk ? k : 0) * 64 + lane];
+        const long long stride = reinterpret_cast<const long long*>(strm)[2 * m.x + 1];
+        f_base[j] = reinterpret_cast<const char* const*>(strm)[2 * m.x] + m.y;
+        f_stride[j] = (int)stride;
+        f_isg[j] = m.x == p.nsrc;
+        f_shared[j] = __all(stride == 0);
+        f_fast = f_fast && stride >= 0 && stride < (1ll << 31);
+      }
+    }
+    f_fast = __builtin_amdgcn_readfirstlane(__all(f_fast));
+  };
+  // `settled`: both image buffers have been filled once by this workgroup
+  auto fetch_image = [&](long inst, int buf, bool settled) {
+    const unsigned dst0 = img_lds + (unsigned)buf * (unsigned)p.rs_img * 8u;
+    const long ginst = gix != nullptr ? (long)gix[inst] : inst;   // (wave-uniform: one scalar load)
+    int kfirst = wave;
+    if (FK > 0 && f_fast) {
+#pragma unroll
+      for (int j = 0; j < FK; ++j) {
+        const int k = wave + j * MW;
+        if (k < nchunk && !(settled && f_shared[j])) {
+          const char* a = f_base[j] + (unsigned long long)(f_isg[j] ? ginst : inst) * (unsigned)f_stride[j];
+          const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + (unsigned)(k * 64 * unit));
+          if (unit == 16)
+            dma16(a, dst);
+          else
+            dma4(a, dst);
+        }
+      }
+      kfirst = wave + FK * MW;
+    }
+    for (int k = kfirst; k < nchunk; k += MW) {
+      const int2 m = meta[k * 64 + lane];
+      const char* base = reinterpret_cast<const char* const*>(strm)[2 * m.x];
+      const long long stride = reinterpret_cast<const long long*>(strm)[2 * m.x + 1];
+      if (settled && __all(stride == 0)) continue;
+      const char* a = base + (m.x == p.nsrc ? ginst : inst) * stride + m.y;
+      const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + (unsigned)(k * 64 * unit));
+      if (unit == 16)
+        dma16(a, dst);
+      else
+        dma4(a, dst);
+    }
+  };
+  if (wave == 0) {
+    constexpr int MK = 2;  // load-table words per lane in the first batch
+    const int nab2 = p.rs_ab * 2, nmeta = nchunk * 64, nltw = p.rs_nlti * RS_LTI_WORDS;
+    const int2* t_ab = reinterpret_cast<const int2*>(plan_itab + p.off_rs_abmeta);
+    const int2* t_meta = reinterpret_cast<const int2*>(plan_itab + p.off_rs_inmeta);
+    const int32_t* t_lti = plan_itab + p.off_rs_lti;
+    int2 v_ab = int2{0, 0}, v_meta[MK];
+    int v_lti = 0;
+    if (lane < nab2) v_ab = t_ab[lane];
+    if (lane < nltw) v_lti = t_lti[lane];
+#pragma unroll
+    for (int k = 0; k < MK; ++k) v_meta[k] = lane + k * 64 < nmeta ? t_meta[lane + k * 64] : int2{0, 0};
+    // (its share of the program behind them: the wait for the tables leaves exactly these loads out)
+    if (prog_early) load_program();
+    if (lane < nab2) abmeta[lane] = v_ab;
+    for (int i = lane + 64; i < nab2; i += 64) abmeta[i] = t_ab[i];
+    if (lane < nltw) lti[lane] = v_lti;
+    for (int i = lane + 64; i < nltw; i += 64) lti[i] = t_lti[i];
+#pragma unroll
+    for (int k = 0; k < MK; ++k)
+      if (lane + k * 64 < nmeta) meta[lane + k * 64] = v_meta[k];
+    for (int i = lane + MK * 64; i < nmeta; i += 64) meta[i] = t_meta[i];
+    // input streams: the sources, then given, params, the plan's constants
+    // (wave-uniform index into the kernel's arguments: scalar loads out of the argument segment, which
+    // the scalar cache already holds -- indexed by the lane, the table would be fetched by vector
+    // loads from wherever the runtime keeps kernel arguments, and the first barrier would wait for it)
+    for (int t = 0; t < p.nsrc + 3; ++t) {
+      const int s = t - p.nsrc;
+      const double* base = s < 0 ? src.ptr[t]
+                                 : (s == 0 ? given : (s == 1 ? params : plan_dtab + p.doff_rs_const));
+      const long long stride =
+          s < 0 ? src.stride[t] : (s == 0 ? (long long)p.ng : (s == 1 ? (long long)p.nparams : 0));
+      if (lane == 0) {
+        reinterpret_cast<const double**>(strm)[2 * t] = base;
+        reinterpret_cast<long long*>(strm)[2 * t + 1] = stride * (long long)sizeof(double);
+      }
+    }
+    // The first two instances' (A, B) and the WHOLE first image start their trip here, before the
+    // barrier: wave 0 reads only what it wrote itself (LDS operations of one wavefront complete in
+    // order), and the CU serves its loads in the order of their issue -- asked for behind the barrier,
+    // these few loads from HBM, which the first instance waits for, queue up behind the 50 KB of
+    // program and tables that the other waves of the CU ask for at the same moment.
+    if (gen) {
+      fetch_ab(instance_at(0), 0);
+      if (instance_at(1) < batch) fetch_ab(instance_at(1), 1);
+    }
+    SETUP_STAMP(2)
+    {
+      const long inst = instance_at(0), ginst = gix != nullptr ? (long)gix[inst] : inst;
+      for (int k = 0; k < nchunk; ++k) {
+        const int2 m = meta[k * 64 + lane];
+        const char* base = reinterpret_cast<const char* const*>(strm)[2 * m.x];
+        const long long stride = reinterpret_cast<const long long*>(strm)[2 * m.x + 1];
+        const char* a = base + (m.x == p.nsrc ? ginst : inst) * stride + m.y;
+        const unsigned dst = __builtin_amdgcn_readfirstlane(img_lds + (unsigned)(k * 64 * unit));
+        if (unit == 16)
+          dma16(a, dst);
+        else
+          dma4(a, dst);
+      }
+    }
+    SETUP_STAMP(0)
+    lds_barrier();
+    SETUP_STAMP(1)
+    prepare_fetch();
+    SETUP_STAMP(3)
+    if (gen) {
+      // the first instance's tables, as soon as its (A, B) are there: they were asked for before the
+      // image, so the wait leaves out the image's loads
+      dma_wait_but(nchunk);
+      SETUP_STAMP(4)
+      generate_sources(0, 0);
+    }
+    if (!prog_early) load_program();
+    SETUP_STAMP(5)
+  } else {
+    SETUP_STAMP(0)
+    lds_barrier();
+    SETUP_STAMP(1)
+    prepare_fetch();
+    SETUP_STAMP(2)
+    load_program();
+    // the structure tables: loaded now, landed in LDS behind the workspace's zeros (below)
+    // (plain vectors: as HIP's int4 / double2, the conditionally loaded values went through scratch memory --
+    // a store and a load of their own, each waited for, in the middle of the set-up)
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
     constexpr int RRK = 3;  // row-record words per thread in the first batch
     const int32_t* trr = plan_itab + p.off_rs_rr;  // row records of G, precomputed by the plan compiler
     const int nrr = p.rr_packed ? 0 : nc * RR_WORDS;  // (packed plans keep compact records, below)
     int v_rr[RRK], v_wtrip = 0, v_split = 0, v_rrwin = 0;
     int2 v_gd[GU], v_gfix = int2{0, 0};
-    int4 v_dpar = int4{0, 0, 0, 0}, v_rra = int4{0, 0, 0, 0}, v_rrb = int4{0, 0, 0, 0};
-    double2 v_dcoef = double2{0.0, 0.0};
+    i32x4 v_dpar = {0, 0, 0, 0};
+    i32x2 v_rrc = {0, 0}, v_rrp = {0, 0};  // of a compact row record: the centers, the packed words
+    int v_rre = 0;                         // ... and the extreme
+    f64x2 v_dcoef = {0.0, 0.0};
     const bool own_gd = resident_g_mode(p) == 2 && tid >= MW * 64;
     const bool own_diag = p.ndiag != 0 && ct >= 0 && ct < no;
     const int wt_ = tid - MW * 64;
+    if (own_diag) {
+      // the diagonal gterms on column ct; free slots read the 0.0 behind the parameters
+      v_dpar = reinterpret_cast<const i32x4*>(plan_itab + p.off_rs_dpar)[ct];
+      v_dcoef = reinterpret_cast<const f64x2*>(plan_dtab + p.doff_rs_dcoef)[ct];
+    }
     if (ct >= 0) {
 #pragma unroll
       for (int k = 0; k < RRK; ++k) v_rr[k] = ct + k * CT < nrr ? trr[ct + k * CT] : 0;
       if (ct < RS_WAVES * 2) v_wtrip = (plan_itab + p.off_rs_wtrip)[ct];
       if (ct < p.rs_nsplit) v_split = (plan_itab + p.off_rs_split)[ct];
-      // (the compact row record of row ct of G: words 8 .. 15 of its 64-byte record, two 16-byte
-      // loads in this batch -- read word by word behind the LDS stores, they cost a second trip)
+      // (the compact row record of row ct of G: words 8, 9 and 13 .. 15 of its 64-byte record, in this
+      // batch -- read word by word behind the LDS stores, they cost a second trip.  Only the words that
+      // are used: a register of a load in flight that nothing reads is handed to the next value, and
+      // that one's load then waits for everything issued so far)
       if (p.rr_packed && ct < nc) {
-        v_rra = reinterpret_cast<const int4*>(trr + ct * RR_WORDS)[2];
-        v_rrb = reinterpret_cast<const int4*>(trr + ct * RR_WORDS)[3];
+        v_rrc = *reinterpret_cast<const i32x2*>(trr + ct * RR_WORDS + RR_CENTER);
+        v_rre = trr[ct * RR_WORDS + RR_EXTREME];
+        v_rrp = *reinterpret_cast<const i32x2*>(trr + ct * RR_WORDS + RR_PACKED);
       }
       if (p.rs_compact && ct < nc) v_rrwin = (plan_itab + p.off_rs_rrwin)[ct];
     }
@@ -653,11 +757,7 @@ __device__ __forceinline__ void resident_body(
       for (int u = 0; u < GU; ++u) v_gd[u] = gd[u * WT + wt_];
       if (p.rs_ngfix != 0) v_gfix = reinterpret_cast<const int2*>(plan_itab + p.off_rs_gfix)[wt_];
     }
-    if (own_diag) {
-      // the diagonal gterms on column ct; free slots read the 0.0 behind the parameters
-      v_dpar = reinterpret_cast<const int4*>(plan_itab + p.off_rs_dpar)[ct];
-      v_dcoef = reinterpret_cast<const double2*>(plan_dtab + p.doff_rs_dcoef)[ct];
-    }
+    // workspace zeroed, structure tables into LDS
     if (ct >= 0) {
       // blocks of P no term reaches stay zero for the whole launch
       if (!L.p_direct)
@@ -677,7 +777,7 @@ __device__ __forceinline__ void resident_body(
       if (p.rr_packed) {
         static_assert(RR_CENTER == 8 && RR_EXTREME == 13 && RR_PACKED == 14, "the row record's second half");
         if (ct < nc)
-          reinterpret_cast<int4*>(rr)[ct] = int4{v_rrb.z, v_rrb.w, v_rra.x | (v_rra.y << 16), v_rrb.y};
+          reinterpret_cast<int4*>(rr)[ct] = int4{v_rrp.x, v_rrp.y, v_rrc.x | (v_rrc.y << 16), v_rre};
         for (int R = ct + CT; R < nc; R += CT) {
           const int32_t* g = trr + R * RR_WORDS;
           reinterpret_cast<int4*>(rr)[R] =
@@ -699,21 +799,20 @@ __device__ __forceinline__ void resident_body(
       if (p.rs_ngfix != 0) gfix[wt_] = v_gfix;
     }
     if (own_diag) {
-      dpar[ct] = v_dpar;
-      dcoef[ct] = v_dcoef;
+      dpar[ct] = int4{v_dpar.x, v_dpar.y, v_dpar.z, v_dpar.w};
+      dcoef[ct] = double2{v_dcoef.x, v_dcoef.y};
     }
+    SETUP_STAMP(3)
+    SETUP_STAMP(4)
+    SETUP_STAMP(5)
   }
-  SETUP_STAMP(4)
   lds_barrier();
-  SETUP_STAMP(5)
+  SETUP_STAMP(6)
   // column no + 1 of the workspace: ones, for the whole launch (nothing composes into it)
   for (int r = tid; r < p.rtot; r += NT) V[(p.rs_vrow0 + r) * ldv + vd + 1] = 1.0;
 
   const bool lookahead = (phases & 128) != 0;  // diagnostic: off = fetch only when needed
-  if (wave < MW) {
-    dma_wait();  // the first image (requested before the set-up above) has landed
-    SETUP_STAMP(6)
-  }
+  if (wave == 0) dma_wait();  // the first image has landed (wave 0 asked for all of it)
   SETUP_STAMP(7)
 
   // ---- K4 bookkeeping of the worker threads: piece e = wt + u WT of G is the 16 bytes
@@ -722,30 +821,15 @@ __device__ __forceinline__ void resident_body(
   const int npair = no >> 1;
   const int gtotal = nc * npair;
   const int g_mode = resident_g_mode(p);
-  // P handed over block by block (L.p_direct): the blocks no term reaches are written as zeros
-  // after barrier C, 16 bytes per thread and piece (block, row, half of the row).  A thread's
-  // first ZK pieces are the same for every instance: where they go is worked out once, here
-  // (element offset in P | 1 << 30 one 16-byte store | 1 << 29 two elements; -1 nothing) --
-  // read from the table per instance, the load's trip to L2 and back sat on the stream waves'
-  // way to barrier A.
-#ifdef MPCASM_SPEC
-  constexpr int ZK = 2;
-#else
-  constexpr int ZK = 0;  // (ahead of time: from the table, no registers held)
-#endif
-  int zoff[ZK > 0 ? ZK : 1];
-  {
-    const int t0 = tid >= MW * 64 ? tid - MW * 64 : tid + WT;  // (the order of the P / q phase)
-    const int32_t* zb = plan_itab + p.off_rs_zblk;
+  int zoff[ZK > 0 ? ZK : 1];  // (see v_zb above)
 #pragma unroll
-    for (int k = 0; k < ZK; ++k) {
-      const int e = t0 + k * NT;
-      zoff[k] = -1;
-      if (L.p_direct && e < p.rs_nzblk * 8) {
-        const int z = zb[e >> 3], row = 4 * (z >> 8) + ((e >> 1) & 3), col = 4 * (z & 255) + 2 * (e & 1);
-        if (row < no && col < no)
-          zoff[k] = (row * no + col) | (col + 1 < no ? ((no & 1) == 0 ? 1 << 30 : 1 << 29) : 0);
-      }
+  for (int k = 0; k < ZK; ++k) {
+    const int e = zt0 + k * NT;
+    zoff[k] = -1;
+    if (L.p_direct && e < p.rs_nzblk * 8) {
+      const int z = v_zb[k], row = 4 * (z >> 8) + ((e >> 1) & 3), col = 4 * (z & 255) + 2 * (e & 1);
+      if (row < no && col < no)
+        zoff[k] = (row * no + col) | (col + 1 < no ? ((no & 1) == 0 ? 1 << 30 : 1 << 29) : 0);
     }
   }
   // (row, column pair) of this thread's first piece, and the step from piece to piece

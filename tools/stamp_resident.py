@@ -59,10 +59,15 @@ def main():
 def setup_stamps(raw, grid):
     """Cycles since kernel start at the stations of the once-per-workgroup set-up."""
     s = raw[grid * 64:2 * grid * 64].reshape(grid, 8, 8).astype(np.float64)
-    names = ["stream tables", "barrier", "compose regs", "first tables", "tables copied", "barrier",
-             "first image", "loop"]
-    for w in (0, 1, 4, 7):
+    names = ["inputs asked", "barrier", "fetch ready", "tables copied", "(A,B) landed", "tables built",
+             "barrier", "loop"]
+    # every wavefront: the barriers wait for the last one, and the waves differ in what they load
+    for w in range(8):
         print("set-up, wave %d: " % w + "  ".join("%s %6.0f" % (n, v) for n, v in zip(names, s[:, w, :].mean(axis=0))))
+    # ... and how far the workgroups of one launch are apart at the loop's start
+    loop = s[:, :, 7].max(axis=1)
+    print("set-up, loop start over the workgroups (last wave of each): min %6.0f  median %6.0f  max %6.0f"
+          % (loop.min(), np.median(loop), loop.max()))
 
 
 if __name__ == "__main__":
