@@ -61,7 +61,7 @@ const char* mpcasm_status_string(int status);
  * kernel's Toeplitz form instead of its scan form, which sums P along diagonals).  The parity
  * tests use it to exercise every path; all paths give the same results. */
 enum { MPCASM_OPT_PATH = 1, MPCASM_OPT_PHASE_MASK = 2, MPCASM_OPT_RESIDENT_PER_CU = 3, MPCASM_OPT_JIT = 4,
-       MPCASM_OPT_P_DIRECT = 5, MPCASM_OPT_RESIDENT_GRID = 6 };
+       MPCASM_OPT_P_DIRECT = 5, MPCASM_OPT_RESIDENT_GRID = 6, MPCASM_OPT_JIT_FETCH_RUNS = 7 };
 /* MPCASM_OPT_PHASE_MASK is a profiling aid (timing-only ablation of the fused
  * kernels: bit 0 compose, 1 Hessian, 2 gradient, 3 constraints, 4 input staging
  * after the first instance, 5 P/q stores, 7 register prefetch of the next instance's
@@ -84,6 +84,9 @@ enum { MPCASM_OPT_PATH = 1, MPCASM_OPT_PHASE_MASK = 2, MPCASM_OPT_RESIDENT_PER_C
  * kernel): 0 (default) = for batches of at least 512 instances, when libhiprtc.so is there
  * (compiled once per plan structure and device, on the first such launch: that launch blocks
  * for the compilation, a second or two); 1 = for every batch; 2 = never.
+ * MPCASM_OPT_JIT_FETCH_RUNS (test aid, 0 .. 8, default 8): a chunk of the fetch tables with more runs of
+ * streams than this stays on the table path of the per-plan kernel (mpcasm_fetch_segments); read when a
+ * plan's kernel is first compiled and by mpcasm_jit_check, so that a small plan exercises both ways.
  * MPCASM_OPT_P_DIRECT (read by mpcasm_plan_create): how the persistent kernel writes P -- 1: its
  * 4x4 blocks go from the matrix core straight to HBM; 2: collected in LDS and copied out with
  * 16-byte stores whenever P fits there beside the workspace; 0 (default): as 1 when the launch
@@ -110,6 +113,17 @@ int mpcasm_resident_lds_bytes(const int32_t* h_itab, size_t n_itab, const double
  * MPCASM_ERR_HIP (compilation failed); the compiler's log goes to `log` (may be NULL). */
 int mpcasm_jit_check(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                      char* log, size_t log_capacity);
+/* Diagnostic, needs no device: how the per-plan kernel fetches the plan's inputs.  The fetch tables
+ * (one (stream, byte offset) per lane and 64-lane chunk: the (A, B) of the generated systems, then the
+ * image) are contiguous runs of streams and padding, and the per-plan kernel gets every chunk of at
+ * most `limit` runs (at most 8) as constants and works its lanes' addresses out by arithmetic; a
+ * chunk with more stays on the table.  Writes per chunk: kind (0: (A, B), 1: image), chunk, runs (0:
+ * on the table), then per run 6 words -- first lane, lanes, stream, first byte, bytes per lane step,
+ * period in lanes: lane l reads byte first + ((l - first lane) % period) * step of the stream.
+ * *n_words: the words that make up the answer; MPCASM_ERR_LIMIT when `capacity` is too small for
+ * them or the plan does not run on the persistent kernel. */
+int mpcasm_fetch_segments(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                          int limit, int32_t* out, size_t capacity, int64_t* n_words);
 
 /* Compile ahead of the first launch what a launch of `batch` instances of this plan would
  * compile (the persistent kernel specialised for the plan, MPCASM_OPT_JIT): a control loop calls

@@ -1133,6 +1133,11 @@ int mpcasm_set_option(int option, int value) {
     g_resident_per_cu = value;
     return MPCASM_OK;
   }
+  if (option == MPCASM_OPT_JIT_FETCH_RUNS) {
+    if (value < 0 || value > FS_MAX) return MPCASM_ERR_ARG;
+    g_jit_fetch_runs = value;
+    return MPCASM_OK;
+  }
   if (option == MPCASM_OPT_RESIDENT_GRID) {
     if (value < 0 || value > (1 << 20)) return MPCASM_ERR_ARG;
     g_resident_grid = value;
@@ -1267,7 +1272,7 @@ int mpcasm_jit_check(const int32_t* h_itab, size_t n_itab, const double* h_dtab,
       if (form == large && small != large && out != MPCASM_OK) break;
       d.rs_p_direct = form;
       // (through the disk cache, as a launch would: a second check of the same plan compiles nothing)
-      out = jit_code_for(jit_spec_header(d, h_itab), false, 0xBF, &code, &text) ? MPCASM_OK : MPCASM_ERR_HIP;
+      out = jit_code_for(jit_spec_header(d, h_itab, g_jit_fetch_runs), false, 0xBF, &code, &text) ? MPCASM_OK : MPCASM_ERR_HIP;
       if (small == large) break;
     }
   }
@@ -1276,6 +1281,22 @@ int mpcasm_jit_check(const int32_t* h_itab, size_t n_itab, const double* h_dtab,
     log[log_capacity - 1] = 0;
   }
   return out;
+}
+
+int mpcasm_fetch_segments(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                          int limit, int32_t* out, size_t capacity, int64_t* n_words) {
+  if (!h_itab || (n_dtab && !h_dtab) || !n_words || (capacity && !out) || limit < 0) return MPCASM_ERR_ARG;
+  const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
+  if (rc != MPCASM_OK) return rc;
+  PlanDev d;
+  memset(&d, 0, sizeof d);
+  plan_dev_from_tables(h_itab, &d);
+  if (!d.rs_ok) return MPCASM_ERR_LIMIT;
+  const std::vector<int32_t> words = jit_fetch_plan(d, h_itab, limit);
+  *n_words = (int64_t)words.size();
+  if (words.size() > capacity) return MPCASM_ERR_LIMIT;
+  if (!words.empty()) memcpy(out, words.data(), words.size() * sizeof(int32_t));
+  return MPCASM_OK;
 }
 
 int mpcasm_jit_stats(int64_t out[3]) {

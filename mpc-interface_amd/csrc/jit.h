@@ -11,10 +11,14 @@
 namespace mpcasm {
 
 extern int g_jit;         // MPCASM_OPT_JIT
+extern int g_jit_fetch_runs;  // MPCASM_OPT_JIT_FETCH_RUNS
 extern int g_phase_mask;  // fused.hip
 
 // "plan_spec.h" of a plan: its sizes and trip lists as constants
-std::string jit_spec_header(const PlanDev& d, const int32_t* h_itab);
+// (seg_limit: most runs a chunk of a fetch table may have to be fetched by arithmetic, at most FS_MAX)
+std::string jit_spec_header(const PlanDev& d, const int32_t* h_itab, int seg_limit = FS_MAX);
+// the fetch tables as runs per chunk: [kind, chunk, runs, runs x FS_WORDS] ... (jit.hip)
+std::vector<int32_t> jit_fetch_plan(const PlanDev& d, const int32_t* h_itab, int seg_limit);
 // resident.hip + that header -> gfx950 code object (needs libhiprtc.so, no device)
 // (phases >= 0: the phase mask as a constant of the build; -1: the kernel argument)
 int jit_compile(const std::string& header, std::vector<char>* code, std::string* log,

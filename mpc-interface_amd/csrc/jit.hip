@@ -4,7 +4,9 @@
 // turns the description into tables once; this file goes one step further for plans that
 // assemble large batches: it hands the persistent kernel's own source (resident.hip, the very
 // file that is also built ahead of time) to hiprtc together with a generated "plan_spec.h"
-// that states the plan's sizes and every wavefront's list of matrix-core trips as constants.
+// that states the plan's sizes, every wavefront's list of matrix-core trips, the fetch tables as
+// runs of streams (so that a workgroup asks for its first inputs without reading a table first) and
+// the records of the systems whose horizon tables are built on chip as constants.
 // What the ahead-of-time kernel interprets per instance -- trip records, flags, loop bounds,
 // kernel-argument reloads -- folds away: a trip is eight 8-byte LDS reads at immediate
 // offsets and four MFMAs.  The result is cached per plan structure; the ahead-of-time kernel
@@ -35,6 +37,7 @@
 namespace mpcasm {
 
 int g_jit = 0;  // MPCASM_OPT_JIT: 0 automatic (batches >= JIT_MIN_BATCH), 1 always, 2 never
+int g_jit_fetch_runs = FS_MAX;  // MPCASM_OPT_JIT_FETCH_RUNS (test aid): most runs a chunk may have to be fetched by arithmetic
 
 namespace {
 
@@ -89,11 +92,57 @@ void append(std::string& s, const char* fmt, long long v) {
 
 }  // namespace
 
+// One chunk of a fetch table -- `lanes` entries (stream, byte offset), one per lane of an LDS-DMA load --
+// as maximal runs: FS_WORDS words each, (first lane, lanes, stream, first byte, bytes per lane step,
+// period in lanes).  Lane l of a run reads byte `first byte + ((l - first lane) % period) * step` of its
+// stream; a plain run has period = lanes, the padding (the plan's two constants over and over) a period
+// of 1, 2 or 4 lanes.  The runs are taken greedily, the longest that starts at each lane.
+std::vector<int32_t> jit_fetch_segments(const int32_t* meta, int lanes) {
+  std::vector<int32_t> out;
+  for (int i = 0; i < lanes;) {
+    const int stream = meta[2 * i], byte0 = meta[2 * i + 1];
+    const int step = i + 1 < lanes && meta[2 * (i + 1)] == stream ? meta[2 * (i + 1) + 1] - byte0 : 0;
+    int best = 0, best_period = 0;
+    for (int period : {0, 4, 2, 1}) {  // (0: plain; a tie goes to the earlier form)
+      int n = 0;
+      while (i + n < lanes && meta[2 * (i + n)] == stream &&
+             meta[2 * (i + n) + 1] == byte0 + (period ? n % period : n) * (period == 1 ? 0 : step))
+        ++n;
+      if (n > best) best = n, best_period = period;
+    }
+    const int period = best_period && best_period < best ? best_period : best;
+    out.insert(out.end(), {i, best, stream, byte0, best > 1 && period > 1 ? step : 0, period});
+    i += best;
+  }
+  return out;
+}
+
+// The fetch tables of a plan by chunks, for the per-plan kernel: per chunk of the (A, B) slot (32 doubles
+// = 64 lanes of 4 bytes), then per chunk of the image, its runs -- or none when it has more than `limit`
+// (at most FS_MAX): that chunk stays on the table.  Returned as [kind (0: (A, B), 1: image), chunk, runs,
+// runs x FS_WORDS words] per chunk.
+std::vector<int32_t> jit_fetch_plan(const PlanDev& d, const int32_t* it, int limit) {
+  std::vector<int32_t> out;
+  if (limit > FS_MAX) limit = FS_MAX;
+  for (int kind = 0; kind < 2; ++kind) {
+    const int chunks = kind == 0 ? d.rs_ab / 32 : d.rs_nchunk;
+    const int32_t* meta = it + (kind == 0 ? d.off_rs_abmeta : d.off_rs_inmeta);
+    for (int k = 0; k < chunks; ++k) {
+      std::vector<int32_t> segs = jit_fetch_segments(meta + k * 128, 64);
+      // (the image's table-path chunks are kept as a 32-bit mask in the kernel)
+      if ((int)segs.size() > limit * FS_WORDS || (kind == 1 && k >= 32)) segs.clear();
+      out.insert(out.end(), {kind, k, (int32_t)(segs.size() / FS_WORDS)});
+      out.insert(out.end(), segs.begin(), segs.end());
+    }
+  }
+  return out;
+}
+
 // The constants of one plan as a header: PlanConst mirrors PlanDev's int fields (same names,
 // so the kernel body reads `p.no` either way), JC picks the compose-slot count the ahead-of-time
 // build would, TRIPS / WTRIP are the trip records (plan_tables.h RT_*) and the per-wavefront
 // ranges.
-std::string jit_spec_header(const PlanDev& d, const int32_t* it) {
+std::string jit_spec_header(const PlanDev& d, const int32_t* it, int seg_limit) {
   std::string s = "// generated by libmpcasm (jit.hip) for one plan\n#pragma once\n"
                   "namespace mpcasm {\nnamespace spec {\nstruct PlanConst {\n";
 #define MPCASM_X(f) append(s, "  static constexpr int " #f " = %lld;\n", (long long)d.f);
@@ -115,6 +164,43 @@ std::string jit_spec_header(const PlanDev& d, const int32_t* it) {
   for (int w = 0; w < RS_WAVES; ++w) {
     append(s, "{%lld, ", wt[2 * w]);
     append(s, "%lld}, ", wt[2 * w + 1]);
+  }
+  s += "};\n";
+  // the input fetch by arithmetic: the runs of every chunk of the (A, B) slot and of the image
+  // (FSEG_*_N[chunk] = 0: that chunk stays on the table), see jit_fetch_segments
+  const std::vector<int32_t> fetch = jit_fetch_plan(d, it, seg_limit);
+  for (int kind = 0; kind < 2; ++kind) {
+    const int chunks = kind == 0 ? d.rs_ab / 32 : d.rs_nchunk;
+    const char* name = kind == 0 ? "AB" : "IMG";
+    std::string counts, table;
+    long long on_table = 0;
+    for (size_t at = 0; at < fetch.size(); at += 3 + fetch[at + 2] * FS_WORDS) {
+      if (fetch[at] != kind) continue;
+      const int n = fetch[at + 2];
+      if (n == 0 && fetch[at + 1] < 32) on_table |= 1ll << fetch[at + 1];
+      append(counts, "%lld, ", n);
+      table += "  {";
+      for (int g = 0; g < FS_MAX; ++g) {
+        table += "{";
+        for (int w = 0; w < FS_WORDS; ++w) append(table, w ? ", %lld" : "%lld", g < n ? fetch[at + 3 + g * FS_WORDS + w] : 0);
+        table += "}, ";
+      }
+      table += "},\n";
+    }
+    if (chunks == 0) counts = "0", table = "  {},\n";
+    s += std::string("constexpr int FSEG_") + name + "_N[] = {" + counts + "};\n";
+    s += std::string("constexpr int FSEG_") + name + "[][8][6] = {\n" + table + "};\n";
+    // bit k: chunk k is fetched through the table (chunks from 32 on always are)
+    s += std::string("constexpr unsigned FSEG_") + name + "_TABLE = ";
+    append(s, "%lldu;\n", on_table);
+  }
+  // the records of the generated systems (plan_tables.h LT_*)
+  s += "constexpr int LTI[4][8] = {\n";
+  for (int g = 0; g < RS_LTI_MAX; ++g) {
+    s += "  {";
+    for (int w = 0; w < RS_LTI_WORDS; ++w)
+      append(s, w ? ", %lld" : "%lld", g < d.rs_nlti ? it[d.off_rs_lti + g * RS_LTI_WORDS + w] : 0);
+    s += "},\n";
   }
   s += "};\n}  // namespace spec\n}  // namespace mpcasm\n";
   return s;
@@ -272,8 +358,9 @@ std::map<std::pair<int, std::string>, JitKernel*> g_cache;
 // else selects a build
 struct FastKey {
   const void* itab;
-  int device, p_direct, phases;
+  int device, p_direct, phases, fetch_runs;
   bool operator<(const FastKey& o) const {
+    if (fetch_runs != o.fetch_runs) return fetch_runs < o.fetch_runs;
     if (itab != o.itab) return itab < o.itab;
     if (device != o.device) return device < o.device;
     if (p_direct != o.p_direct) return p_direct < o.p_direct;
@@ -325,7 +412,7 @@ const void* jit_kernel_for(const PlanDev& d, const int32_t* h_itab, int device, 
   // (the phase mask is a constant of the build: the shipped value in every normal process, one
   // more build per value a profiling tool sets)
   const int phases = stamps ? -1 : g_phase_mask;
-  const FastKey fast{d.itab, stamps ? device + 4096 : device, d.rs_p_direct, phases};
+  const FastKey fast{d.itab, stamps ? device + 4096 : device, d.rs_p_direct, phases, g_jit_fetch_runs};
   // a small launch does not start a compilation, but takes the kernel when it is there already
   // (mpcasm_plan_prepare, or an earlier large launch)
   const bool may_build = t_jit == 1 || batch >= JIT_MIN_BATCH;
@@ -339,7 +426,7 @@ const void* jit_kernel_for(const PlanDev& d, const int32_t* h_itab, int device, 
       slot = found->second;
     } else if (may_build) {
       // by the generated header's text: another plan of the same structure may have built it
-      header = jit_spec_header(d, h_itab);
+      header = jit_spec_header(d, h_itab, fast.fetch_runs);
       JitKernel*& by_text = g_cache[std::make_pair(fast.device, header + "//" + std::to_string(phases))];
       if (by_text == nullptr) {
         by_text = new JitKernel();

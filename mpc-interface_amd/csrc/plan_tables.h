@@ -341,6 +341,11 @@ constexpr int RS_BLOCKS_MAX = 255;  // 4-column blocks of the unknowns (one byte
 // the powers A^(2^s) they are built from
 enum { LT_N = 0, LT_M, LT_HORIZON, LT_A, LT_B, LT_TA, LT_TB, LT_TP, RS_LTI_WORDS = 8 };
 constexpr int RS_LTI_MAX = 4;
+// a run of a fetch table, as the per-plan kernel gets it (jit.hip jit_fetch_segments): lane l of
+// [FS_FIRST, FS_FIRST + FS_LANES) reads byte FS_BYTE + ((l - FS_FIRST) % FS_PERIOD) * FS_STEP of stream
+// FS_STREAM; at most FS_MAX runs per chunk, else the chunk stays on the table
+enum { FS_FIRST = 0, FS_LANES, FS_STREAM, FS_BYTE, FS_STEP, FS_PERIOD, FS_WORDS = 6 };
+constexpr int FS_MAX = 8;
 // row record of G: voff[4] (index of column 0 of the axis' row in the persistent kernel's
 // workspace layout, see RT_* below), arrow param[4], center param[4], naxes, extreme param, the
 // first two axes packed once more: voff0 | voff1 << 16, arrow0 | arrow1 << 16

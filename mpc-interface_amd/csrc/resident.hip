@@ -45,8 +45,10 @@
 // ONE source, two builds.  Ahead of time (libmpcasm.so) the kernel reads the plan's sizes and
 // the trip lists at run time.  Compiled by hiprtc for ONE plan (MPCASM_SPEC, jit.hip) the very
 // same body sees them as constants from a generated "plan_spec.h": the plan's sizes fold into
-// immediates (no kernel-argument reloads, no scalar-register spills) and every wavefront's
-// trip list is unrolled into straight-line code -- no records, no flag tests, no loop.
+// immediates (no kernel-argument reloads, no scalar-register spills), every wavefront's
+// trip list is unrolled into straight-line code -- no records, no flag tests, no loop --, the first
+// inputs are asked for at addresses worked out from the lane index (spec_lane_src) and the horizon
+// tables are built by loops of constant size.
 #ifdef __HIPCC_RTC__
 using __hip_internal::int32_t;
 using __hip_internal::int64_t;
@@ -299,6 +301,119 @@ __device__ __forceinline__ void spec_trip(TripState& s) {
   }
 }
 
+// ---- the input fetch of a specialised kernel: a lane's source by arithmetic --------------
+// The fetch tables are a few runs of streams and padding per 64-lane chunk (jit.hip
+// jit_fetch_segments, plan_tables.h FS_*); a chunk of at most FS_MAX runs reaches this build as
+// constants, and a lane finds its stream and offset by comparing its index with the runs' first
+// lanes -- no table to load before the first byte of input can be asked for.  The streams' bases
+// and strides are kernel arguments: scalar loads at constant offsets.
+struct LaneSrc {
+  const char* base;  // the lane's bytes in instance 0
+  long long stride;  // bytes per instance
+  bool isg;          // out of `given` (whose rows a launch may pick through an index)
+  int2 entry;        // what the fetch table says for the lane: (stream, byte offset)
+};
+static_assert(FS_MAX == 8 && FS_WORDS == 6 && RS_LTI_MAX == 4 && RS_LTI_WORDS == 8, "plan_spec.h, as jit.hip writes it");
+template <bool AB, int K>
+constexpr int spec_fetch_runs() {
+  if constexpr (AB)
+    return K < spec::PlanConst::rs_ab / 32 ? spec::FSEG_AB_N[K] : 0;
+  else
+    return K < spec::PlanConst::rs_nchunk ? spec::FSEG_IMG_N[K] : 0;
+}
+template <bool AB, int K, int S>
+__device__ __forceinline__ void spec_lane_run(LaneSrc& out, int lane, const SrcTable& src, const double* params,
+                                              const double* given, const double* plan_dtab) {
+  using PC = spec::PlanConst;
+  if constexpr (S < spec_fetch_runs<AB, K>()) {
+    constexpr int first = AB ? spec::FSEG_AB[K][S][FS_FIRST] : spec::FSEG_IMG[K][S][FS_FIRST];
+    constexpr int lanes = AB ? spec::FSEG_AB[K][S][FS_LANES] : spec::FSEG_IMG[K][S][FS_LANES];
+    constexpr int stream = AB ? spec::FSEG_AB[K][S][FS_STREAM] : spec::FSEG_IMG[K][S][FS_STREAM];
+    constexpr int byte0 = AB ? spec::FSEG_AB[K][S][FS_BYTE] : spec::FSEG_IMG[K][S][FS_BYTE];
+    constexpr int step = AB ? spec::FSEG_AB[K][S][FS_STEP] : spec::FSEG_IMG[K][S][FS_STEP];
+    constexpr int period = AB ? spec::FSEG_AB[K][S][FS_PERIOD] : spec::FSEG_IMG[K][S][FS_PERIOD];
+    static_assert(period >= lanes || (period & (period - 1)) == 0, "a periodic run repeats every 1, 2 or 4 lanes");
+    // (the streams as the set-up lists them: the sources, given, params, the plan's constants)
+    const char* base;
+    long long stride;
+    if constexpr (stream < PC::nsrc) {
+      base = reinterpret_cast<const char*>(src.ptr[stream]);
+      stride = src.stride[stream] * (long long)sizeof(double);
+    } else if constexpr (stream == PC::nsrc) {
+      base = reinterpret_cast<const char*>(given);
+      stride = (long long)PC::ng * (long long)sizeof(double);
+    } else if constexpr (stream == PC::nsrc + 1) {
+      base = reinterpret_cast<const char*>(params);
+      stride = (long long)PC::nparams * (long long)sizeof(double);
+    } else {
+      base = reinterpret_cast<const char*>(plan_dtab + PC::doff_rs_const);
+      stride = 0;
+    }
+    const int rel = lane - first;
+    const int off = byte0 + (period < lanes ? rel & (period - 1) : rel) * step;
+    if (S == 0 || lane >= first) {  // (the runs ascend: the last one that starts at or before the lane)
+      out.base = base + off;
+      out.stride = stride;
+      out.isg = stream == PC::nsrc;
+      out.entry = int2{stream, off};
+    }
+    spec_lane_run<AB, K, S + 1>(out, lane, src, params, given, plan_dtab);
+  }
+}
+template <bool AB, int K>
+__device__ __forceinline__ LaneSrc spec_lane_src(int lane, const SrcTable& src, const double* params,
+                                                 const double* given, const double* plan_dtab) {
+  LaneSrc out{nullptr, 0, false, int2{0, 0}};
+  spec_lane_run<AB, K, 0>(out, lane, src, params, given, plan_dtab);
+  return out;
+}
+// The LDS copies of the fetch tables, which the loop's fetches read: written from the same runs
+template <bool AB, int K>
+__device__ __forceinline__ void spec_write_table(int2* table, int lane, const SrcTable& src, const double* params,
+                                                 const double* given, const double* plan_dtab) {
+  if constexpr (K < (AB ? spec::PlanConst::rs_ab / 32 : spec::PlanConst::rs_nchunk)) {
+    table[K * 64 + lane] = spec_lane_src<AB, K>(lane, src, params, given, plan_dtab).entry;
+    spec_write_table<AB, K + 1>(table, lane, src, params, given, plan_dtab);
+  }
+}
+// The first requests of a workgroup (wave 0): the (A, B) of its first two instances into the ring's two
+// slots, chunk by chunk ...
+template <int K>
+__device__ __forceinline__ void spec_first_ab(int lane, long inst0, long inst1, bool two, unsigned ab_lds,
+                                              const SrcTable& src, const double* params, const double* given,
+                                              const double* plan_dtab) {
+  using PC = spec::PlanConst;
+  if constexpr (K < PC::rs_ab / 32) {
+    // ((A, B) never come out of `given`: no index to look up)
+    const LaneSrc m = spec_lane_src<true, K>(lane, src, params, given, plan_dtab);
+    dma4(m.base + inst0 * m.stride, ab_lds + (unsigned)(K * 32 * 8));
+    if (two) dma4(m.base + inst1 * m.stride, ab_lds + (unsigned)((PC::rs_ab + K * 32) * 8));
+    spec_first_ab<K + 1>(lane, inst0, inst1, two, ab_lds, src, params, given, plan_dtab);
+  }
+}
+// ... and the chunks of its first image that have their runs
+template <int K>
+__device__ __forceinline__ void spec_first_image(int lane, long inst, long ginst, unsigned img_lds, const SrcTable& src,
+                                                 const double* params, const double* given, const double* plan_dtab) {
+  using PC = spec::PlanConst;
+  if constexpr (K < PC::rs_nchunk && K < 32) {
+    if constexpr (spec_fetch_runs<false, K>() != 0) {
+      const LaneSrc m = spec_lane_src<false, K>(lane, src, params, given, plan_dtab);
+      const char* a = m.base + (m.isg ? ginst : inst) * m.stride;
+      if constexpr (PC::rs_unit == 16)
+        dma16(a, img_lds + (unsigned)(K * 64 * 16));
+      else
+        dma4(a, img_lds + (unsigned)(K * 64 * 4));
+    }
+    spec_first_image<K + 1>(lane, inst, ginst, img_lds, src, params, given, plan_dtab);
+  }
+}
+constexpr bool spec_ab_by_runs() {  // every chunk of the (A, B) slot has its runs
+  for (int k = 0; k < spec::PlanConst::rs_ab / 32; ++k)
+    if (spec::FSEG_AB_N[k] == 0) return false;
+  return true;
+}
+
 template <int I, int N>
 __device__ __forceinline__ void spec_trips(TripState& s) {
   if constexpr (I < N) {
@@ -393,17 +508,15 @@ __device__ __forceinline__ void resident_body(
   auto generate_sources = [&](int buf, int slot) {  // one wavefront
     double* im = lds + L.img + buf * p.rs_img;
     const double* ab = lds + L.ab + slot * p.rs_ab;
-    for (int g = 0; g < p.rs_nlti; ++g) {
-      // (the record comes out of LDS: the same for every lane, and said so -- sizes and offsets the
-      // compiler takes for per-lane values turn every loop below into a masked one)
-      const int* rec = lti + g * RS_LTI_WORDS;
-      const int n = __builtin_amdgcn_readfirstlane(rec[LT_N]), m = __builtin_amdgcn_readfirstlane(rec[LT_M]);
-      const int N = __builtin_amdgcn_readfirstlane(rec[LT_HORIZON]), nn = n * n, nm = n * m;
-      const double* Am = ab + __builtin_amdgcn_readfirstlane(rec[LT_A]);
-      const double* Bm = ab + __builtin_amdgcn_readfirstlane(rec[LT_B]);
-      double* TA = im + __builtin_amdgcn_readfirstlane(rec[LT_TA]);
-      double* TB = im + __builtin_amdgcn_readfirstlane(rec[LT_TB]);
-      double* TP = im + __builtin_amdgcn_readfirstlane(rec[LT_TP]);
+    // one system; `word(k)`: word k of its record (plan_tables.h LT_*)
+    auto generate = [&](auto word) __attribute__((always_inline)) {
+      const int n = word(LT_N), m = word(LT_M);
+      const int N = word(LT_HORIZON), nn = n * n, nm = n * m;
+      const double* Am = ab + word(LT_A);
+      const double* Bm = ab + word(LT_B);
+      double* TA = im + word(LT_TA);
+      double* TB = im + word(LT_TB);
+      double* TP = im + word(LT_TP);
       if (n <= 4 && n + m <= 4) {
         // Small systems: the recurrence X_d = A X_{d-1}, X_0 = [B | A] (tools.py:21-30) in
         // registers.  Lane 4 c + i of a group of 16 holds element i of column c, so the n
@@ -413,7 +526,14 @@ __device__ __forceinline__ void resident_body(
         // reference's way (three steps; the A part of X_3 is A^4), then the four groups of
         // 16 lanes advance X_r, r = 0..3, by A^4 per step, side by side -- six dependent
         // steps instead of fifteen for N = 16 (a few ulp from the reference's rounding).
-        const int grp = lane >> 4, gi = lane & 3, gc = (lane >> 2) & 3;
+        // (from an opaque copy of the lane index: with the sizes constant, everything below that depends
+        // on the lane alone -- masks, offsets into the tables -- is the same for every instance, and hoisted
+        // out of the instance loop it would sit in registers for the whole launch)
+        int lane_ = lane;
+#ifdef MPCASM_SPEC
+        asm volatile("" : "+v"(lane_));
+#endif
+        const int grp = lane_ >> 4, gi = lane_ & 3, gc = (lane_ >> 2) & 3;
         const bool live = gi < n && gc < n + m;
         double ar[4];
 #pragma unroll
@@ -444,7 +564,7 @@ __device__ __forceinline__ void resident_body(
             if (live && d < N) out[d * step] = x;
           }
         }
-        continue;
+        return;
       }
       for (int e = lane; e < nn; e += 64) {
         const double v = Am[e];
@@ -484,7 +604,22 @@ __device__ __forceinline__ void resident_body(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         have += cnt;
       }
+    };
+#ifdef MPCASM_SPEC
+    // compiled for one plan the records are constants (spec::LTI): the sizes fold, the loops unroll, no
+    // record is read -- the same operations in the same order
+    if constexpr (PlanT::rs_nlti > 0) generate([](int k) { return spec::LTI[0][k]; });
+    if constexpr (PlanT::rs_nlti > 1) generate([](int k) { return spec::LTI[1][k]; });
+    if constexpr (PlanT::rs_nlti > 2) generate([](int k) { return spec::LTI[2][k]; });
+    if constexpr (PlanT::rs_nlti > 3) generate([](int k) { return spec::LTI[3][k]; });
+#else
+    for (int g = 0; g < p.rs_nlti; ++g) {
+      // (the record comes out of LDS: the same for every lane, and said so -- sizes and offsets the
+      // compiler takes for per-lane values turn every loop below into a masked one)
+      const int* rec = lti + g * RS_LTI_WORDS;
+      generate([&](int k) { return __builtin_amdgcn_readfirstlane(rec[k]); });
     }
+#endif
   };
   // The n-th instance of this workgroup.  Large batches go round the workgroups in runs of four
   // consecutive instances: an instance's q and h are not whole 128-byte lines, and a line that
@@ -630,26 +765,70 @@ __device__ __forceinline__ void resident_body(
   };
   if (wave == 0) {
     constexpr int MK = 2;  // load-table words per lane in the first batch
-    const int nab2 = p.rs_ab * 2, nmeta = nchunk * 64, nltw = p.rs_nlti * RS_LTI_WORDS;
+#ifdef MPCASM_SPEC
+    constexpr int nltw = 0;  // (the records of the generated systems are constants of the build)
+#else
+    const int nltw = p.rs_nlti * RS_LTI_WORDS;
+#endif
+    const int nab2 = p.rs_ab * 2, nmeta = nchunk * 64;
     const int2* t_ab = reinterpret_cast<const int2*>(plan_itab + p.off_rs_abmeta);
     const int2* t_meta = reinterpret_cast<const int2*>(plan_itab + p.off_rs_inmeta);
     const int32_t* t_lti = plan_itab + p.off_rs_lti;
     int2 v_ab = int2{0, 0}, v_meta[MK];
     int v_lti = 0;
-    if (lane < nab2) v_ab = t_ab[lane];
+    // Compiled for one plan, the chunks of the fetch tables that are a few runs of streams (jit.hip
+    // jit_fetch_segments) are fetched by arithmetic on the lane index, and wave 0's FIRST memory
+    // instructions are the requests the first instance waits for: the first two instances' (A, B), then
+    // the first image.  The tables these requests used to be read from cost a trip to memory and back
+    // before the first byte of input could be asked for.  Their LDS copies, which the loop's fetches
+    // still read, are written behind the requests -- from the runs again where every chunk of a table
+    // has them: then the table is not loaded at all.
+#ifdef MPCASM_SPEC
+    constexpr bool ab_runs = spec_ab_by_runs();
+    constexpr unsigned on_table = spec::FSEG_IMG_TABLE;
+    constexpr bool img_runs = on_table == 0 && PlanT::rs_nchunk <= 32;  // every chunk of the image has its runs
+    // the image's requests behind the (A, B)'s when those come off the table: what the wait for (A, B) leaves out
+    constexpr int img_late = __builtin_popcount(on_table) + (PlanT::rs_nchunk > 32 ? PlanT::rs_nchunk - 32 : 0);
+    const int ab_later = ab_runs ? nchunk : img_late;
+    if (gen && ab_runs) {
+      const long i1 = instance_at(1);
+      spec_first_ab<0>(lane, instance_at(0), i1, i1 < batch, __builtin_amdgcn_readfirstlane(ab_lds), src, params,
+                       given, plan_dtab);
+    }
+    if (ab_runs) SETUP_STAMP(2)
+    {
+      const long inst = instance_at(0), ginst = gix != nullptr ? (long)gix[inst] : inst;
+      spec_first_image<0>(lane, inst, ginst, __builtin_amdgcn_readfirstlane(img_lds), src, params, given, plan_dtab);
+    }
+#else
+    constexpr bool ab_runs = false, img_runs = false;
+    constexpr unsigned on_table = ~0u;
+    const int ab_later = nchunk;
+#endif
+    if (!ab_runs && lane < nab2) v_ab = t_ab[lane];
     if (lane < nltw) v_lti = t_lti[lane];
+    if (!img_runs) {
 #pragma unroll
-    for (int k = 0; k < MK; ++k) v_meta[k] = lane + k * 64 < nmeta ? t_meta[lane + k * 64] : int2{0, 0};
+      for (int k = 0; k < MK; ++k) v_meta[k] = lane + k * 64 < nmeta ? t_meta[lane + k * 64] : int2{0, 0};
+    }
     // (its share of the program behind them: the wait for the tables leaves exactly these loads out)
     if (prog_early) load_program();
-    if (lane < nab2) abmeta[lane] = v_ab;
-    for (int i = lane + 64; i < nab2; i += 64) abmeta[i] = t_ab[i];
+    if (!ab_runs) {
+      if (lane < nab2) abmeta[lane] = v_ab;
+      for (int i = lane + 64; i < nab2; i += 64) abmeta[i] = t_ab[i];
+    }
     if (lane < nltw) lti[lane] = v_lti;
     for (int i = lane + 64; i < nltw; i += 64) lti[i] = t_lti[i];
+    if (!img_runs) {
 #pragma unroll
-    for (int k = 0; k < MK; ++k)
-      if (lane + k * 64 < nmeta) meta[lane + k * 64] = v_meta[k];
-    for (int i = lane + MK * 64; i < nmeta; i += 64) meta[i] = t_meta[i];
+      for (int k = 0; k < MK; ++k)
+        if (lane + k * 64 < nmeta) meta[lane + k * 64] = v_meta[k];
+      for (int i = lane + MK * 64; i < nmeta; i += 64) meta[i] = t_meta[i];
+    }
+#ifdef MPCASM_SPEC
+    if constexpr (ab_runs) spec_write_table<true, 0>(abmeta, lane, src, params, given, plan_dtab);
+    if constexpr (img_runs) spec_write_table<false, 0>(meta, lane, src, params, given, plan_dtab);
+#endif
     // input streams: the sources, then given, params, the plan's constants
     // (wave-uniform index into the kernel's arguments: scalar loads out of the argument segment, which
     // the scalar cache already holds -- indexed by the lane, the table would be fetched by vector
@@ -665,19 +844,20 @@ __device__ __forceinline__ void resident_body(
         reinterpret_cast<long long*>(strm)[2 * t + 1] = stride * (long long)sizeof(double);
       }
     }
-    // The first two instances' (A, B) and the WHOLE first image start their trip here, before the
-    // barrier: wave 0 reads only what it wrote itself (LDS operations of one wavefront complete in
-    // order), and the CU serves its loads in the order of their issue -- asked for behind the barrier,
-    // these few loads from HBM, which the first instance waits for, queue up behind the 50 KB of
-    // program and tables that the other waves of the CU ask for at the same moment.
-    if (gen) {
+    // What is fetched through the tables.  The first two instances' (A, B) and the WHOLE first image start
+    // their trip before the barrier: wave 0 reads only what it wrote itself (LDS operations of one
+    // wavefront complete in order), and the CU serves its loads in the order of their issue -- asked for
+    // behind the barrier, these few loads from HBM, which the first instance waits for, queue up behind
+    // the 50 KB of program and tables that the other waves of the CU ask for at the same moment.
+    if (gen && !ab_runs) {
       fetch_ab(instance_at(0), 0);
       if (instance_at(1) < batch) fetch_ab(instance_at(1), 1);
     }
-    SETUP_STAMP(2)
-    {
+    if (!ab_runs) SETUP_STAMP(2)
+    if (!img_runs) {
       const long inst = instance_at(0), ginst = gix != nullptr ? (long)gix[inst] : inst;
       for (int k = 0; k < nchunk; ++k) {
+        if (k < 32 && !((on_table >> k) & 1)) continue;  // (asked for above)
         const int2 m = meta[k * 64 + lane];
         const char* base = reinterpret_cast<const char* const*>(strm)[2 * m.x];
         const long long stride = reinterpret_cast<const long long*>(strm)[2 * m.x + 1];
@@ -695,9 +875,14 @@ __device__ __forceinline__ void resident_body(
     prepare_fetch();
     SETUP_STAMP(3)
     if (gen) {
-      // the first instance's tables, as soon as its (A, B) are there: they were asked for before the
-      // image, so the wait leaves out the image's loads
-      dma_wait_but(nchunk);
+      // the first instance's tables, as soon as its (A, B) are there: they were asked for first, and the
+      // wait leaves out the last `ab_later` loads behind them.  That is a lower bound of what this wave has
+      // issued since (dma_wait_but: too small a number only waits longer) -- the table path's image loads
+      // exactly; in the per-plan kernel, where the (A, B) go first of all, the image's loads AND the table
+      // and program loads the compiler issued behind them, so this wait also covers the image and all but
+      // the last few program loads.  The exact count (the image's loads plus the program's) would rest on
+      // how many load instructions the compiler makes of load_program(): not relied on, not measured.
+      dma_wait_but(ab_later);
       SETUP_STAMP(4)
       generate_sources(0, 0);
     }

@@ -18,6 +18,7 @@ OPT_PHASE_MASK = 2
 OPT_RESIDENT_PER_CU = 3
 OPT_RESIDENT_GRID = 6
 OPT_P_DIRECT = 5     # the persistent kernel writes P 1: straight to HBM, 2: through LDS when it fits, 0: by the launch's size (read at plan creation)
+OPT_JIT_FETCH_RUNS = 7  # test aid: chunks of the fetch tables with more runs stay on the table path (0 .. 8)
 OPT_JIT = 4            # 0: specialise the persistent kernel for batches >= 512, 1: always, 2: never
 PHASE_DEFAULT = 0xBF   # every phase on, cycle stamps (bit 6) off
 PHASE_STAMPS = 0x40
@@ -64,6 +65,8 @@ SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_jit_check": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
                                         ctypes.c_char_p, ctypes.c_size_t]),
+    "mpcasm_fetch_segments": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, ctypes.c_int,
+                                             _void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),

@@ -61,7 +61,11 @@ RS_TRIP_WORDS = 8
 # cost model of the wavefront assignment (rounded cycles of one wavefront), see _resident_program
 TRIP_COST, TRIP_STEP_COST, TERM_COST, TRIP_Q_COST, PACK_COST, G_PIECE_COST = 200, 30, 60, 60, 250, 500
 G_DESC_PIECE_COST = 330     # ... a piece of G by the descriptor table (small problems; stamps: 1 950 cycles for six)
-TABLES_COST, STREAM_WAVE_COST, FETCH_CHUNK_COST = 3300, 500, 350   # horizon tables on chip; h and the rest of a stream wave
+# horizon tables on chip (stamps: the last matrix wave's trips phase fell by 1 100 cycles when the
+# per-plan kernel got the systems' sizes as constants); h and the rest of a stream wave; a chunk of the fetch
+# (systems of the general branch, n > 4 or n + m > 4, build their tables as before: TABLES_COST_GENERAL)
+TABLES_COST, STREAM_WAVE_COST, FETCH_CHUNK_COST = 2200, 500, 350
+TABLES_COST_GENERAL = 3300
 import os as _os
 if _os.environ.get("MPCASM_TRIP_COSTS"):          # tuning aid: "trip,step,term,q,pack,piece[,tables,stream,chunk]"
     _c = [int(x) for x in _os.environ["MPCASM_TRIP_COSTS"].split(",")]
@@ -69,6 +73,7 @@ if _os.environ.get("MPCASM_TRIP_COSTS"):          # tuning aid: "trip,step,term,
     G_DESC_PIECE_COST = G_PIECE_COST
     if len(_c) > 6:
         TABLES_COST, STREAM_WAVE_COST, FETCH_CHUNK_COST = _c[6:9]
+        TABLES_COST_GENERAL = TABLES_COST
 # trip record (csrc/plan_tables.h RT_*): words A, B, D, W, AIM, WORD, BI, BJ;
 # WORD = rows (16 or 4) | short << 5 | half << 6 | nop << 7 | first << 8 | last << 9 | live << 10
 #        | qmask << 14 | last trip of its term in the pack << 18
@@ -990,7 +995,8 @@ def _resident_program(fused, gterms, no, ldv, ws, image, ng, nparams, nc_rows):
     loads = []
     for w in range(RS_WAVES):
         if w < NW:
-            gen = TABLES_COST if image["groups"] and w == NW - 1 else 0   # builds the horizon tables
+            small = all(g["n"] <= 4 and g["n"] + g["m"] <= 4 for g in image["groups"])
+            gen = (TABLES_COST if small else TABLES_COST_GENERAL) if image["groups"] and w == NW - 1 else 0   # builds the horizon tables
             loads.append((FETCH_CHUNK_COST * len(range(w, image["nchunk"], NW)) + gen, w))
         else:                                      # threads of this wave own pieces e = wt + u WT
             first = (w - NW) * 64

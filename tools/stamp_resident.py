@@ -62,8 +62,14 @@ def setup_stamps(raw, grid):
     names = ["inputs asked", "barrier", "fetch ready", "tables copied", "(A,B) landed", "tables built",
              "barrier", "loop"]
     # every wavefront: the barriers wait for the last one, and the waves differ in what they load
+    # (wave 0, the fetch wave: station 2 is taken when it has asked for the first (A, B), station 0 when the
+    # whole first image is asked for and the LDS copies of the fetch tables are written, station 3 when its
+    # share of the image's addresses is in registers)
+    names0 = ["inputs asked", "barrier", "(A,B) asked", "fetch ready", "(A,B) landed", "tables built", "barrier", "loop"]
     for w in range(8):
-        print("set-up, wave %d: " % w + "  ".join("%s %6.0f" % (n, v) for n, v in zip(names, s[:, w, :].mean(axis=0))))
+        # (a station no workgroup stamped is left out)
+        print("set-up, wave %d: " % w + "  ".join("%s %6.0f" % (n, v)
+                                                  for n, v in zip(names if w else names0, s[:, w, :].mean(axis=0)) if v > 0))
     # ... and how far the workgroups of one launch are apart at the loop's start
     loop = s[:, :, 7].max(axis=1)
     print("set-up, loop start over the workgroups (last wave of each): min %6.0f  median %6.0f  max %6.0f"
