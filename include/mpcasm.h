@@ -304,6 +304,23 @@ int mpcasm_preview_goal_distance(const mpcasm_plan* plan, const double* const* h
                                  int nterms, int ngoals, double* d_out, void* d_work, int batch,
                                  void* stream);
 
+/* Diagnostic, needs no device: which kernel mpcasm_preview_direct (ngoals == 0) or
+ * mpcasm_preview_goal_distance (its nterms, ngoals) launches for these tables -- validated as
+ * mpcasm_plan_create does -- when the sources have the strides h_src_stride (as for mpcasm_assemble:
+ * 0 for a source the batch shares; may be NULL when the plan has no source).  The launches take the same
+ * decision from the same function, MPCASM_PREVIEW_NO_BLOCKS included.  out[0]: MPCASM_PREVIEW_*;
+ * out[1..4]: the template arguments E1, R1, E2, R2 of the kernel's instantiation (entries per base row,
+ * base rows per thread, entries per definition row, definition rows per thread; 0 on the direct
+ * kernel); out[5]: 1 when the kernel writes the goal distances itself; out[6]: dynamic LDS bytes of a
+ * workgroup; out[7]: 1 when that is more than 64 KB (the whole-LDS attribute is set before the launch).
+ * MPCASM_ERR_LIMIT exactly where the launch would return it (out is zeroed): for the distances, the
+ * caller then takes the rows and mpcasm_goal_distance. */
+enum { MPCASM_PREVIEW_NONE = 0 /* no rows: nothing is launched */, MPCASM_PREVIEW_DIRECT = 1,
+       MPCASM_PREVIEW_STAGED = 2 /* the plan's tables in registers, the streams in LDS */,
+       MPCASM_PREVIEW_BLOCKED = 3 /* ... every stream shared by the batch: four instances at a time */ };
+int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                         const int64_t* h_src_stride, int nterms, int ngoals, int32_t out[8]);
+
 /* f3  sparse hand-off -----------------------------------------------------------
  * Replaces the dense -> CSC conversion in front of the solver call of the walking loop
  *   Q = scipy.sparse.csc_matrix(Q); A = scipy.sparse.csc_matrix(A)

@@ -1491,6 +1491,28 @@ int mpcasm_preview_direct(const mpcasm_plan* plan, const double* const* h_src,
   return rc;
 }
 
+int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                         const int64_t* h_src_stride, int nterms, int ngoals, int32_t out[8]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out || nterms < 0 || ngoals < 0) return MPCASM_ERR_ARG;
+  memset(out, 0, 8 * sizeof(int32_t));
+  const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
+  if (rc != MPCASM_OK) return rc;
+  PlanDev d;
+  memset(&d, 0, sizeof d);
+  plan_dev_from_tables(h_itab, &d);
+  if (d.nsrc && !h_src_stride) return MPCASM_ERR_ARG;
+  if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (as mpcasm_preview_direct)
+  SrcTable src, eff;
+  memset(&src, 0, sizeof src);
+  for (int s = 0; s < d.nsrc; ++s) {
+    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
+    src.stride[s] = h_src_stride[s];
+  }
+  const int lti = lti_effective_sources(d, src, nullptr, h_itab, &eff);
+  if (lti != MPCASM_OK) return lti;
+  return preview_route(d, eff, h_itab, nterms, ngoals, out);
+}
+
 int mpcasm_given_map_compile(const mpcasm_plan* plan, const int32_t* h_rows, const double* h_values, int ng,
                              int32_t* h_map, int64_t capacity, int64_t* words) {
   if (!plan || !h_rows || !words || capacity < 0) return MPCASM_ERR_ARG;

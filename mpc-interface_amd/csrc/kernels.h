@@ -37,6 +37,9 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
                           const int32_t* h_itab);
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* work, int batch,
                       const int32_t* h_itab, SrcTable* eff, hipStream_t stream);
+// (host only: the streams a launch reads once launch_lti_tables has run -- the strides alone with work == nullptr)
+int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* work, const int32_t* h_itab,
+                          SrcTable* eff);
 // sweep.hip: a dynamics compiled as ltv -- per-step, per-instance (A_k, B_k), no horizon matrix
 bool sweep_eligible(const PlanDev& p);
 int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* params,
@@ -50,6 +53,9 @@ int launch_preview_goals(const PlanDev& p, const SrcTable& eff, const double* gi
                          const double* params, long long nparams, const int32_t* terms, int nterms,
                          int ngoals, double* out, int batch, int num_cus, hipStream_t stream,
                          hipError_t* err, const int32_t* h_itab);
+// host only: the kernel the two launches above pick (mpcasm_preview_route; ngoals == 0: the rows)
+int preview_route(const PlanDev& p, const SrcTable& eff, const int32_t* h_itab, int nterms, int ngoals,
+                  int32_t out[8]);
 // the next tick's `given` (mpcasm_next_given): the map's rows / constants into the instances' rows
 int launch_next_given(const PlanDev& p, const SrcTable& eff, const int32_t* map, long long map_words,
                       double* given, long long rows, const double* optim, const int32_t* index,

@@ -1750,11 +1750,14 @@ size_t tiled_workspace_bytes(const PlanDev& p, int batch) {
 // The horizon tables of the plan's generated groups, from the (A, B) in the slots of each group's
 // first two sources, into the scratch (t_work doubles per instance); `eff`: the launch's sources
 // with those tables in the places of the groups' U_j and S -- what the column tables address.
-int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* w, int batch,
-                      const int32_t* h_itab, SrcTable* eff, hipStream_t stream) {
+// where a launch reads every stream from: the caller's sources, and for the groups of a plan compiled
+// with lti=[...] the horizon tables in the workspace `w` (one set per instance).  Host only: nothing is
+// launched, and with w == nullptr only the strides mean anything (mpcasm_preview_route).
+int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* w, const int32_t* h_itab,
+                          SrcTable* eff) {
   *eff = src;
   if (p.t_nlti == 0) return MPCASM_OK;
-  if (h_itab == nullptr || w == nullptr) return MPCASM_ERR_ARG;
+  if (h_itab == nullptr) return MPCASM_ERR_ARG;
   const long long stride = p.t_work;
   for (int g = 0; g < p.t_nlti; ++g) {
     const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
@@ -1762,11 +1765,24 @@ int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* w, int batc
     if (n * (m + n) > LTI_XMAX || n > 64) return MPCASM_ERR_LIMIT;
     const int32_t* ids = h_itab + p.off_t_lti_ids + rec[TL_IDS];
     for (int j = 0; j < m; ++j) {
-      eff->ptr[ids[j]] = w + rec[TL_TB];
+      eff->ptr[ids[j]] = w ? w + rec[TL_TB] : nullptr;
       eff->stride[ids[j]] = stride;
     }
-    eff->ptr[ids[m]] = w + rec[TL_TA];
+    eff->ptr[ids[m]] = w ? w + rec[TL_TA] : nullptr;
     eff->stride[ids[m]] = stride;
+  }
+  return MPCASM_OK;
+}
+
+int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* w, int batch,
+                      const int32_t* h_itab, SrcTable* eff, hipStream_t stream) {
+  *eff = src;
+  if (p.t_nlti == 0) return MPCASM_OK;
+  if (h_itab == nullptr || w == nullptr) return MPCASM_ERR_ARG;
+  const long long stride = p.t_work;
+  {
+    const int rc = lti_effective_sources(p, src, w, h_itab, eff);
+    if (rc != MPCASM_OK) return rc;
   }
   size_t lds = 0, small = 0;
   bool all_small = true;

@@ -67,6 +67,9 @@ SIGNATURES = {
                                         ctypes.c_char_p, ctypes.c_size_t]),
     "mpcasm_fetch_segments": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, ctypes.c_int,
                                              _void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_preview_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
+                                            ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),
@@ -129,6 +132,8 @@ KERNEL_NAMES = {0: "none", 1: "resident_assemble_kernel (persistent, ahead of ti
                 6: "toeplitz_scan_kernel (tiled, scan form: P summed along diagonals)",
                 7: "ltv_sweep_kernel (per-step dynamics, no horizon matrix)",
                 8: "shared_p_kernel / shared_g_kernel (tiled, shared-model form: weighted sums of per-term matrices)"}
+PREVIEW_NONE, PREVIEW_DIRECT, PREVIEW_STAGED, PREVIEW_BLOCKED = range(4)   # out[0] of mpcasm_preview_route
+PREVIEW_ROUTES = {0: "none", 1: "direct", 2: "staged", 3: "blocked"}
 BOX_RECENTER, BOX_TRANSLATE, BOX_ROTATE, BOX_SCALE, BOX_MARGIN = range(5)
 
 

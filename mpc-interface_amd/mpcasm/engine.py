@@ -330,6 +330,25 @@ def resident_lds_bytes(plan):
     return int(out[0]), int(out[1])
 
 
+def preview_route(plan, src_stride=None, nterms=0, ngoals=0):
+    """The kernel ``mpcasm_preview_direct`` (``ngoals == 0``) or ``mpcasm_preview_goal_distance`` (a goal
+    table of ``nterms`` records for ``ngoals`` goals) launches for ``plan`` when its sources have the strides
+    ``src_stride`` (default: every source shared by the batch) -- ``mpcasm_preview_route``, no device needed:
+    ``(route, E1, R1, E2, R2, DIST, LDS bytes, whole LDS)`` with ``route`` one of ``capi.PREVIEW_*``, or
+    ``None`` where the launch returns ``MPCASM_ERR_LIMIT``."""
+    out = (ctypes.c_int32 * 8)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    n = len(plan.sources)
+    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
+    rc = capi.load().mpcasm_preview_route(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides,
+        int(nterms), int(ngoals), out)
+    if rc == capi.ERR_LIMIT:
+        return None
+    capi.check(rc, "mpcasm_preview_route")
+    return tuple(int(x) for x in out)
+
+
 STREAMING_LAUNCH_BYTES = 560e6    # results per launch from which P is collected in LDS (resident.hip)
 
 
@@ -792,6 +811,16 @@ class Assembler:
                 _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_preview_direct")
         return out
+
+    def preview_route(self, goals=False):
+        """What :meth:`preview_rows` -- with ``goals`` (the Formulation whose goals :meth:`goal_terms` lists)
+        the fused kernel of :meth:`full_goal_distances` -- launches with the sources bound now
+        (:func:`preview_route`); ``None``: no kernel fuses the distances, :meth:`full_goal_distances` falls back."""
+        nterms = ngoals = 0
+        if goals is not False and goals is not None:
+            table, names = self.goal_terms(goals)
+            nterms, ngoals = int(table.shape[0]), len(names)
+        return preview_route(self.plan, self._src_stride, nterms, ngoals)
 
     def given_map(self, rules):
         """The device table of a given map for this assembler's plan (``mpcasm_given_map_compile``; rules as

@@ -288,25 +288,30 @@ def test_sweep_per_step_growing_plant(gpu_api, torch_gpu):
 
 
 # ---------------------------------------------------------------------------------------------------
-# Preview rows (mpcasm_preview_direct) on generated tables.
+# Preview rows (mpcasm_preview_direct) on generated tables: three shapes on the direct kernel (n + m N > 32) and
+# one on the staged kernel; every instantiation of the two fast kernels: test_gpu_preview_variants.py.
 # ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nx,nu,N,rho,B", [(5, 3, 48, 1.3, 300), (12, 6, 64, 1.25, 24), (4, 2, 100, 1.3, 300)],
-                         ids=["5-3-48", "c4-shape", "4-2-100"])
-def test_preview_rows(gpu_api, torch_gpu, nx, nu, N, rho, B):
+@pytest.mark.parametrize("nx,nu,N,rho,B,route",
+                         [(5, 3, 48, 1.3, 300, "direct"), (12, 6, 64, 1.25, 24, "direct"), (4, 2, 100, 1.3, 300, "direct"),
+                          (4, 2, 14, 1.3, 300, "staged")],
+                         ids=["5-3-48", "c4-shape", "4-2-100", "staged-4-2-14"])
+def test_preview_rows(gpu_api, torch_gpu, nx, nu, N, rho, B, route):
     torch = torch_gpu
-    from mpcasm import engine
+    from mpcasm import capi, engine
+    from preview_cases import generated_rows_reference
 
     rng = np.random.default_rng(nx + N)
     A, Bm = cancellation_free_plants(rng, B, nx, nu, rho, N)
     form = problems.random_lti(gpu_api, rng, nx=nx, nu=nu, N=N)
     asm = engine.Assembler(form, batch=B, lti=["plant"])
     asm.bind_lti("plant", torch.as_tensor(A, device="cuda"), torch.as_tensor(Bm, device="cuda"))
+    assert capi.PREVIEW_ROUTES[asm.preview_route()[0]] == route, asm.preview_route()
     given = rng.normal(0, 0.3, [B, form.given_len])
     optim = rng.normal(0, 0.5, [B, form.optim_len])
     out = torch.full((B, asm.plan.pmrows), float("nan"), dtype=torch.float64, device="cuda")
     rows = asm.preview_rows(given, optim, out=out).cpu().numpy()
     kap, worst = kappa(N, nx), 0.0
     for b in _samples(B, few=nx == 12):
-        ref = precise_reference(form, "plant", A[b], Bm[b], given[b], optim=optim[b], pm_rows=asm.plan.pm_rows)
+        ref = {"rows": generated_rows_reference(form, "plant", A[b], Bm[b], given[b], optim[b], asm.plan)}
         worst = max(worst, _check({"rows": rows}, b, ref, kap, "preview rows"))
     _report("preview rows (%d, %d, %d)" % (nx, nu, N), worst, kap)
