@@ -4,6 +4,7 @@ iteration) iterate by iterate, and against the KKT conditions of the QPs at the 
 import numpy as np
 import pytest
 
+import solver_reference as sr
 from helpers import assert_close
 from mpcasm import problems
 from oracle import admm_oracle as ao
@@ -113,6 +114,8 @@ def test_the_inverse_kept_from_one_call_to_the_next(gpu_api, torch_gpu):
     assert not bool(torch.isnan(kinv).any())
     Kref = np.linalg.inv(P[3].cpu().numpy() + 1e-6 * np.eye(no) + G[3].cpu().numpy().T @ G[3].cpu().numpy())
     assert_close(kinv[3].cpu().numpy(), Kref, 1e-9, "K^-1")
+    # (and within the forward bound no u kappa2 |X*|_2 of the long-double inverse: 1e-12 of its size here)
+    sr.assert_inverse(kinv[3].cpu().numpy(), P[3].cpu().numpy(), G[3].cpu().numpy(), 1.0, 1e-6)
     q2, h2 = to_dev(torch, rng.standard_normal((B, no)), rng.uniform(0.1, 1.0, (B, nc)))
     fresh = engine.admm(P, q2, G, h2, iters=30, rho=1.0)
     garbage = torch.full_like(P, float("nan"))                 # (not read with a valid inverse and no residuals)

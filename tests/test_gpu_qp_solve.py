@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import osqp_restatement as rs
+import solver_reference as sr
 from helpers import assert_close
 from mpcasm import problems
 from oracle import admm_oracle as ao
@@ -151,6 +152,8 @@ def test_adaptive_rho_and_the_inverse_it_leaves(gpu_api, torch_gpu):
         r = float(sol.rho[b])
         Kref = np.linalg.inv(Pn[b] + engine.OSQP_SIGMA * np.eye(Pn.shape[1]) + r * Gn[b].T @ Gn[b])
         assert_close(kinv[b].cpu().numpy(), Kref, 1e-9, "K^-1 for the final rho")
+        # (and within the forward bound no u kappa2 |X*|_2 of the long-double inverse, whatever rho came out)
+        sr.assert_inverse(kinv[b].cpu().numpy(), Pn[b], Gn[b], r, engine.OSQP_SIGMA, "K^-1 for the final rho")
 
 
 def test_a_fleet_from_the_assembly_to_solutions(gpu_api, torch_gpu):

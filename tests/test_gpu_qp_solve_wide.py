@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import osqp_restatement as rs
+import solver_reference as sr
 from helpers import assert_close
 from mpcasm import problems
 from oracle import admm_oracle as ao
@@ -197,6 +198,8 @@ def test_kinv_on_and_off_chip(gpu_api, torch_gpu, monkeypatch, home):
     r = float(sol.rho[0])
     Kref = np.linalg.inv(Pn + engine.OSQP_SIGMA * np.eye(96) + r * Gn.T @ Gn)
     assert_close(kinv[0].cpu().numpy(), Kref, 1e-9, "K^-1 for the final rho")
+    # (and within the forward bound no u kappa2 |X*|_2 of the long-double inverse, whatever rho came out)
+    sr.assert_inverse(kinv[0].cpu().numpy(), Pn, Gn, r, engine.OSQP_SIGMA, "K^-1 for the final rho")
 
 
 @pytest.mark.parametrize("home", [None, "global"])
