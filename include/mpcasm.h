@@ -321,6 +321,19 @@ enum { MPCASM_PREVIEW_NONE = 0 /* no rows: nothing is launched */, MPCASM_PREVIE
 int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                          const int64_t* h_src_stride, int nterms, int ngoals, int32_t out[8]);
 
+/* Diagnostic, needs no device: what mpcasm_assemble launches for the tables of a plan with a dynamics compiled
+ * as ltv (the sweep kernel; tables validated as mpcasm_plan_create does).  The launch takes the decision from
+ * the same function.  out[0]: CPT, the columns a thread owns (1, 2, 4); out[1]: 1 for the instantiation with
+ * the system's sizes as constants (3 states, 1 input, 2 axes), else 0; out[2]: 1 when a thread's two columns
+ * are neighbours (PAIR); out[3]: 1 when the weights of G's lines are kept per line (a limit whose arrow
+ * changes from line to line), 0 per limit; out[4]: the regular lines, 0 .. 4 (the first lines of every step
+ * that belong to the same limits, a row further down G per step); out[5]: LR, the lines of a step fetched at
+ * once where no line is regular (8, 4, 2 by CPT); out[6]: dynamic LDS bytes of a workgroup; out[7]: 1 when
+ * that is more than 64 KB.  MPCASM_ERR_LIMIT exactly where the launch returns it (out is zeroed): more than
+ * 1024 unknowns, a system beyond 4 states / 4 inputs / 4 axes, LDS beyond a CU's.  MPCASM_ERR_ARG for a plan
+ * that does not run on the sweep kernel. */
+int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int32_t out[8]);
+
 /* f3  sparse hand-off -----------------------------------------------------------
  * Replaces the dense -> CSC conversion in front of the solver call of the walking loop
  *   Q = scipy.sparse.csc_matrix(Q); A = scipy.sparse.csc_matrix(A)

@@ -1513,6 +1513,29 @@ int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_d
   return preview_route(d, eff, h_itab, nterms, ngoals, out);
 }
 
+int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int32_t out[8]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  memset(out, 0, 8 * sizeof(int32_t));
+  const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
+  if (rc != MPCASM_OK) return rc;
+  PlanDev d;
+  memset(&d, 0, sizeof d);
+  plan_dev_from_tables(h_itab, &d);
+  if (!sweep_eligible(d)) return MPCASM_ERR_ARG;  // (no dynamics compiled as ltv: another kernel's plan)
+  SweepChoice c;
+  const int choice = sweep_choose(d, h_itab, &c);
+  if (choice != MPCASM_OK) return choice;
+  out[0] = c.cpt;
+  out[1] = c.specialised;
+  out[2] = c.pair;
+  out[3] = c.per_line;
+  out[4] = c.reg_lines;
+  out[5] = sweep_lines_ahead(c.cpt);
+  out[6] = (int32_t)c.lds;
+  out[7] = c.lds > 64 * 1024;
+  return MPCASM_OK;
+}
+
 int mpcasm_given_map_compile(const mpcasm_plan* plan, const int32_t* h_rows, const double* h_values, int ng,
                              int32_t* h_map, int64_t capacity, int64_t* words) {
   if (!plan || !h_rows || !words || capacity < 0) return MPCASM_ERR_ARG;

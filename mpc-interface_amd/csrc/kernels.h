@@ -42,6 +42,15 @@ int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* work, c
                           SrcTable* eff);
 // sweep.hip: a dynamics compiled as ltv -- per-step, per-instance (A_k, B_k), no horizon matrix
 bool sweep_eligible(const PlanDev& p);
+// host only: what launch_assemble_sweep launches for a plan (mpcasm_sweep_route) -- the instantiation
+// ltv_sweep_kernel<cpt, NS, MS, AS, pair> (specialised: NS, MS, AS = 3, 1, 2, else 0, 0, 0), how the lines of G
+// are walked (per_line, reg_lines) and the dynamic LDS of a workgroup; MPCASM_ERR_LIMIT where nothing is launched
+struct SweepChoice {
+  int cpt, specialised, pair, per_line, reg_lines;
+  size_t lds;
+};
+int sweep_choose(const PlanDev& p, const int32_t* h_itab, SweepChoice* out);
+int sweep_lines_ahead(int cpt);   // LR: the lines of a step whose words and weights are fetched at once
 int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* params,
                           const double* given, double* P, double* q, double* G, double* h, int batch,
                           hipStream_t stream, hipError_t* err, const int32_t* h_itab);

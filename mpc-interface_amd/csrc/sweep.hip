@@ -56,6 +56,8 @@ struct SweepLds {
 constexpr int LIMW = SW_LIM_WORDS + SW_AXMAX * SW_LAX_WORDS;
 constexpr int SW_TERMS_REG = 8;   // cost terms the recursion waves keep in registers
 constexpr int SW_LINES_REG = 8;   // lines of G of one step whose words are fetched a step ahead
+// ... of which a thread with CPT columns keeps LR in registers (its weights are per column)
+constexpr int sweep_lr(int cpt) { return cpt == 1 ? SW_LINES_REG : (cpt == 2 ? 4 : 2); }
 // [A_k | B_k] of a step: n n + n m doubles, rounded up to whole 16-byte pieces; the vectors the sweeps read
 // per step (Psi_l B_l[:, j], the weights of a line of G) are padded to SW_NMAX = 4 doubles: two 16-byte reads
 __host__ __device__ inline int sweep_abw(int n, int m) { return (n * n + n * m + 1) & ~1; }
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(SW_BLOCK) void ltv_sweep_kernel(
       for (int s_ = 0; s_ < SW_NMAX; ++s_) wreg[x][t][s_] = (x < reg_lines && s_ < n) ? wp[s_] : 0.0;
     }
   }
-  constexpr int LR = CPT == 1 ? SW_LINES_REG : (CPT == 2 ? 4 : 2);   // lines of a step in registers
+  constexpr int LR = sweep_lr(CPT);   // lines of a step in registers
   int wcur[LR];   // the words of the step's first lines (wave-uniform)
 #pragma unroll
   for (int x = 0; x < LR; ++x) wcur[x] = G != nullptr ? __builtin_amdgcn_readfirstlane(lword[x]) : 0;
@@ -704,10 +706,12 @@ __global__ __launch_bounds__(SW_BLOCK) void ltv_sweep_kernel(
 }  // namespace
 
 bool sweep_eligible(const PlanDev& p) { return p.sw_ok != 0; }
+int sweep_lines_ahead(int cpt) { return sweep_lr(cpt); }
 
-int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h, int batch,
-                          hipStream_t stream, hipError_t* err, const int32_t* h_itab) {
+// the one decision, taken by launch_assemble_sweep and reported by mpcasm_sweep_route: the limits, whether
+// the weights of G's lines are kept per line, the regular lines, the LDS and the instantiation
+int sweep_choose(const PlanDev& p, const int32_t* h_itab, SweepChoice* out) {
+  *out = SweepChoice{};
   const int n = p.sw_n, m = p.sw_m, naxes = p.sw_naxes;
   if (n < 1 || n > SW_NMAX || m < 1 || m > SW_MMAX || naxes < 1 || naxes > SW_AXMAX ||
       naxes * n * n > 64 || p.no > SW_BLOCK * 4)
@@ -745,12 +749,32 @@ int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* p
   }
   const size_t lds = (size_t)sweep_lds(p, per_line).total * sizeof(double);
   if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
+  const bool even = (p.no & 1) == 0 && (p.sw_horizon & 1) == 0;
+  const bool lipm = n == 3 && m == 1 && naxes == 2;
+  SweepChoice c;
+  c.per_line = per_line;
+  c.reg_lines = reg_lines;
+  c.lds = lds;
+  c.pair = even && p.no <= SW_BLOCK * 2;
+  c.cpt = c.pair ? 2 : (p.no <= SW_BLOCK ? 1 : (p.no <= SW_BLOCK * 2 ? 2 : 4));
+  c.specialised = lipm && (c.pair || c.cpt == 1);
+  *out = c;
+  return MPCASM_OK;
+}
+
+int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* params,
+                          const double* given, double* P, double* q, double* G, double* h, int batch,
+                          hipStream_t stream, hipError_t* err, const int32_t* h_itab) {
+  SweepChoice c;
+  const int rc = sweep_choose(p, h_itab, &c);
+  if (rc != MPCASM_OK) return rc;
+  const int per_line = c.per_line, reg_lines = c.reg_lines;
+  const size_t lds = c.lds;
   const double* A = src.ptr[p.sw_src_a];
   const double* Bm = src.ptr[p.sw_src_b];
   const long long sa = src.stride[p.sw_src_a], sb = src.stride[p.sw_src_b];
-#define MPCASM_SWEEP_CASE(CPT, NS, MS, AS) MPCASM_SWEEP_CASE_P(CPT, NS, MS, AS, false)
-#define MPCASM_SWEEP_CASE_P(CPT, NS, MS, AS, PAIR)                                                     \
-  if (p.no <= SW_BLOCK * CPT && (NS == 0 || (n == NS && m == MS && naxes == AS))) {                    \
+#define MPCASM_SWEEP_CASE(CPT, NS, MS, AS, PAIR)                                                       \
+  if (c.cpt == CPT && c.specialised == (NS != 0) && c.pair == (int)PAIR) {                             \
     auto kernel = ltv_sweep_kernel<CPT, NS, MS, AS, PAIR>;                                             \
     if (lds > 64 * 1024) {                                                                             \
       *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));                                   \
@@ -761,14 +785,13 @@ int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* p
     *err = hipGetLastError();                                                                          \
     return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;                                            \
   }
-  if ((p.no & 1) == 0 && (p.sw_horizon & 1) == 0) { MPCASM_SWEEP_CASE_P(2, 3, 1, 2, true) }
-  MPCASM_SWEEP_CASE(1, 3, 1, 2)
-  if ((p.no & 1) == 0 && (p.sw_horizon & 1) == 0) { MPCASM_SWEEP_CASE_P(2, 0, 0, 0, true) }
-  MPCASM_SWEEP_CASE(1, 0, 0, 0)
-  MPCASM_SWEEP_CASE(2, 0, 0, 0)
-  MPCASM_SWEEP_CASE(4, 0, 0, 0)
+  MPCASM_SWEEP_CASE(2, 3, 1, 2, true)
+  MPCASM_SWEEP_CASE(1, 3, 1, 2, false)
+  MPCASM_SWEEP_CASE(2, 0, 0, 0, true)
+  MPCASM_SWEEP_CASE(1, 0, 0, 0, false)
+  MPCASM_SWEEP_CASE(2, 0, 0, 0, false)
+  MPCASM_SWEEP_CASE(4, 0, 0, 0, false)
 #undef MPCASM_SWEEP_CASE
-#undef MPCASM_SWEEP_CASE_P
   return MPCASM_ERR_LIMIT;
 }
 

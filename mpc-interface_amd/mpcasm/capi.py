@@ -70,6 +70,8 @@ SIGNATURES = {
     "mpcasm_preview_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
                                             ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_sweep_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),

@@ -349,6 +349,19 @@ def preview_route(plan, src_stride=None, nterms=0, ngoals=0):
     return tuple(int(x) for x in out)
 
 
+def sweep_route(plan):
+    """What ``mpcasm_assemble`` launches for a plan with a dynamics compiled as ``ltv`` -- ``mpcasm_sweep_route``,
+    the launch's own decision, no device needed: ``(CPT, specialised, PAIR, per_line, reg_lines, LR, LDS bytes,
+    whole LDS)`` of ``ltv_sweep_kernel<CPT, NS, MS, AS, PAIR>`` (``specialised``: ``NS, MS, AS = 3, 1, 2``).
+    Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the plan, with
+    ``MPCASM_ERR_ARG`` for a plan that does not run on the sweep kernel."""
+    out = (ctypes.c_int32 * 8)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    capi.check(capi.load().mpcasm_sweep_route(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, out), "mpcasm_sweep_route")
+    return tuple(int(x) for x in out)
+
+
 STREAMING_LAUNCH_BYTES = 560e6    # results per launch from which P is collected in LDS (resident.hip)
 
 
@@ -821,6 +834,10 @@ class Assembler:
             table, names = self.goal_terms(goals)
             nterms, ngoals = int(table.shape[0]), len(names)
         return preview_route(self.plan, self._src_stride, nterms, ngoals)
+
+    def sweep_route(self):
+        """The instantiation of the sweep kernel :meth:`assemble` launches for this plan (:func:`sweep_route`)."""
+        return sweep_route(self.plan)
 
     def given_map(self, rules):
         """The device table of a given map for this assembler's plan (``mpcasm_given_map_compile``; rules as
