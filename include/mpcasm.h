@@ -42,7 +42,9 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 
 /* library / device ------------------------------------------------------- */
 
-/* ABI version of this header (major*1000 + minor). */
+/* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
+ * mpcasm_ltv_rollout and mpcasm_ltv_advance (the project's tests pin the value): a client cannot tell from this
+ * number whether those three entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
 /* Number of visible HIP devices (0 when none; never fails). */
 int mpcasm_device_count(void);
@@ -524,6 +526,59 @@ int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const
                       double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
                       const int32_t* d_status, uint32_t apply_mask, const int32_t* d_map, int64_t map_words,
                       void* d_work, int count, void* stream);
+
+/* f2 + the loop, per-step dynamics  the preview rows and the next `given` of a plan compiled with ltv=[...] ----
+ * Replaces, for a batch whose dynamics differ from step to step and from instance to instance
+ * (x_{k+1} = A_k x_k + B_k u_k: the plans the sweep kernel assembles),
+ *   Formulation.preview                         python/mpc_interface/body.py:209-219
+ *   preview_all + update_given_collector        biped_mpc_loop.py:62-95
+ * mpcasm_preview_direct, mpcasm_given_map_compile and mpcasm_next_given keep answering MPCASM_ERR_LIMIT for
+ * such a plan: they read horizon matrices, and it has none.  Nor does it need any: every unknown is an input of
+ * its one system, every given value an initial state, so the rows of a definition are the given values or the
+ * unknowns themselves, or c . x_{k+1} along the forward recursion, and the next given is x_1 of every axis --
+ * O(N n (n + m)) per axis, (A_k, B_k) read once from the plan's two ltv source slots (A (N, n, n), B (N, n, m)
+ * per instance; stride 0: shared), the rows written once, no workspace.
+ *
+ * The *row table* says what every row of the preview program is (the rows mpcasm_preview_direct would write:
+ * definition v at mpcasm/plan.py's pm_rows[v]).  h_recs: nrec records of MPCASM_ROLL_REC_WORDS int32, in the
+ * order of the rows, each a run of rows
+ *   kind, first row, rows, axis, k0, kstep, index of c in h_cvec, 0
+ *   MPCASM_ROLL_GIVEN   row i of the run = given[k0 + i kstep]                      (bit for bit)
+ *   MPCASM_ROLL_OPTIM   row i of the run = optim[k0 + i kstep]                      (bit for bit)
+ *   MPCASM_ROLL_STATE   row i of the run = c . x_{k0 + i kstep + 1} of the axis     (c: SW_NMAX = 4 doubles, 0 beyond n)
+ * mpcasm/plan.py rollout_rows derives them from the plan.  h_sizes: what the records were made for --
+ * states, inputs, steps, axes, rows of the preview program, ng, no.  Host only, no device call, no plan handle:
+ * the tables are validated as mpcasm_plan_create does.  *words = the number of int32 words; h_table == NULL asks
+ * for that number only, a smaller capacity is MPCASM_ERR_ARG.  The caller copies the words to the device.
+ * MPCASM_ERR_ARG: tables of a plan without a dynamics compiled as ltv, h_sizes that are not the plan's, records
+ * that do not cover every row exactly once in order, an index outside the plan's sizes, a c that is not finite;
+ * MPCASM_ERR_LIMIT: more than 4096 words of records and combinations. */
+enum { MPCASM_ROLL_GIVEN = 0, MPCASM_ROLL_OPTIM = 1, MPCASM_ROLL_STATE = 2 };
+#define MPCASM_ROLL_REC_WORDS 8
+int mpcasm_ltv_rollout_compile(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                               const int32_t h_sizes[7], const int32_t* h_recs, int nrec, const double* h_cvec,
+                               int ncvec, int32_t* h_table, int64_t capacity, int64_t* words);
+
+/* The rows (Formulation.preview, body.py:209-219, of every definition): for count instances b, from row
+ * d_index[b] of d_given (rows x ng; NULL: row b, rows >= count) and row b of d_optim (count x no), row b of d_out
+ * (count x preview rows, 8-byte aligned).  d_table / table_words: the words of mpcasm_ltv_rollout_compile for
+ * THIS plan; a table whose header does not match the plan's sizes, or that is no such table, writes nothing.
+ * h_src / h_src_stride as for mpcasm_assemble.  MPCASM_ERR_ARG for a plan without a dynamics compiled as ltv
+ * (mpcasm_preview_direct is for those); MPCASM_ERR_LIMIT when one instance does not fit in a CU's LDS. */
+int mpcasm_ltv_rollout(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                       const double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
+                       const int32_t* d_table, int64_t table_words, double* d_out, int count, void* stream);
+
+/* The next tick's given (update_given_collector, biped_mpc_loop.py:62-95): x_1 = A_0 x_0 + B_0 u_0 of every
+ * axis, written IN PLACE into row d_index[b] of d_given -- the row is read before any of it is written; only
+ * A_0, B_0 and the first sample of every input are read.  d_index, d_status, apply_mask: exactly as for
+ * mpcasm_next_given (distinct entries in [0, rows), checked by the host that builds them; an instance writes only
+ * when bit MPCASM_QP_BIT(d_status[b]) of apply_mask is set, else its row stays as it was; NULL status: all
+ * apply).  d_table and the return codes as for mpcasm_ltv_rollout. */
+int mpcasm_ltv_advance(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                       double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
+                       const int32_t* d_status, uint32_t apply_mask, const int32_t* d_table, int64_t table_words,
+                       int count, void* stream);
 
 #ifdef __cplusplus
 }

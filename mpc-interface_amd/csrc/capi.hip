@@ -1586,6 +1586,72 @@ int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const
   return rc;
 }
 
+int mpcasm_ltv_rollout_compile(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                               const int32_t h_sizes[7], const int32_t* h_recs, int nrec, const double* h_cvec,
+                               int ncvec, int32_t* h_table, int64_t capacity, int64_t* words) {
+  if (!h_itab || (n_dtab && !h_dtab) || !h_sizes || !h_recs || !words || nrec < 1 || ncvec < 0 ||
+      (ncvec && !h_cvec) || capacity < 0)
+    return MPCASM_ERR_ARG;
+  const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
+  if (rc != MPCASM_OK) return rc;
+  PlanDev d;
+  memset(&d, 0, sizeof d);
+  plan_dev_from_tables(h_itab, &d);
+  if (!d.sw_ok) return MPCASM_ERR_ARG;  // (no dynamics compiled as ltv: mpcasm_preview_direct's plan)
+  const int32_t have[7] = {d.sw_n, d.sw_m, d.sw_horizon, d.sw_naxes, d.pmrows, d.ng, d.no};
+  if (memcmp(have, h_sizes, sizeof have) != 0) return MPCASM_ERR_ARG;
+  std::vector<int32_t> table;
+  const int made = compile_rollout_table(d, h_recs, nrec, h_cvec, ncvec, &table);
+  if (made != MPCASM_OK) return made;
+  *words = (int64_t)table.size();
+  if (h_table == nullptr) return MPCASM_OK;
+  if (capacity < (int64_t)table.size()) return MPCASM_ERR_ARG;
+  memcpy(h_table, table.data(), table.size() * sizeof(int32_t));
+  return MPCASM_OK;
+}
+
+namespace {
+int rollout_impl(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride, double* d_given,
+                 int64_t rows, const double* d_optim, const int32_t* d_index, const int32_t* d_status,
+                 uint32_t apply_mask, const int32_t* d_table, int64_t table_words, double* d_out, int write_given,
+                 int count, void* stream) {
+  if (!plan || count < 0 || rows < 0 || table_words < 0) return MPCASM_ERR_ARG;
+  const PlanDev& d = plan->dev;
+  if (!d.sw_ok) return MPCASM_ERR_ARG;  // (a plan with horizon matrices: mpcasm_preview_direct / mpcasm_next_given)
+  if (count == 0 || (!write_given && d.pmrows == 0)) return MPCASM_OK;
+  if (!d_given || !d_optim || !d_table || !h_src || !h_src_stride || (!write_given && !d_out)) return MPCASM_ERR_ARG;
+  if (!d_index && rows < count) return MPCASM_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(d_out) & 7) return MPCASM_ERR_ARG;
+  {  // the plan's tables live on the device it was created on
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  }
+  SrcTable src;
+  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  hipError_t err;
+  rc = launch_ltv_rollout(d, src, d_table, table_words, d_given, rows, d_optim, d_index, d_status, apply_mask, d_out,
+                          write_given, count, static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+}  // namespace
+
+int mpcasm_ltv_rollout(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                       const double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
+                       const int32_t* d_table, int64_t table_words, double* d_out, int count, void* stream) {
+  return rollout_impl(plan, h_src, h_src_stride, const_cast<double*>(d_given), rows, d_optim, d_index, nullptr, 0u,
+                      d_table, table_words, d_out, 0, count, stream);
+}
+
+int mpcasm_ltv_advance(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                       double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
+                       const int32_t* d_status, uint32_t apply_mask, const int32_t* d_table, int64_t table_words,
+                       int count, void* stream) {
+  return rollout_impl(plan, h_src, h_src_stride, d_given, rows, d_optim, d_index, d_status, apply_mask, d_table,
+                      table_words, nullptr, 1, count, stream);
+}
+
 int mpcasm_preview_goal_distance(const mpcasm_plan* plan, const double* const* h_src,
                                  const int64_t* h_src_stride, const double* d_given,
                                  const double* d_optim, const double* d_params, const int32_t* d_terms,

@@ -72,6 +72,13 @@ int launch_next_given(const PlanDev& p, const SrcTable& eff, const int32_t* map,
                       hipError_t* err);
 int compile_given_map(const PlanDev& p, const int32_t* h_itab, const int32_t* rows, const double* values,
                       std::vector<int32_t>* out);
+// rollout.hip: the preview rows and the next given of a plan compiled as ltv, by the forward recursion
+int compile_rollout_table(const PlanDev& p, const int32_t* recs, int nrec, const double* cvec, int ncvec,
+                          std::vector<int32_t>* out);
+int launch_ltv_rollout(const PlanDev& p, const SrcTable& src, const int32_t* table, long long table_words,
+                       double* given, long long rows, const double* optim, const int32_t* index,
+                       const int32_t* status, unsigned apply_mask, double* out, int write_given, int count,
+                       hipStream_t stream, hipError_t* err);
 int launch_goal_distance(const double* preview, long long preview_stride, const double* params,
                          long long nparams, const int32_t* terms, int nterms, int ngoals,
                          double* out, int batch, hipStream_t stream, hipError_t* err);

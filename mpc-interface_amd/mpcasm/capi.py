@@ -39,6 +39,8 @@ QP_STATUS = {
     -4: "MPCASM_QP_DUAL_INFEASIBLE",
     -7: "MPCASM_QP_NON_CVX",
 }
+ROLL_GIVEN, ROLL_OPTIM, ROLL_STATE, ROLL_REC_WORDS = 0, 1, 2, 8   # records of mpcasm_ltv_rollout_compile
+ERR_ARG = -1
 GIVEN_KEEP, GIVEN_CONST = -1, -2     # given-map records of mpcasm_given_map_compile (a row: its index >= 0)
 
 
@@ -118,6 +120,15 @@ SIGNATURES = {
     "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
                                          ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_uint32, _void_p,
                                          ctypes.c_int64, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_ltv_rollout_compile": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, _void_p, _void_p,
+                                                  ctypes.c_int, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
+                                                  ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_ltv_rollout": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
+                                          ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_int64, _void_p,
+                                          ctypes.c_int, _void_p]),
+    "mpcasm_ltv_advance": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
+                                          ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_uint32, _void_p,
+                                          ctypes.c_int64, ctypes.c_int, _void_p]),
     "mpcasm_gather": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p,
                                      ctypes.c_int, _void_p]),
     "mpcasm_box_transform": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p,

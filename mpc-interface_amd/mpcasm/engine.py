@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .plan import compile_plan, is_causal
+from .plan import compile_plan, is_causal, rollout_rows, rollout_sizes
 
 
 def _torch():
@@ -362,6 +362,32 @@ def sweep_route(plan):
     return tuple(int(x) for x in out)
 
 
+def rollout_table(plan, records=None, cvec=None, sizes=None):
+    """The words of the row table ``mpcasm_ltv_rollout`` and ``mpcasm_ltv_advance`` read for ``plan`` (compiled
+    with ``ltv=``), an int32 array -- ``mpcasm_ltv_rollout_compile``, host only, no device needed.  ``records``,
+    ``cvec``: :func:`mpcasm.plan.rollout_rows`'s (the default; ``ValueError`` there for a definition that is none
+    of its three kinds); ``sizes``: what they were made for (default: the plan's).  :class:`capi.MpcasmError` with
+    ``MPCASM_ERR_ARG`` for a plan without a dynamics compiled as ``ltv``, sizes that are not the plan's or
+    records that do not fit it."""
+    if records is None:
+        records, cvec = rollout_rows(plan)
+    records = np.ascontiguousarray(records, dtype=np.int32).reshape(-1, capi.ROLL_REC_WORDS)
+    cvec = np.ascontiguousarray(cvec, dtype=np.float64).reshape(-1, 4)
+    if sizes is None:
+        sw = plan.sweep or {}
+        sizes = rollout_sizes(plan) if sw else np.zeros(7, dtype=np.int32)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    lib, words = capi.load(), ctypes.c_int64()
+    args = (itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, sizes.ctypes.data,
+            records.ctypes.data, records.shape[0], cvec.ctypes.data if cvec.size else None, cvec.shape[0])
+    capi.check(lib.mpcasm_ltv_rollout_compile(*args, None, 0, ctypes.byref(words)), "mpcasm_ltv_rollout_compile")
+    host = np.zeros(words.value, dtype=np.int32)
+    capi.check(lib.mpcasm_ltv_rollout_compile(*args, host.ctypes.data, host.size, ctypes.byref(words)),
+               "mpcasm_ltv_rollout_compile")
+    return host
+
+
 STREAMING_LAUNCH_BYTES = 560e6    # results per launch from which P is collected in LDS (resident.hip)
 
 
@@ -625,6 +651,30 @@ class Assembler:
             else:
                 raise ValueError("%s of %r expects %s or %s, got %s"
                                  % ("AB"[slot], name, shape, (self.batch,) + shape, tuple(t.shape)))
+
+    def bind_ltv_window(self, name, A_seq, B_seq, t):
+        """The steps ``[t, t + N)`` of a longer sequence as the per-step matrices of a dynamics compiled as ``ltv``
+        -- ``A_seq`` ``(T, n, n)`` / ``(B, T, n, n)`` and ``B_seq`` ``(T, n, m)`` / ``(B, T, n, m)``, contiguous
+        float64 tensors on this assembler's device, ``t + N <= T`` -- bound by pointer offset, nothing copied:
+        instance ``b`` reads its ``N`` steps from ``t`` on, a batch stride of ``T n n`` (``T n m``) apart.  The
+        receding horizon of a loop is one call per tick (:class:`mpcasm.ltv_loop.LtvLoop`); :meth:`bind_ltv` is
+        for a window that lies on its own."""
+        torch = self._torch
+        g = self._ltv[name]
+        n, m, N = g["n"], g["m"], g["N"]
+        t = int(t)
+        T = A_seq.shape[-3] if torch.is_tensor(A_seq) and A_seq.dim() >= 3 else -1
+        if not 0 <= t <= T - N:
+            raise ValueError("the window [%d, %d) does not lie in the %d steps of the sequence" % (t, t + N, T))
+        for slot, (seq, tail) in enumerate(((A_seq, (T, n, n)), (B_seq, (T, n, m)))):
+            if not (torch.is_tensor(seq) and seq.dtype == torch.float64 and seq.device == self.device
+                    and seq.is_contiguous() and tuple(seq.shape) in (tail, (self.batch,) + tail)):
+                raise ValueError("%s_seq of %r: a contiguous float64 tensor of shape %s or %s on %s"
+                                 % ("AB"[slot], name, tail, (self.batch,) + tail, self.device))
+            i = g["ids"][slot]
+            # (a view that starts at step t: its data_ptr is the window's, the tensor keeps the sequence alive)
+            self._src[i] = seq[..., t:, :, :]
+            self._src_stride[i] = int(np.prod(tail)) if seq.dim() == 4 else 0
 
     def bind_lti(self, name, A, B):
         """System matrices of a dynamics compiled as ``lti``: ``A`` ``(n, n)`` / ``(B, n, n)``
@@ -898,6 +948,97 @@ class Assembler:
                 ptr(status), int(apply_mask) & 0xFFFFFFFF, gmap.table.data_ptr(), gmap.words, work.data_ptr(), n,
                 _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_next_given")
+        return given
+
+    # ---- a plan compiled as ltv: rows and the next given by the forward recursion ------------------------
+    def _rollout_table(self):
+        """The device copy of this plan's row table (:func:`rollout_table`), made once."""
+        if not self._ltv:
+            raise ValueError("no dynamics of this assembler was compiled as ltv: its rows come from preview_rows, "
+                             "its next given from next_given")
+        if getattr(self, "_roll", None) is None:
+            self._roll = self._torch.as_tensor(rollout_table(self.plan), device=self.device)
+        return self._roll
+
+    def _rollout_args(self, given, optim, index, n, writes):
+        torch = self._torch
+        if not 0 <= n <= self.batch:         # (per-instance sources are sized for the batch)
+            raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
+        if not (torch.is_tensor(given) and given.dtype == torch.float64 and given.device == self.device
+                and given.is_contiguous() and given.dim() == 2 and given.shape[1] == self.ng):
+            raise ValueError("given: a contiguous float64 (rows, %d) tensor on %s%s"
+                             % (self.ng, self.device, " (updated in place)" if writes else ""))
+        if not (torch.is_tensor(optim) and optim.dtype == torch.float64 and optim.device == self.device
+                and optim.is_contiguous() and optim.dim() == 2 and optim.shape[1] == self.no and optim.shape[0] >= n):
+            raise ValueError("optim: a contiguous float64 (>= %d, %d) tensor on %s" % (n, self.no, self.device))
+        if index is not None and not torch.is_tensor(index):
+            index = np.asarray(index)
+            if index.ndim != 1 or index.size < n:
+                raise ValueError("index: %d entries" % n)
+            index = index[:n]
+            if writes:
+                index = checked_index(index, given.shape[0])
+            elif index.size and (index.min() < 0 or index.max() >= given.shape[0]):
+                raise ValueError("an index of rows must hold entries in [0, %d)" % given.shape[0])
+            index = torch.as_tensor(index.astype(np.int32), device=self.device)
+        if index is not None and not (index.dtype == torch.int32 and index.device == self.device
+                                      and index.is_contiguous() and index.dim() == 1 and index.numel() >= n):
+            raise ValueError("index: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
+        if index is None and given.shape[0] < n:
+            raise ValueError("given must have %d rows, got %d" % (n, given.shape[0]))
+        return index
+
+    def rollout(self, given, optim, index=None, out=None, count=None, stream=None):
+        """:meth:`preview_rows` for a plan compiled with ``ltv=`` (``mpcasm_ltv_rollout``; body.py:209-219):
+        ``(B, preview_rows)``, rows of definition ``v`` at ``plan.pm_rows[v]``, from the forward recursion
+        ``x_{k+1} = A_k x_k + B_k u_k`` on the ``(A_k, B_k)`` bound now (:meth:`bind_ltv`,
+        :meth:`bind_ltv_window`) -- no horizon matrix, no workspace; the rows that are a given value or an unknown
+        itself are copies, bit for bit.  ``given``: ``(rows, ng)``, ``optim``: ``(>= count, no)``, contiguous
+        float64 tensors on this device; ``index`` (int32 device tensor, or a host array: checked and copied):
+        instance ``b`` reads row ``index[b]`` of ``given``.  The rows are what :meth:`goal_distance` takes: the
+        goals' distances of such a plan are ``asm.goal_distance(form, asm.rollout(given, optim))``.
+        ``ValueError`` on an assembler without ``ltv=``: :meth:`preview_rows` is for it."""
+        torch = self._torch
+        table = self._rollout_table()
+        n = self.batch if count is None else int(count)
+        index = self._rollout_args(given, optim, index, n, False)
+        if out is None:
+            out = torch.empty((self.batch, self.plan.pmrows), dtype=torch.float64, device=self.device)
+        else:
+            _checked_out(torch, out, (n, self.plan.pmrows), self.device, "rollout")
+        ptrs, strides = self._src_args()
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_ltv_rollout(
+                self._handle, ptrs, strides, given.data_ptr(), given.shape[0], optim.data_ptr(),
+                index.data_ptr() if index is not None else None, table.data_ptr(), table.numel(), out.data_ptr(),
+                n, _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_ltv_rollout")
+        return out
+
+    def advance(self, given, optim, index=None, status=None, apply_mask=APPLY_SOLVED, count=None, stream=None):
+        """:meth:`next_given` for a plan compiled with ``ltv=`` (``mpcasm_ltv_advance``; biped_mpc_loop.py:62-95):
+        row ``index[b]`` of ``given`` becomes ``x_1 = A_0 x_0 + B_0 u_0`` of every axis, IN PLACE, from row ``b``
+        of ``optim`` -- every given value of such a plan is an initial state, so no map is needed.  ``index``,
+        ``status`` and ``apply_mask`` as for :meth:`next_given`: distinct rows in range (a host index is checked,
+        :func:`checked_index`), and an instance whose status has no bit in ``apply_mask`` leaves its row exactly
+        as it was.  Returns ``given``.  ``ValueError`` on an assembler without ``ltv=``: :meth:`next_given` is
+        for it."""
+        torch = self._torch
+        table = self._rollout_table()
+        n = self.batch if count is None else int(count)
+        index = self._rollout_args(given, optim, index, n, True)
+        if status is not None and not (torch.is_tensor(status) and status.dtype == torch.int32
+                                       and status.device == self.device and status.is_contiguous()
+                                       and status.dim() == 1 and status.numel() >= n):
+            raise ValueError("status: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
+        ptrs, strides = self._src_args()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_ltv_advance(
+                self._handle, ptrs, strides, given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index),
+                ptr(status), int(apply_mask) & 0xFFFFFFFF, table.data_ptr(), table.numel(), n,
+                _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_ltv_advance")
         return given
 
     def goal_terms(self, form):

@@ -1525,7 +1525,83 @@ def _sweep_tables(b, gterms, limit_recs, lax_recs, rowptr, entbase, entk, entcoe
                 cptr=cptr, cent=cent, gptr=gptr, gent=gent,
                 terms=np.asarray(terms, dtype=np.int64).reshape(-1, SW_TERM_WORDS),
                 lims=np.asarray(lims, dtype=np.int64).reshape(-1, SW_LIM_WORDS + SW_AXMAX * SW_LAX_WORDS),
-                col=col, cvec=cv.reshape(-1)), None
+                col=col, cvec=cv.reshape(-1), state_of=state_of, base_axis=base_axis), None
+
+
+ROLL_GIVEN, ROLL_OPTIM, ROLL_STATE, ROLL_REC_WORDS = 0, 1, 2, 8     # (include/mpcasm.h MPCASM_ROLL_*)
+
+
+def rollout_rows(plan):
+    """The row table of ``mpcasm_ltv_rollout`` / ``mpcasm_ltv_advance`` (csrc/rollout.hip) for a plan compiled
+    with ``ltv=``: ``(records, cvec)`` -- ``records (nrec, ROLL_REC_WORDS)`` int32, one per run of rows of the
+    preview program in the rows' order, ``(kind, first row, rows, axis, k0, kstep, index of c, 0)``, and ``cvec
+    (ncvec, SW_NMAX)`` the combinations ``c`` of the states.  A sweep plan guarantees that every unknown is an
+    input of its one system and every given value an initial state (:func:`_sweep_tables`), so a row of a
+    definition can be
+
+      ``ROLL_GIVEN``   the given value in column ``k0 + i kstep`` itself (an initial state, ``x0_*``);
+      ``ROLL_OPTIM``   the unknown in column ``k0 + i kstep`` itself (a sample of an input);
+      ``ROLL_STATE``   ``c . x_{k+1}``, ``k = k0 + i kstep``: a fixed combination of ONE step's states of one
+                       axis -- row k of a state on the horizon matrices is ``x_{k+1}`` (tools.py:14-33);
+
+    ``ValueError`` naming the definition whose row is none of the three (a combination over two steps or two
+    axes, a multiple of a given value, ...), or when the plan has no dynamics compiled as ``ltv``.  A run ends
+    with its definition: a definition's rows are contiguous in the result."""
+    src = getattr(plan, "rollout_src", None)
+    if not getattr(plan, "sweep", None) or src is None:
+        raise ValueError("no dynamics of this plan was compiled as ltv: preview_rows / next_given are for it")
+    rowptr, entbase, entk, entcoef = src["pm"]
+    state_of, base_axis, ident = plan.sweep["state_of"], plan.sweep["base_axis"], src["ident"]
+    n, ng = plan.sweep["n"], plan.ng
+    recs, cvecs = [], []
+
+    def cvec_index(c):
+        for at, have in enumerate(cvecs):
+            if np.array_equal(have, c):
+                return at
+        cvecs.append(c)
+        return len(cvecs) - 1
+
+    for var, (r0, rows) in plan.pm_rows.items():
+        info = []
+        for r in range(r0, r0 + rows):
+            e0, e1 = int(rowptr[r]), int(rowptr[r + 1])
+            bids, ks = [int(x) for x in entbase[e0:e1]], [int(k) for k in entk[e0:e1]]
+            one = None
+            if e1 - e0 == 1 and bids[0] in ident and float(entcoef[e0]) == 1.0:
+                col = ident[bids[0]] + ks[0]
+                one = (ROLL_GIVEN, 0, col, -1) if col < ng else (ROLL_OPTIM, 0, col - ng, -1)
+            elif e1 > e0 and all(b in state_of for b in bids) and len(set(ks)) == 1 \
+                    and len({base_axis[b] for b in bids}) == 1:
+                c = np.zeros(SW_NMAX)
+                for b, cf in zip(bids, entcoef[e0:e1]):
+                    c[state_of[b]] += cf
+                one = (ROLL_STATE, base_axis[bids[0]], ks[0], cvec_index(c))
+            if one is None:
+                raise ValueError(
+                    "definition %r (sample %d) is neither a given value, an unknown nor a fixed combination of the "
+                    "states of one step and one axis: the rows of this plan cannot be rolled out" % (var, r - r0))
+            info.append(one)
+        i = 0
+        while i < len(info):            # runs: the same kind, axis and c, the steps an arithmetic progression
+            kind, ax, k0, cv = info[i]
+            same = lambda x: (x[0], x[1], x[3]) == (kind, ax, cv)
+            j, kstep = i + 1, 0
+            if j < len(info) and same(info[j]):
+                kstep = info[j][2] - k0
+                while j < len(info) and same(info[j]) and info[j][2] == k0 + (j - i) * kstep:
+                    j += 1
+            recs.append([kind, r0 + i, j - i, ax, k0, kstep, max(cv, 0), 0])
+            i = j
+    return (np.asarray(recs, dtype=np.int32).reshape(-1, ROLL_REC_WORDS),
+            np.asarray(cvecs, dtype=np.float64).reshape(-1, SW_NMAX))
+
+
+def rollout_sizes(plan):
+    """What a row table is made for (``h_sizes`` of ``mpcasm_ltv_rollout_compile``): states, inputs, steps, axes,
+    rows of the preview program, ``ng``, ``no``."""
+    sw = plan.sweep
+    return np.asarray([sw["n"], sw["m"], sw["N"], sw["axes"].shape[0], plan.pmrows, plan.ng, plan.no], dtype=np.int32)
 
 
 def _structural_patterns(form, b, fused, gterms, gr, rtot, ldv, groups=()):
@@ -1820,7 +1896,15 @@ def _sweep_back_end(form, fe, lti, ltv, csc):
                      SW_NCENT=sweep["cent"].size, SW_NGENT=sweep["gent"].shape[0])
     ltv = ([dict(name=tuple(ltv)[0], n=sweep["n"], m=sweep["m"], N=sweep["N"],
                  ids=[sweep["src_a"], sweep["src_b"]])] if sweep is not None else [])
-    return dict(words=words, sections=sections, attrs=dict(sweep=sweep, ltv=ltv))
+    # (what rollout_rows reads, kept beside the plan, not in its tables: the rows of the preview program and the
+    # bases that are a block of [given | optim] themselves, base -> first column)
+    ident = {}
+    for bid, colseg in enumerate(b.colseg):
+        segs = [b.segments[sg] for sg in sorted(set(int(x) for x in colseg if x >= 0))]
+        if len(segs) == 1 and segs[0][6] == SEG_IDENTITY:
+            ident[bid] = segs[0][4]
+    rollout_src = dict(pm=fe.pm, ident=ident) if sweep is not None else None
+    return dict(words=words, sections=sections, attrs=dict(sweep=sweep, ltv=ltv, rollout_src=rollout_src))
 
 
 def _workspace(fe, workspace, csc):
