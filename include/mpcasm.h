@@ -336,6 +336,29 @@ int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_d
  * that does not run on the sweep kernel. */
 int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int32_t out[8]);
 
+/* Diagnostic, needs no device: what mpcasm_assemble launches for the tables of a plan that runs on the tiled
+ * path (128 unknowns or more, not on chip, no dynamics compiled as ltv; tables validated as mpcasm_plan_create
+ * does), for a launch of `batch` instances whose sources have the strides h_src_stride (as for mpcasm_assemble:
+ * 0 for a source the batch shares; may be NULL when the plan has no source), that wants the halves `want`
+ * (MPCASM_WANT_COST | MPCASM_WANT_CONSTRAINTS) under MPCASM_OPT_PATH `path` (0 .. 4; -1: the process-wide value).
+ * The launch takes the decision from the same function.  out[0]: the form, MPCASM_TILED_*; scan form:
+ * out[1]: 1 when the kernel makes its table and d itself (fused), 0 behind the pre-passes; out[2], out[3]: KP, CB
+ * of the instantiation (Hessian terms and column blocks in registers); out[4]: 1 when the records of G's rows
+ * ride in LDS; out[5]: 1 when results leave as whole 128-byte lines.  out[6]: dynamic LDS bytes of a workgroup
+ * of the scan or the Toeplitz kernel; out[7]: 1 when that is more than 64 KB; out[8]: the pre-pass that makes
+ * the horizon tables, MPCASM_TILED_TABLES_*; out[9]: TG of the shared-model form's kernel for P (4 .. 32; 0: P
+ * not wanted or no weight); out[10]: 1 when only the lower block pairs of P are multiplied (Toeplitz, general
+ * and shared form); out[11 .. 15]: 0.  MPCASM_ERR_LIMIT exactly where the launch returns it (out is zeroed):
+ * a generated system beyond 64 states or n (m + n) > 2048 that the fused scan form does not take.
+ * MPCASM_ERR_ARG for a plan that does not run on the tiled path -- the persistent kernel takes a plan that
+ * fits on chip first (input alignment, a property of the launch's pointers, is taken as given). */
+enum { MPCASM_TILED_SCAN = 1, MPCASM_TILED_TOEPLITZ = 2, MPCASM_TILED_SHARED = 3, MPCASM_TILED_GENERAL = 4 };
+enum { MPCASM_TILED_TABLES_NONE = 0, MPCASM_TILED_TABLES_SMALL = 1 /* a wavefront per few systems */,
+       MPCASM_TILED_TABLES_SYSTEM = 2 /* a workgroup per system */ };
+enum { MPCASM_WANT_COST = 1, MPCASM_WANT_CONSTRAINTS = 2 };
+int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                       const int64_t* h_src_stride, int batch, int want, int path, int32_t out[16]);
+
 /* f3  sparse hand-off -----------------------------------------------------------
  * Replaces the dense -> CSC conversion in front of the solver call of the walking loop
  *   Q = scipy.sparse.csc_matrix(Q); A = scipy.sparse.csc_matrix(A)

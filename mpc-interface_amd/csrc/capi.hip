@@ -381,6 +381,9 @@ int validate_tiled(const int32_t* it, const double* h_dtab, int64_t n, int64_t n
     const int32_t* cio = it + it[H_OFF_T_CIO];
     const int32_t* x0 = it + it[H_OFF_T_STAGE];
     const int64_t base0 = x0[TS_BASE] & 0xFFFF, sb0 = x0[TS_SBOFFA];
+    // (a stage's window of TK rows may start up to TK - 1 rows before the horizon's end: what it reads behind the
+    // last row of the table are the zeros the kernel itself keeps there, toeplitz_zero_pad of them -- held to 16,
+    // a stage that starts at row 32 of a horizon of 33 or 34 was refused as malformed)
     if (base0 >= nbase) return MPCASM_ERR_PLAN;
     auto is_u = [&](int64_t sid) {
       for (int64_t j = 0; j < gm; ++j)
@@ -409,7 +412,7 @@ int validate_tiled(const int32_t* it, const double* h_dtab, int64_t n, int64_t n
           if (!valid) continue;
           const int64_t part = (int64_t)(uint32_t)e[0] - sb;
           if (!is_u(sid) || ((e[1] << 8) >> 8) != 1 || part != (int64_t)(uint32_t)e0[0] - sb0 ||
-              part + U < 0 || part + U + 15 + 3 >= tbn + 16)
+              part + U < 0 || part + U + 15 + 3 >= tbn + toeplitz_zero_pad((int)gN))
             return MPCASM_ERR_PLAN;
         }
       }
@@ -1533,6 +1536,49 @@ int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
   out[5] = sweep_lines_ahead(c.cpt);
   out[6] = (int32_t)c.lds;
   out[7] = c.lds > 64 * 1024;
+  return MPCASM_OK;
+}
+
+int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                       const int64_t* h_src_stride, int batch, int want, int path, int32_t out[16]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out || batch < 1 || path < -1 || path > 4 || want < 1 || want > 3)
+    return MPCASM_ERR_ARG;
+  memset(out, 0, 16 * sizeof(int32_t));
+  const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
+  if (rc != MPCASM_OK) return rc;
+  PlanDev d;
+  memset(&d, 0, sizeof d);
+  plan_dev_from_tables(h_itab, &d);
+  if (d.nsrc && !h_src_stride) return MPCASM_ERR_ARG;
+  SrcTable src;
+  memset(&src, 0, sizeof src);
+  for (int s = 0; s < d.nsrc; ++s) {
+    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
+    src.stride[s] = h_src_stride[s];
+  }
+  if (path < 0) path = g_path;
+  // launch_assemble's order: the sweep kernel, the persistent kernel, then the tiled path
+  if (sweep_eligible(d)) return MPCASM_ERR_ARG;
+  d.rs_p_direct = d.rs_ok ? resident_p_direct_for(d, batch) : 0;
+  const size_t rs = resident_lds_bytes(d);
+  if (rs != 0 && rs <= RESIDENT_LDS_LIMIT && (path == 0 || d.rs_nlti != 0 || d.csc_pnnz != 0 || d.csc_gnnz != 0))
+    return MPCASM_ERR_ARG;
+  if (!tiled_eligible(d) || path == 2 || d.csc_pnnz != 0 || d.csc_gnnz != 0) return MPCASM_ERR_ARG;
+  TiledChoice c;
+  const int choice = tiled_choose(d, src, h_itab, path, batch, (want & MPCASM_WANT_COST) != 0,
+                                  (want & MPCASM_WANT_CONSTRAINTS) != 0, true, true, &c);
+  if (choice != MPCASM_OK) return choice;
+  out[0] = c.form;
+  out[1] = c.fused;
+  out[2] = c.kp;
+  out[3] = c.cb;
+  out[4] = c.rows_in_lds;
+  out[5] = c.whole_lines;
+  out[6] = (int32_t)c.lds;
+  out[7] = c.lds > 64 * 1024;
+  out[8] = c.tables;
+  out[9] = c.tg;
+  out[10] = c.sym;
   return MPCASM_OK;
 }
 

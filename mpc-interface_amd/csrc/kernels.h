@@ -37,6 +37,24 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
                           const int32_t* h_itab);
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* work, int batch,
                       const int32_t* h_itab, SrcTable* eff, hipStream_t stream);
+// the zeros toeplitz_assemble_kernel keeps in LDS behind the group's table (doubles; even): what a stage's window
+// may read past the table's end (validate_plan holds the stages to it)
+int toeplitz_zero_pad(int N);
+// host only: what launch_assemble_tiled launches for a plan (mpcasm_tiled_route).  `form`: MPCASM_TILED_*;
+// scan form: fused (the kernel makes its table and d itself) or behind the pre-passes, the instantiation
+// toeplitz_scan_kernel<kp, cb>, whether the records of G's rows ride in LDS, whether results leave as whole
+// lines; `lds`: dynamic LDS of the scan or the Toeplitz kernel; `tables`: the pre-pass that makes the horizon
+// tables (MPCASM_TILED_TABLES_*); `tg`: shared_p_kernel<tg> (0: P not wanted, or no weight); `sym`: only the
+// lower block pairs of P (Toeplitz, general and the K_g of the shared form).  What the decision depends on
+// beside the plan: the sources' strides, the batch, which halves are wanted, MPCASM_OPT_PATH, and whether the
+// launch has `given` and a workspace.
+struct TiledChoice {
+  int form, fused, kp, cb, rows_in_lds, whole_lines, tables, tg, sym;
+  int dlen;     // (scan form: doubles of d in LDS)
+  size_t lds;
+};
+int tiled_choose(const PlanDev& p, const SrcTable& src, const int32_t* h_itab, int path, int batch,
+                 bool want_cost, bool want_constraints, bool have_given, bool have_work, TiledChoice* out);
 // (host only: the streams a launch reads once launch_lti_tables has run -- the strides alone with work == nullptr)
 int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* work, const int32_t* h_itab,
                           SrcTable* eff);

@@ -1737,6 +1737,8 @@ __global__ __launch_bounds__(BLOCK) void shared_qh_kernel(PlanDev p, const doubl
 
 extern int g_phase_mask;  // fused.hip (MPCASM_OPT_PHASE_MASK)
 
+int toeplitz_zero_pad(int N) { return (std::max(N, 16) + 16 + 1) & ~1; }  // (even: what follows stays 16-byte aligned)
+
 bool tiled_eligible(const PlanDev& p) { return p.t_ok != 0 && p.no >= T_BLOCK; }
 
 // the shared-model form may run on plans without generated groups and with rows of G in 16-byte pieces
@@ -1774,6 +1776,44 @@ int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* w, cons
   return MPCASM_OK;
 }
 
+namespace {
+
+// the pre-pass that makes the generated groups' horizon tables: a wavefront per `systems` systems while every
+// group is small, else a workgroup per system
+struct LtiTablesChoice {
+  int kind;             // MPCASM_TILED_TABLES_*
+  size_t lds, small;    // per-system kernel: its dynamic LDS; small kernel: doubles of one system
+  int lanes, systems;
+};
+
+LtiTablesChoice lti_tables_choose(const PlanDev& p, const int32_t* h_itab) {
+  LtiTablesChoice c{MPCASM_TILED_TABLES_NONE, 0, 0, 1, 1};
+  if (p.t_nlti == 0) return c;
+  bool all_small = true;
+  for (int g = 0; g < p.t_nlti; ++g) {
+    const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
+    const size_t n = rec[TL_N], m = rec[TL_M], N = rec[TL_HORIZON];
+    c.lds = std::max(c.lds, (n * n + 2 * n * (m + n) + n * m * LTI_HIST) * sizeof(double));
+    const size_t tables = N * n * n + n * m * 2 * N;
+    all_small = all_small && n * (m + n) <= 64 && tables <= 1800;  // (four wavefronts: under 64 KB of LDS)
+    c.small = std::max(c.small, 192 + tables + (tables & 1));
+  }
+  c.kind = all_small ? MPCASM_TILED_TABLES_SMALL : MPCASM_TILED_TABLES_SYSTEM;
+  if (all_small) {  // a wavefront per `systems` systems
+    size_t elems = 0;
+    for (int g = 0; g < p.t_nlti; ++g) {
+      const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
+      elems = std::max<size_t>(elems, (size_t)rec[TL_N] * (rec[TL_M] + rec[TL_N]));
+    }
+    while ((size_t)c.lanes < elems) c.lanes *= 2;
+    // (as many systems per wavefront as lanes and 64 KB of LDS per workgroup allow)
+    c.systems = (int)std::max<size_t>(1, std::min<size_t>(64 / c.lanes, (64 * 1024 / sizeof(double) / (BLOCK / 64)) / c.small));
+  }
+  return c;
+}
+
+}  // namespace
+
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* w, int batch,
                       const int32_t* h_itab, SrcTable* eff, hipStream_t stream) {
   *eff = src;
@@ -1784,51 +1824,33 @@ int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* w, int batc
     const int rc = lti_effective_sources(p, src, w, h_itab, eff);
     if (rc != MPCASM_OK) return rc;
   }
-  size_t lds = 0, small = 0;
-  bool all_small = true;
-  for (int g = 0; g < p.t_nlti; ++g) {
-    const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
-    const size_t n = rec[TL_N], m = rec[TL_M], N = rec[TL_HORIZON];
-    lds = std::max(lds, (n * n + 2 * n * (m + n) + n * m * LTI_HIST) * sizeof(double));
-    const size_t tables = N * n * n + n * m * 2 * N;
-    all_small = all_small && n * (m + n) <= 64 && tables <= 1800;  // (four wavefronts: under 64 KB of LDS)
-    small = std::max(small, 192 + tables + (tables & 1));
-  }
-  if (all_small) {  // a wavefront per `systems` systems
-    size_t elems = 0;
-    for (int g = 0; g < p.t_nlti; ++g) {
-      const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
-      elems = std::max<size_t>(elems, (size_t)rec[TL_N] * (rec[TL_M] + rec[TL_N]));
-    }
-    int lanes = 1;
-    while ((size_t)lanes < elems) lanes *= 2;
-    // (as many systems per wavefront as lanes and 64 KB of LDS per workgroup allow)
-    const int systems = (int)std::max<size_t>(1, std::min<size_t>(64 / lanes, (64 * 1024 / sizeof(double) / (BLOCK / 64)) / small));
+  const LtiTablesChoice c = lti_tables_choose(p, h_itab);
+  if (c.kind == MPCASM_TILED_TABLES_SMALL) {
     const long jobs = (long)batch * p.t_nlti;
-    const long per_wg = (long)(BLOCK / 64) * systems;
+    const long per_wg = (long)(BLOCK / 64) * c.systems;
     const unsigned grid = (unsigned)std::min<long>((jobs + per_wg - 1) / per_wg, 256L * 8);
     hipLaunchKernelGGL(lti_tables_small_kernel, dim3(grid), dim3(BLOCK),
-                       small * systems * (BLOCK / 64) * sizeof(double), stream, p, src, w, stride, jobs, (int)small,
-                       lanes, systems);
+                       c.small * c.systems * (BLOCK / 64) * sizeof(double), stream, p, src, w, stride, jobs,
+                       (int)c.small, c.lanes, c.systems);
     return MPCASM_OK;
   }
-  hipLaunchKernelGGL(lti_tables_kernel, dim3((unsigned)batch * p.t_nlti), dim3(BLOCK), lds, stream, p,
+  hipLaunchKernelGGL(lti_tables_kernel, dim3((unsigned)batch * p.t_nlti), dim3(BLOCK), c.lds, stream, p,
                      src, w, stride);
   return MPCASM_OK;
 }
 
 namespace {
 
-// The shared-model form; MPCASM_ERR_LIMIT when the launch is not one (a source of an instance's own, more
-// weights than SH_TMAX, a row of G with more than two axes, an odd width): the general kernel then.
-int launch_shared_form(const PlanDev& p, const SrcTable& eff, const double* params, double* w,
-                       long long stride, double* P, double* q, double* G, double* h, int batch, int nb,
-                       int npairs, int sym, const int32_t* h_itab, hipStream_t stream, hipError_t* err) {
-  if (!shared_form_plan(p) || w == nullptr) return MPCASM_ERR_LIMIT;
+// Whether a launch is one of the shared-model form, and the weight parameters of its Hessian terms (of every
+// stage and of every diagonal term); MPCASM_ERR_LIMIT when it is not (a source of an instance's own, more
+// weights than SH_TMAX, a batch that does not pay for the K_g, a row of G with more than two axes, an odd
+// width): the general kernel then.
+int shared_form_choose(const PlanDev& p, const SrcTable& eff, const int32_t* h_itab, int batch,
+                       bool want_constraints, bool have_work, SharedSlots* out, size_t* qh_lds_out) {
+  if (!shared_form_plan(p) || !have_work) return MPCASM_ERR_LIMIT;
   for (int i = 0; i < p.nsrc; ++i)
     if (eff.stride[i] != 0) return MPCASM_ERR_LIMIT;
-  // the weight parameters: of every stage and of every diagonal term
-  SharedSlots sl;
+  SharedSlots& sl = *out;
   sl.n = 0;
   for (int g = 0; g < SH_TMAX; ++g) sl.slot[g] = 0;
   auto add = [&](int slot) {
@@ -1845,12 +1867,34 @@ int launch_shared_form(const PlanDev& p, const SrcTable& eff, const double* para
     if ((rec[GT_FLAGS] & GT_FLAG_DIAG) && !add(rec[GT_WPARAM])) return MPCASM_ERR_LIMIT;
   }
   if (batch < 2 * sl.n) return MPCASM_ERR_LIMIT;   // (the K_g cost a launch of sl.n instances themselves)
-  if (G != nullptr)
+  if (want_constraints)
     for (int R = 0; R < p.nc; ++R)
       if (h_itab[p.off_rs_rr + R * RS_RR_WORDS + RR_NAXES] > 2) return MPCASM_ERR_LIMIT;
   const int nrho = p.t_nstage * TK;
   const size_t qh_lds = (size_t)nrho * SH_QB * sizeof(double) + (size_t)nrho * sizeof(int);
   if (qh_lds > 64 * 1024) return MPCASM_ERR_LIMIT;
+  *qh_lds_out = qh_lds;
+  return MPCASM_OK;
+}
+
+// (the kernel multiplies by every one of its TG matrices, the ones behind the last being zeros: the
+// instantiation just above the number of weights -- at 32 for C4's 18 the kernel was bound by its FMAs)
+int shared_tg(int weights) {
+  return weights > 24 ? 32 : weights > 20 ? 24 : weights > 16 ? 20 : weights > 12 ? 16 : weights > 8 ? 12
+         : weights > 4 ? 8 : weights > 0 ? 4 : 0;
+}
+
+// The shared-model form, for a launch tiled_choose found to be one
+int launch_shared_form(const PlanDev& p, const SrcTable& eff, const double* params, double* w,
+                       long long stride, double* P, double* q, double* G, double* h, int batch, int nb,
+                       int npairs, int sym, int tg, const int32_t* h_itab, hipStream_t stream, hipError_t* err) {
+  SharedSlots sl;
+  size_t qh_lds = 0;
+  {
+    const int rc = shared_form_choose(p, eff, h_itab, batch, G != nullptr, w != nullptr, &sl, &qh_lds);
+    if (rc != MPCASM_OK) return rc;
+  }
+  const int nrho = p.t_nstage * TK;
   const SharedScratch S = shared_scratch(p);
   double* base = w + (size_t)batch * stride;
   double* V = base + S.v;
@@ -1874,20 +1918,26 @@ int launch_shared_form(const PlanDev& p, const SrcTable& eff, const double* para
   }
   if (P != nullptr) {
     const dim3 pgrid((unsigned)ceil_div(nn, (long)SH_PRANGE), (unsigned)ceil_div(batch, SH_PIB));
-    // (the kernel multiplies by every one of its TG matrices, the ones behind the last being zeros: the
-    // instantiation just above the number of weights -- at 32 for C4's 18 the kernel was bound by its FMAs)
 #define MPCASM_SHARED_P(TG)                                                                                \
-  hipLaunchKernelGGL((shared_p_kernel<TG>), pgrid, dim3(BLOCK), 0, stream, sl, nn, K, params, p.nparams, P, batch)
-    if (sl.n > 24) MPCASM_SHARED_P(32);
-    else if (sl.n > 20) MPCASM_SHARED_P(24);
-    else if (sl.n > 16) MPCASM_SHARED_P(20);
-    else if (sl.n > 12) MPCASM_SHARED_P(16);
-    else if (sl.n > 8) MPCASM_SHARED_P(12);
-    else if (sl.n > 4) MPCASM_SHARED_P(8);
-    else if (sl.n > 0) MPCASM_SHARED_P(4);
+  case TG:                                                                                                 \
+    hipLaunchKernelGGL((shared_p_kernel<TG>), pgrid, dim3(BLOCK), 0, stream, sl, nn, K, params, p.nparams, P, \
+                       batch);                                                                             \
+    break;
+    switch (tg) {
+      MPCASM_SHARED_P(32)
+      MPCASM_SHARED_P(24)
+      MPCASM_SHARED_P(20)
+      MPCASM_SHARED_P(16)
+      MPCASM_SHARED_P(12)
+      MPCASM_SHARED_P(8)
+      MPCASM_SHARED_P(4)
 #undef MPCASM_SHARED_P
-    else
-      (void)hipMemsetAsync(P, 0, sizeof(double) * (size_t)batch * nn, stream);
+      case 0:
+        (void)hipMemsetAsync(P, 0, sizeof(double) * (size_t)batch * nn, stream);
+        break;
+      default:
+        return MPCASM_ERR_LIMIT;   // (tiled_choose and this list have come apart)
+    }
   }
   if (G != nullptr && p.nc > 0)
     hipLaunchKernelGGL(shared_g_kernel,
@@ -1930,33 +1980,51 @@ int launch_scan_as(const PlanDev& p, const SrcTable& eff, const double* A, long 
 
 // the scan form for this plan, or MPCASM_ERR_LIMIT: no instantiation holds its K terms and column
 // blocks in registers, or an instance does not fit in LDS (the Toeplitz form takes it then).
-// `src`: the launch's own sources (the group's (A, B) in the slots of its first two), `eff`: with the
-// generated tables in the places of the group's U_j and S.
-// `fused`: no pre-pass has run -- the kernel makes its table and d itself (H_T_SCAN_FUSED); `eff` and `w` unused.
-int launch_scan(const PlanDev& p, const SrcTable& src, const SrcTable& eff, const double* params,
-                const double* w, long long stride, double* P, double* q, double* G, double* h, int batch,
-                const int32_t* h_itab, hipStream_t stream, hipError_t* err, const double* given = nullptr,
-                int fused = 0) {
+// `fused`: no pre-pass runs -- the kernel makes its table and d itself (H_T_SCAN_FUSED).
+int scan_choose(const PlanDev& p, const int32_t* h_itab, bool fused, bool have_given, TiledChoice* c) {
   const int K = p.t_scan, nblk = p.t_scan_nblk;
   const int32_t* rec = h_itab + p.off_t_lti;
   const int n = rec[TL_N], m = rec[TL_M], N = rec[TL_HORIZON];
   if (p.no > 128 * SCAN_GCH_MAX || n > 64 || (N & 1)) return MPCASM_ERR_LIMIT;
-  if (fused && given == nullptr) return MPCASM_ERR_LIMIT;
+  if (fused && !have_given) return MPCASM_ERR_LIMIT;
   const int dlen = p.rtot + (p.rtot & 1);
   // the records of G's rows in LDS while that leaves room for two workgroups per CU
   const int rows_in_lds = scan_lds(dlen, p.nparams, n, m, N, p.nc, true).total + NSTREAM * sizeof(double*) <= SCAN_HALF_CU;
   const size_t lds = scan_lds(dlen, p.nparams, n, m, N, p.nc, rows_in_lds != 0).total;
   if (lds + NSTREAM * sizeof(double*) > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
-  const int32_t* ids = h_itab + p.off_t_lti_ids + rec[TL_IDS];
   // results leave as whole 128-byte lines when every run of a wavefront's store starts and ends on one
   int whole = p.no % 16 == 0 && N % 16 == 0;
   const int32_t* blk = h_itab + p.off_t_scan_blk;
   for (int b = 0; b < nblk; ++b) whole = whole && blk[2 * b] % 16 == 0;
+  // the instantiations, in the order they are tried
+  static const int inst[][2] = {{4, 4}, {8, 4}, {4, 8}, {8, 8}, {12, 4}, {12, 6}, {16, 4}};
+  for (const auto& kc : inst)
+    if (K <= kc[0] && nblk <= kc[1]) {
+      c->fused = fused;
+      c->kp = kc[0];
+      c->cb = kc[1];
+      c->rows_in_lds = rows_in_lds;
+      c->whole_lines = whole;
+      c->dlen = dlen;
+      c->lds = lds;
+      return MPCASM_OK;
+    }
+  return MPCASM_ERR_LIMIT;
+}
+
+// the scan form as tiled_choose picked it.  `src`: the launch's own sources (the group's (A, B) in the slots of
+// its first two), `eff`: with the generated tables in the places of the group's U_j and S (fused: unused, as `w`)
+int launch_scan(const PlanDev& p, const SrcTable& src, const SrcTable& eff, const double* params,
+                const double* w, long long stride, double* P, double* q, double* G, double* h, int batch,
+                const int32_t* h_itab, const TiledChoice& c, const double* given, hipStream_t stream,
+                hipError_t* err) {
+  const int32_t* rec = h_itab + p.off_t_lti;
+  const int32_t* ids = h_itab + p.off_t_lti_ids + rec[TL_IDS];
 #define MPCASM_SCAN_CASE(KP, CB)                                                                          \
-  if (K <= KP && nblk <= CB)                                                                             \
+  if (c.kp == KP && c.cb == CB)                                                                          \
     return launch_scan_as<KP, CB>(p, eff, src.ptr[ids[0]], src.stride[ids[0]], src.ptr[ids[1]],           \
-                                  src.stride[ids[1]], params, w, stride, P, q, G, h, batch, dlen, whole, \
-                                  rows_in_lds, lds, given, fused, stream, err);
+                                  src.stride[ids[1]], params, w, stride, P, q, G, h, batch, c.dlen,       \
+                                  c.whole_lines, c.rows_in_lds, c.lds, given, c.fused, stream, err);
   MPCASM_SCAN_CASE(4, 4)
   MPCASM_SCAN_CASE(8, 4)
   MPCASM_SCAN_CASE(4, 8)
@@ -1965,10 +2033,97 @@ int launch_scan(const PlanDev& p, const SrcTable& src, const SrcTable& eff, cons
   MPCASM_SCAN_CASE(12, 6)
   MPCASM_SCAN_CASE(16, 4)
 #undef MPCASM_SCAN_CASE
-  return MPCASM_ERR_LIMIT;
+  return MPCASM_ERR_LIMIT;   // (scan_choose and this list have come apart)
+}
+
+// the Toeplitz kernel's dynamic LDS (behind the table and the zeros: d, and at the end of a diagonal block the
+// gradient's partial sums of four wavefronts + the diagonal gterms of its T_BLOCK columns)
+struct ToeplitzLds {
+  int tbn, nzero;
+  size_t total;
+};
+ToeplitzLds toeplitz_lds(const PlanDev& p, const int32_t* rec) {
+  ToeplitzLds x;
+  x.tbn = rec[TL_N] * rec[TL_M] * 2 * rec[TL_HORIZON];
+  x.nzero = toeplitz_zero_pad(rec[TL_HORIZON]);
+  x.total = ((size_t)x.tbn + x.nzero + std::max(p.rtot + (p.rtot & 1), (WAVES + 1) * T_BLOCK)) * sizeof(double);
+  return x;
 }
 
 }  // namespace
+
+// The one decision, taken by launch_assemble_tiled and reported by mpcasm_tiled_route: which form a launch runs
+// on and with what, or the launch's refusal.  Only the strides of `src` are read.
+int tiled_choose(const PlanDev& p, const SrcTable& src, const int32_t* h_itab, int path, int batch,
+                 bool want_cost, bool want_constraints, bool have_given, bool have_work, TiledChoice* out) {
+  TiledChoice c{};
+  *out = c;
+  c.sym = p.rs_sym_any;
+  // the scan form with its set-up fused (H_T_SCAN_FUSED): one kernel, no scratch (MPCASM_OPT_PATH 1 keeps the
+  // pre-passes: the A/B of the two)
+  if (p.t_scan_fused && p.t_scan > 0 && p.t_toeplitz && p.t_nlti == 1 && h_itab != nullptr && path == 0 &&
+      (p.no & 1) == 0) {
+    const int rc = scan_choose(p, h_itab, true, have_given, &c);
+    if (rc == MPCASM_OK) {
+      c.form = MPCASM_TILED_SCAN;
+      c.sym = 0;   // (the scan form writes every row of P)
+      *out = c;
+      return MPCASM_OK;
+    }
+    if (rc != MPCASM_ERR_LIMIT) return rc;
+  }
+  // the pre-passes: the generated groups' horizon tables, then d
+  SrcTable eff = src;
+  if (p.t_nlti != 0) {
+    if (h_itab == nullptr || !have_work) return MPCASM_ERR_ARG;
+    const int rc = lti_effective_sources(p, src, nullptr, h_itab, &eff);
+    if (rc != MPCASM_OK) return rc;
+    c.tables = lti_tables_choose(p, h_itab).kind;
+  }
+  if (p.rtot > 0 && (size_t)p.ng * sizeof(double) > 48 * 1024) return MPCASM_ERR_LIMIT;
+  const long long stride = p.t_work;
+  // (the Toeplitz forms write rows of G in 16-byte pieces: an even width)
+  if (p.t_toeplitz && p.t_nlti == 1 && h_itab != nullptr && path != 3 && (p.no & 1) == 0) {
+    // every stage is a window of the one generated group's table: operands straight out of LDS
+    const int32_t* rec = h_itab + p.off_t_lti;
+    const bool aligned = (rec[TL_TB] & 1) == 0 && (stride & 1) == 0;
+    if (p.t_scan > 0 && path != 4 && aligned) {
+      // scan form: every Hessian term is the full horizon of one state -- P is a sum along diagonals
+      const int rc = scan_choose(p, h_itab, false, have_given, &c);
+      if (rc == MPCASM_OK) {
+        c.form = MPCASM_TILED_SCAN;
+        c.sym = 0;
+        *out = c;
+        return MPCASM_OK;
+      }
+      if (rc != MPCASM_ERR_LIMIT) return rc;
+    }
+    const size_t lds = toeplitz_lds(p, rec).total;
+    if (lds <= (size_t)RESIDENT_LDS_LIMIT && aligned) {
+      c.form = MPCASM_TILED_TOEPLITZ;
+      c.lds = lds;
+      *out = c;
+      return MPCASM_OK;
+    }
+  }
+  // one model for the whole batch (every source shared): P and G are weighted sums of matrices that are
+  // the same for every instance -- the shared-model form (MPCASM_OPT_PATH 3 keeps the general kernel)
+  if (path != 3 && h_itab != nullptr && batch >= 8) {
+    SharedSlots sl;
+    size_t qh_lds = 0;
+    const int rc = shared_form_choose(p, eff, h_itab, batch, want_constraints, have_work, &sl, &qh_lds);
+    if (rc == MPCASM_OK) {
+      c.form = MPCASM_TILED_SHARED;
+      c.tg = want_cost ? shared_tg(sl.n) : 0;
+      *out = c;
+      return MPCASM_OK;
+    }
+    if (rc != MPCASM_ERR_LIMIT) return rc;
+  }
+  c.form = MPCASM_TILED_GENERAL;
+  *out = c;
+  return MPCASM_OK;
+}
 
 int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* params,
                           const double* given, double* P, double* q, double* G, double* h,
@@ -1976,13 +2131,14 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
                           const int32_t* h_itab) {
   double* w = static_cast<double*>(work);
   const long long stride = p.t_work;
-  // the scan form with its set-up fused (H_T_SCAN_FUSED): one kernel, no scratch (MPCASM_OPT_PATH 1 keeps the
-  // pre-passes: the A/B of the two)
-  if (p.t_scan_fused && p.t_scan > 0 && p.t_toeplitz && p.t_nlti == 1 && h_itab != nullptr && t_path == 0 &&
-      (p.no & 1) == 0) {
-    const int rc = launch_scan(p, src, src, params, nullptr, 0, P, q, G, h, batch, h_itab, stream, err, given, 1);
-    if (rc != MPCASM_ERR_LIMIT) return rc;
+  TiledChoice c;
+  {
+    const int rc = tiled_choose(p, src, h_itab, t_path, batch, P != nullptr, G != nullptr, given != nullptr,
+                                w != nullptr, &c);
+    if (rc != MPCASM_OK) return rc;
   }
+  if (c.form == MPCASM_TILED_SCAN && c.fused)
+    return launch_scan(p, src, src, params, nullptr, 0, P, q, G, h, batch, h_itab, c, given, stream, err);
   SrcTable eff;
   {
     const int rc = launch_lti_tables(p, src, w, batch, h_itab, &eff, stream);
@@ -1990,7 +2146,6 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
   }
   if (p.rtot > 0) {
     const unsigned nrb = ceil_div(p.rtot, BLOCK);
-    if ((size_t)p.ng * sizeof(double) > 48 * 1024) return MPCASM_ERR_LIMIT;
     hipLaunchKernelGGL(compose_d_kernel, dim3(nrb * batch), dim3(BLOCK), (size_t)p.ng * sizeof(double),
                        stream, p, eff, given, w, stride, (int)nrb);
   }
@@ -1998,36 +2153,24 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
   const int sym = p.rs_sym_any;
   const int npairs = sym ? nb * (nb + 1) / 2 : nb * nb;
   const unsigned groups = ceil_div((unsigned)batch, 8u);
-  // (the Toeplitz forms write rows of G in 16-byte pieces: an even width)
-  if (p.t_toeplitz && p.t_nlti == 1 && h_itab != nullptr && t_path != 3 && (p.no & 1) == 0) {
-    // every stage is a window of the one generated group's table: operands straight out of LDS
-    const int32_t* rec = h_itab + p.off_t_lti;
-    const int tbn = rec[TL_N] * rec[TL_M] * 2 * rec[TL_HORIZON];
-    if (p.t_scan > 0 && t_path != 4 && (rec[TL_TB] & 1) == 0 && (stride & 1) == 0) {
-      // scan form: every Hessian term is the full horizon of one state -- P is a sum along diagonals
-      const int rc = launch_scan(p, src, eff, params, w, stride, P, q, G, h, batch, h_itab, stream, err);
-      if (rc != MPCASM_ERR_LIMIT) return rc;
-    }
-    const int nzero = (std::max(rec[TL_HORIZON], 16) + 16 + 1) & ~1;  // (even: what follows stays 16-byte aligned)
-    // (behind the table and the zeros: d, and at the end of a diagonal block the gradient's partial
-    // sums of four wavefronts + the diagonal gterms of its T_BLOCK columns)
-    const size_t lds = ((size_t)tbn + nzero + std::max(p.rtot + (p.rtot & 1), (WAVES + 1) * T_BLOCK)) * sizeof(double);
-    if (lds <= (size_t)RESIDENT_LDS_LIMIT && (rec[TL_TB] & 1) == 0 && (stride & 1) == 0) {
+  switch (c.form) {
+    case MPCASM_TILED_SCAN:
+      return launch_scan(p, src, eff, params, w, stride, P, q, G, h, batch, h_itab, c, nullptr, stream, err);
+    case MPCASM_TILED_TOEPLITZ: {
+      const ToeplitzLds x = toeplitz_lds(p, h_itab + p.off_t_lti);
       *err = allow_whole_lds(reinterpret_cast<const void*>(toeplitz_assemble_kernel));
       if (*err != hipSuccess) return MPCASM_ERR_HIP;
-      hipLaunchKernelGGL(toeplitz_assemble_kernel, dim3((unsigned)batch), dim3(BLOCK), lds,
-                         stream, p, eff, params, w, stride, P, q, G, h, nb, npairs, sym, batch, tbn, nzero,
+      hipLaunchKernelGGL(toeplitz_assemble_kernel, dim3((unsigned)batch), dim3(BLOCK), c.lds,
+                         stream, p, eff, params, w, stride, P, q, G, h, nb, npairs, sym, batch, x.tbn, x.nzero,
                          g_phase_mask);
       *err = hipGetLastError();
       return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
     }
-  }
-  // one model for the whole batch (every source shared): P and G are weighted sums of matrices that are
-  // the same for every instance -- the shared-model form (MPCASM_OPT_PATH 3 keeps the general kernel)
-  if (t_path != 3 && h_itab != nullptr && batch >= 8) {
-    const int rc = launch_shared_form(p, eff, params, w, stride, P, q, G, h, batch, nb, npairs, sym, h_itab,
-                                      stream, err);
-    if (rc != MPCASM_ERR_LIMIT) return rc;
+    case MPCASM_TILED_SHARED:
+      return launch_shared_form(p, eff, params, w, stride, P, q, G, h, batch, nb, npairs, sym, c.tg, h_itab,
+                                stream, err);
+    default:
+      break;
   }
   t_last_kernel = MPCASM_KERNEL_TILED;
   hipLaunchKernelGGL(tiled_assemble_kernel, dim3(groups * 8 * (unsigned)npairs), dim3(BLOCK), 0,

@@ -74,6 +74,9 @@ SIGNATURES = {
                                             ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_sweep_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
                                           ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_tiled_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),
@@ -147,6 +150,10 @@ KERNEL_NAMES = {0: "none", 1: "resident_assemble_kernel (persistent, ahead of ti
                 8: "shared_p_kernel / shared_g_kernel (tiled, shared-model form: weighted sums of per-term matrices)"}
 PREVIEW_NONE, PREVIEW_DIRECT, PREVIEW_STAGED, PREVIEW_BLOCKED = range(4)   # out[0] of mpcasm_preview_route
 PREVIEW_ROUTES = {0: "none", 1: "direct", 2: "staged", 3: "blocked"}
+TILED_SCAN, TILED_TOEPLITZ, TILED_SHARED, TILED_GENERAL = range(1, 5)         # out[0] of mpcasm_tiled_route
+TILED_FORMS = {1: "scan", 2: "toeplitz", 3: "shared", 4: "general"}
+TILED_TABLES_NONE, TILED_TABLES_SMALL, TILED_TABLES_SYSTEM = range(3)         # out[8]
+WANT_COST, WANT_CONSTRAINTS = 1, 2
 BOX_RECENTER, BOX_TRANSLATE, BOX_ROTATE, BOX_SCALE, BOX_MARGIN = range(5)
 
 

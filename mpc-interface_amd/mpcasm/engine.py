@@ -362,6 +362,31 @@ def sweep_route(plan):
     return tuple(int(x) for x in out)
 
 
+TiledRoute = collections.namedtuple(
+    "TiledRoute", "form fused kp cb rows_in_lds whole_lines lds whole_lds tables tg sym")
+
+
+def tiled_route(plan, batch, src_stride=None, want=capi.WANT_COST | capi.WANT_CONSTRAINTS, path=0):
+    """What ``mpcasm_assemble`` launches for a plan on the tiled path (csrc/tiled.hip) -- ``mpcasm_tiled_route``,
+    the launch's own decision, no device needed -- for ``batch`` instances whose sources have the strides
+    ``src_stride`` (default: every source shared by the batch; the slots of a dynamics compiled with ``lti=``
+    carry its ``(A, B)``), the halves ``want`` (``capi.WANT_COST | capi.WANT_CONSTRAINTS``) and
+    ``MPCASM_OPT_PATH`` ``path`` (``-1``: the process-wide value).  A :class:`TiledRoute`: ``form`` one of
+    ``capi.TILED_*``; for the scan form ``fused``, the instantiation ``toeplitz_scan_kernel<kp, cb>``,
+    ``rows_in_lds`` and ``whole_lines``; ``lds`` bytes of the scan or Toeplitz kernel and ``whole_lds`` (more than
+    64 KB); ``tables`` one of ``capi.TILED_TABLES_*``; ``tg`` of ``shared_p_kernel<tg>``; ``sym``.  Raises
+    :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the plan, with ``MPCASM_ERR_ARG``
+    for a plan that does not run on the tiled path."""
+    out = (ctypes.c_int32 * 16)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    n = len(plan.sources)
+    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
+    capi.check(capi.load().mpcasm_tiled_route(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides, int(batch),
+        int(want), int(path), out), "mpcasm_tiled_route")
+    return TiledRoute(*(int(x) for x in out[:11]))
+
+
 def rollout_table(plan, records=None, cvec=None, sizes=None):
     """The words of the row table ``mpcasm_ltv_rollout`` and ``mpcasm_ltv_advance`` read for ``plan`` (compiled
     with ``ltv=``), an int32 array -- ``mpcasm_ltv_rollout_compile``, host only, no device needed.  ``records``,
@@ -532,6 +557,8 @@ class Assembler:
         process-wide value again.  Plan state, unlike ``mpcasm_set_option``."""
         capi.check(capi.load().mpcasm_plan_set_option(self._handle, int(option), int(value)),
                    "mpcasm_plan_set_option")
+        if int(option) == capi.OPT_PATH:
+            self._opt_path = int(value)
 
     # ---- per-instance numbers -------------------------------------------------
     def refresh_params(self):
@@ -888,6 +915,13 @@ class Assembler:
     def sweep_route(self):
         """The instantiation of the sweep kernel :meth:`assemble` launches for this plan (:func:`sweep_route`)."""
         return sweep_route(self.plan)
+
+    def tiled_route(self, want_cost=True, want_constraints=True, count=None):
+        """What :meth:`assemble` launches on the tiled path with the sources bound now and this assembler's
+        ``capi.OPT_PATH`` (:func:`tiled_route`)."""
+        want = (capi.WANT_COST if want_cost else 0) | (capi.WANT_CONSTRAINTS if want_constraints and self.nc else 0)
+        return tiled_route(self.plan, self.batch if count is None else int(count), self._src_stride, want,
+                           getattr(self, "_opt_path", -1))
 
     def given_map(self, rules):
         """The device table of a given map for this assembler's plan (``mpcasm_given_map_compile``; rules as

@@ -39,11 +39,12 @@ def ranges_from_json(text):
 
 
 def lti_tracking_problem(api, rng, nx, nu, N, *, scaled=False, extra_unknown=False, given_input=False,
-                  two_axis_limit=False, scheduled_cost=False, plant=None):
+                  two_axis_limit=False, scheduled_cost=False, crossed_cost=False, plant=None):
     """A random LTI tracking problem (problems.random_lti) with the features the scan form of the
     tiled kernel has to tell apart: a cost on a multiple of a state (coefficient != 1), unknowns that
     are no input of the plant, an input that is GIVEN, a limit over two states (a row of G that is no
-    single state row), a cost on part of the horizon (no scan form).  ``plant``: the nominal ``(A, B)``
+    single state row), a cost on part of the horizon (no scan form), a crossed cost of two states (rows A != rows
+    B: P is not symmetric, every block pair is computed; no scan form).  ``plant``: the nominal ``(A, B)``
     (default: problems.random_lti_matrices)."""
     from mpcasm import problems
 
@@ -62,6 +63,9 @@ def lti_tracking_problem(api, rng, nx, nu, N, *, scaled=False, extra_unknown=Fal
         form.incorporate_goal("track " + name, api.Cost(
             var, float(rng.uniform(0.1, 1)), aim=[float(rng.normal())],
             schedule=range(2, N) if scheduled_cost and i == 0 else range(0)))
+    if crossed_cost:
+        form.incorporate_goal("crossed", api.Cost("s0", 0.4, aim=[float(rng.normal())], cross="s1",
+                                                  cross_aim=[float(rng.normal())]))
     form.incorporate_goal("effort", api.Cost(inputs[-1], 0.3))
     if extra_unknown:
         form.incorporate_goal("slack", api.Cost("slack", 0.2, aim=[0.1]))

@@ -657,27 +657,86 @@ def run_tiled(plan, given, params=None, sources=None, ab=None):
     return {"P": Pm, "q": q, "G": G, "h": h, "d": d, "Vo": Vo[:, :no]}
 
 
-def run_scan(plan, given, params=None, ab=None):
+def fused_setup(plan, given, ab):
+    """The table ``Tc[(i m + j) N + d] = (A^d B)[i][j]`` and the free response ``x_k = A^{k+1} given`` as the scan
+    kernel's fused set-up makes them (csrc/tiled.hip toeplitz_scan_kernel, H_T_SCAN_FUSED), by DOUBLING: with
+    ``A^have`` at hand, ``X_{have + d} = A^have X_d`` for ``d < cnt = min(have, N - have)`` at once, then
+    ``A^{2 have}`` unless the round was the last -- the kernel's rounds, and its order of every n-term sum (t = 0
+    first; a multiply and an add where the kernel has one fma).  Then ``d[first row of term g + k] = c_g
+    x_k[state of g]``.  Returns ``(Tc, x, d)``: ``(n m N,)``, ``(N, n)``, ``(rtot,)``."""
+    it, dt = plan.itab, plan.dtab
+    assert it[H["T_SCAN_FUSED"]] == 1
+    lti = _section(it, "OFF_T_LTI", P.T_LTI_WORDS)
+    n, m, N = int(lti[0]), int(lti[1]), int(lti[2])
+    Am, Bm = (np.asarray(x, dtype=np.float64) for x in ab[0])
+    g = np.asarray(given, dtype=np.float64).ravel()
+    assert g.size == n
+    Tc = np.zeros((n, m, N))
+    Tc[:, :, 0] = Bm
+    x = np.zeros((N, n))
+    for t in range(n):
+        x[0] = x[0] + Am[:, t] * g[t]
+    pw, have = Am.copy(), 1
+    while have < N:
+        cnt = min(have, N - have)
+        Xn, xn, pn = np.zeros((n, m, cnt)), np.zeros((cnt, n)), np.zeros((n, n))
+        for t in range(n):
+            Xn = Xn + pw[:, t, None, None] * Tc[t, None, :, :cnt]
+            xn = xn + x[:cnt, t, None] * pw[None, :, t]
+            pn = pn + pw[:, t, None] * pw[t, None, :]
+        Tc[:, :, have:have + cnt] = Xn
+        x[have:have + cnt] = xn
+        if have + cnt < N:
+            pw = pn
+        have += cnt
+    K = int(it[H["T_SCAN"]])
+    gt = _section(it, "OFF_T_SCAN_GT", K * P.T_SCAN_GT_WORDS).reshape(K, P.T_SCAN_GT_WORDS)
+    gc = dt[it[H["T_DOFF_SCAN_GC"]]:it[H["T_DOFF_SCAN_GC"]] + K]
+    d = np.zeros(int(it[H["RTOT"]]))
+    for k_ in range(K):
+        d[gt[k_, 3]:gt[k_, 3] + N] = gc[k_] * x[:, gt[k_, 0] // (m * N)]
+    return Tc.ravel(), x, d
+
+
+def run_scan(plan, given, params=None, ab=None, fused=None, with_ref=True):
     """P, q, G, h of one instance as the tiled kernel's *scan form* computes them (csrc/tiled.hip
     toeplitz_scan_kernel, plan_tables.h T_SCAN*): the Hessian block of two input column blocks by
     the recurrence P[(j,l)][(j',l')] = C + P[(j,l+1)][(j',l'+1)] with the rank-K term C from the
     LAST rows of the states, rows of G straight out of the group's Toeplitz table, the gradient by
     correlating the table with s (d - aim), everything else (d, h, the diagonal terms, the rows of G
-    that are no single state row) as the other forms do."""
+    that are no single state row) as the other forms do.  ``fused`` (default: the plan's H_T_SCAN_FUSED, the
+    route MPCASM_OPT_PATH 0 takes): the table and d by the kernel's own doubling (:func:`fused_setup`) instead of
+    the pre-passes' recurrence, and h from that d.  ``with_ref`` False (fused only): without run_tiled's
+    restatement of the other forms under ``"ref"``."""
     it, dt = plan.itab, plan.dtab
     K = int(it[H["T_SCAN"]])
     assert K > 0, "the plan has no scan form"
     ng, no, nc = plan.ng, plan.no, plan.nc
     params = plan.params if params is None else np.asarray(params, dtype=float)
     prm0 = np.append(params, 0.0)
-    ref = run_tiled(plan, given, params=params, ab=ab)            # d, and what must come out
-    d = ref["d"]
+    fused = bool(it[H["T_SCAN_FUSED"]]) if fused is None else bool(fused)
+    assert with_ref or fused
+    ref = run_tiled(plan, given, params=params, ab=ab) if with_ref else None   # d, and what must come out
     lti = _section(it, "OFF_T_LTI", P.T_LTI_WORDS)
     n, m, N = int(lti[0]), int(lti[1]), int(lti[2])
     ids = _section(it, "OFF_T_LTI_IDS", lti[3] + m + 1)[lti[3]:]
-    tb = _tiled_streams(plan, [s.array for s in plan.sources], ab)[ids[0]]
-    assert tb.size == n * m * 2 * N
-    tb = np.ascontiguousarray(tb.reshape(n * m, 2 * N)[:, N:]).ravel()     # Tc: without the zero halves
+    if fused:
+        tb, _, d = fused_setup(plan, given, ab)
+        rr = _section(it, "OFF_RS_RR", nc * P.RS_RR_WORDS).reshape(nc, P.RS_RR_WORDS)
+        grow_d = _section(it, "OFF_T_GROW", nc * P.RS_AXMAX).reshape(nc, P.RS_AXMAX)
+        h = np.zeros(nc)
+        for R in range(nc):
+            x = rr[R]
+            ac = ad = 0.0
+            for ax in range(x[12]):
+                ac += prm0[x[4 + ax]] * prm0[x[8 + ax]]
+                ad += prm0[x[4 + ax]] * d[grow_d[R, ax]]
+            h[R] = (prm0[x[13]] + ac) - ad
+    else:
+        d, h = ref["d"], ref["h"]
+        tb = _tiled_streams(plan, [s.array for s in plan.sources], ab)[ids[0]]
+        assert tb.size == n * m * 2 * N
+        tb = np.ascontiguousarray(tb.reshape(n * m, 2 * N)[:, N:]).ravel()     # Tc: without the zero halves
 
     def at(i):                       # Tc[i], 0 where the window leaves the row towards negative steps
         return tb[np.maximum(i, 0)]
@@ -750,7 +809,7 @@ def run_scan(plan, given, params=None, ab=None):
             k = grow[R, 0] % N                           # (the row's step: columns l > k hold zeros)
             G[R, blk[bx, 0]:blk[bx, 0] + N] = prm0[grow[R, 1]] * (
                 gcoef[R] * np.where(lane <= k, at(grow[R, 0] + blk[bx, 1] - lane), 0.0))
-    return {"P": Pm, "q": q, "G": G, "h": ref["h"], "ref": ref}
+    return {"P": Pm, "q": q, "G": G, "h": h, "ref": ref}
 
 
 def run_sweep(plan, given, A_steps, B_steps, params=None):

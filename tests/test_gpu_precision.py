@@ -11,7 +11,9 @@ import pytest
 
 from helpers import (LD, assert_componentwise, cancellation_free_plants, kappa, lti_tracking_problem,
                      precise_reference)
+import tiled_cases as tc
 from mpcasm import problems
+from mpcasm.plan import _H
 from oracle import qp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -170,27 +172,41 @@ TILED = [
     (5, 3, 48, 1.3, dict(scaled=True), 70), (5, 3, 48, 1.3, dict(extra_unknown=True), 70),
     (5, 4, 48, 1.3, dict(given_input=True), 70),        # (one input given: 4 inputs keep no >= 128, the tiled kernel's)
     (5, 3, 48, 1.3, dict(two_axis_limit=True), 70),
+    # the only shape here whose plan has T_SCAN_FUSED (tiled_cases.py's builder: no row but the costs' own): on the
+    # others "scan" and "scan-prepass" are one and the same launch
+    (8, 4, 32, 1.3, dict(fused=True), 70),
 ]
 
 
 @pytest.mark.parametrize("path", [0, 1, 4, 3], ids=["scan", "scan-prepass", "toeplitz", "general"])
 @pytest.mark.parametrize("nx,nu,N,rho,kw,B", TILED,
-                         ids=["5-3-48", "c4-shape", "4-2-100", "scaled", "extra-unknown", "given-input", "two-axis-limit"])
+                         ids=["5-3-48", "c4-shape", "4-2-100", "scaled", "extra-unknown", "given-input", "two-axis-limit",
+                              "fused-8-4-32"])
 def test_tiled(gpu_api, torch_gpu, nx, nu, N, rho, kw, B, path):
     torch = torch_gpu
     from mpcasm import capi, engine
 
     rng = np.random.default_rng(nx * 1000 + N + len(kw))
     A, Bm = cancellation_free_plants(rng, B, nx, nu, rho, N)
-    form, _, _ = lti_tracking_problem(gpu_api, rng, nx, nu, N, plant=(A[0], Bm[0]), **kw)
+    if kw.get("fused"):
+        form = tc.build(gpu_api, rng, tc.Shape("fused", "fused", nx, nu, N, nx, ()), (A[0], Bm[0]))
+    else:
+        form, _, _ = lti_tracking_problem(gpu_api, rng, nx, nu, N, plant=(A[0], Bm[0]), **kw)
     given = rng.normal(0, 0.3, [B, form.given_len])
     asm = engine.Assembler(form, batch=B, lti=["plant"])
     asm.set_option(capi.OPT_PATH, path)
+    # the set-up fused into the scan kernel only where the plan allows it and the path option is 0
+    fused = int(asm.plan.itab[_H["T_SCAN_FUSED"]])
+    assert fused == (1 if kw.get("fused") else 0)
     asm.bind_lti("plant", torch.as_tensor(A, device="cuda"), torch.as_tensor(Bm, device="cuda"))
     out = asm.assemble(torch.as_tensor(given, device="cuda"), out=_nan_out(torch, asm))
     kernel = asm.last_kernel()
     assert "tiled" in kernel, kernel
     assert ("scan" in kernel) == (path in (0, 1) and N <= 64), kernel
+    route = asm.tiled_route()
+    assert route.form == {0: capi.TILED_SCAN if N <= 64 else capi.TILED_TOEPLITZ, 1: capi.TILED_SCAN if N <= 64
+                          else capi.TILED_TOEPLITZ, 4: capi.TILED_TOEPLITZ, 3: capi.TILED_GENERAL}[path], route
+    assert route.fused == (1 if fused and path == 0 else 0), route
     res = dict(zip("PqGh", (t.cpu().numpy() for t in out)))
     kap, worst = kappa(N, nx), 0.0
     for b in _samples(B, few=nx == 12):

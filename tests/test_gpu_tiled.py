@@ -167,6 +167,9 @@ def test_horizon_tables_from_the_systems_own_matrices(gpu_api, torch_gpu, nx, nu
     assert "tiled" in lti.last_kernel()
     assert ("scan" in lti.last_kernel()) == (path in (0, 1) and N <= 64), lti.last_kernel()
     assert lti.plan.itab[_H["T_SCAN_FUSED"]] == (1 if N <= 64 else 0)      # (path 0: the kernel makes its own table and d; 1: pre-passes)
+    route = lti.tiled_route()
+    assert route.fused == (1 if N <= 64 and path == 0 else 0), route          # ("scan" and "scan with pre-passes" are two launches)
+    assert (route.form == capi.TILED_SCAN) == (path in (0, 1) and N <= 64), route
     # one half at a time: the same numbers
     P2, q2, _, _ = lti.assemble(given, want_constraints=False)
     assert torch.equal(P2, Pl) and torch.equal(q2, ql)
@@ -232,6 +235,10 @@ def test_scan_form_against_the_toeplitz_form_and_the_oracle(gpu_api, torch_gpu, 
         scan = asm.plan.itab[_H["T_SCAN"]] > 0
         assert scan == (not kw.get("scheduled_cost"))
         assert ("scan" in asm.last_kernel()) == (scan and path == 0), asm.last_kernel()
+        # (helpers.lti_tracking_problem's scheduled limit adds workspace rows: no plan here has the set-up fused, the
+        # scan form runs behind the pre-passes; the fused route: test_gpu_tiled_variants.py)
+        assert asm.plan.itab[_H["T_SCAN_FUSED"]] == 0 and asm.tiled_route().fused == 0
+        assert asm.tiled_route().form == (capi.TILED_SCAN if scan and path == 0 else capi.TILED_TOEPLITZ)
         if path == 0:
             P2, q2, _, _ = asm.assemble(given, want_constraints=False)
             assert torch.equal(P2, results[0][0]) and torch.equal(q2, results[0][1])
