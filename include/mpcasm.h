@@ -509,6 +509,50 @@ int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, c
  * MPCASM_ERR_LIMIT beyond the size limit of mpcasm_qp_solve_wide (the other outputs still written). */
 int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
 
+/* Per-instance outcome of mpcasm_qp_polish, written to d_polish on the device. */
+enum {
+  MPCASM_POLISH_DONE = 1,      /* the polished point replaced the iterate                                  */
+  MPCASM_POLISH_SKIPPED = 0,   /* not a solved instance, or more active rows than unknowns: nothing written */
+  MPCASM_POLISH_REJECTED = -1  /* a pivot not positive, or the polished point is not the better one          */
+};
+
+/* Solution polishing, the step OSQP takes after its iteration has stopped -- what
+ *   self.optim = osqp_solve_qp(P=Q, q=q, G=A, h=h)      biped_mpc_loop.py:60
+ * does with polishing on (Stellato et al. 2020, section 4 "Solution polishing") -- for a batch of iterates of
+ * mpcasm_qp_solve (which itself does not polish): the same operands in the same layouts, every instance on its
+ * own, nothing read back, the call can be captured in a graph.  Per instance b, in order:
+ *   skipped    d_status != NULL and d_status[b] != MPCASM_QP_SOLVED (the instance is not read: NON_CVX holds
+ *              NaN), or the guessed active set has na > no rows: d_polish[b] = MPCASM_POLISH_SKIPPED and
+ *              x, y, z, d_res[b] are not written
+ *   active set row i iff h_i - z_i < y_i (OSQP's test with l = -inf, u = h); G_A, h_A the na active rows
+ *   solve      K = [[P, G_A'], [G_A, 0]], g = [-q; h_A], dK = diag(delta I_no, -delta I_na):
+ *              t = (K + dK)^-1 g, then refine_iters times t += (K + dK)^-1 (g - K t), the residual from K as it
+ *              is, with P and G as given.  OSQP's defaults: delta = 1e-6, refine_iters = 3.  Block elimination
+ *              with two Cholesky factorisations, P + delta I = L L' and G_A (P + delta I)^-1 G_A' + delta I; a
+ *              pivot that is not positive: MPCASM_POLISH_REJECTED
+ *   point      x^ = t[:no]; y^ = t[no:] on the active rows, 0 elsewhere; z^ = min(G x^, h)
+ *   accept     with r_p = |Gx - z|, r_d = |Px + q + G'y| of the iterate passed in (computed here) and r^_p, r^_d
+ *              of the polished point, infinity norms: OSQP's rule
+ *                (r^_p < r_p and r^_d < r_d) or (r^_p < r_p and r_d < 1e-10) or (r^_d < r_d and r_p < 1e-10)
+ *              AND every y^_i >= 0 -- a departure from OSQP, whose rule does not see a multiplier's sign
+ *              (DESIGN.md).  Accepted: x, y, z <- x^, y^, z^, d_res[b] = (r^_p, r^_d), MPCASM_POLISH_DONE.
+ *              Otherwise MPCASM_POLISH_REJECTED and x, y, z, d_res[b] keep their bits; a NaN anywhere fails
+ *              every comparison.
+ * d_status (may be NULL: every instance is polished) [batch] int32, mpcasm_qp_solve's; d_polish [batch] int32;
+ * d_res (may be NULL) [batch][2].
+ * Size limit: one instance takes 4 no (no | 1) + 13 no + 4 nc + 16 + ceil(no / 2) doubles of LDS (four
+ * matrices -- P + delta I and its factor, the factor's inverse, G_A, the Schur complement -- the vectors and
+ * the partial sums), rounded up to even; MPCASM_ERR_LIMIT, nothing launched, beyond 156 KB: the biped up to
+ * N = 24 and (65, 70) fit, C3 does not.  MPCASM_ERR_ARG, before any device call: delta not finite or <= 0,
+ * refine_iters < 0, batch < 0, no < 1, nc < 0, a null d_P, d_q, d_x, d_polish (with nc > 0: d_G, d_h, d_y,
+ * d_z).  batch == 0: MPCASM_OK. */
+int mpcasm_qp_polish(int no, int nc, const double* d_P, const double* d_q, const double* d_G, const double* d_h,
+                     double* d_x, double* d_y, double* d_z, const int32_t* d_status, double delta,
+                     int refine_iters, int32_t* d_polish, double* d_res, int batch, void* stream);
+/* Needs no device: the LDS bytes one instance of mpcasm_qp_polish takes (*out; MPCASM_ERR_LIMIT too when that
+ * exceeds what a workgroup may have). */
+int mpcasm_qp_polish_lds_bytes(int no, int nc, int64_t* out);
+
 /* f2 + the loop  the next tick's `given` from a solution ------------------------------------------------
  * Replaces, for a batch of walkers, the end of every tick of the walking loop
  *   preview_all + update_given_collector       biped_mpc_loop.py:62-65, 81-92

@@ -1854,6 +1854,28 @@ int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_
   return qp_solve_wide_info(no, nc, lds_bytes, kinv_on_chip);
 }
 
+int mpcasm_qp_polish(int no, int nc, const double* d_P, const double* d_q, const double* d_G, const double* d_h,
+                     double* d_x, double* d_y, double* d_z, const int32_t* d_status, double delta,
+                     int refine_iters, int32_t* d_polish, double* d_res, int batch, void* stream) {
+  if (no < 1 || nc < 0 || batch < 0 || refine_iters < 0 || !(delta > 0.0) || !std::isfinite(delta) ||
+      no > (1 << 12) || nc > (1 << 16))
+    return MPCASM_ERR_ARG;
+  if (batch == 0) return MPCASM_OK;
+  if (!d_P || !d_q || !d_x || !d_polish || (nc > 0 && (!d_G || !d_h || !d_y || !d_z))) return MPCASM_ERR_ARG;
+  if (polish_lds_bytes(no, nc) > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
+  hipError_t err;
+  const int rc = launch_qp_polish(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, d_status, delta, refine_iters,
+                                  d_polish, d_res, batch, static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
+int mpcasm_qp_polish_lds_bytes(int no, int nc, int64_t* out) {
+  if (no < 1 || nc < 0 || no > (1 << 12) || nc > (1 << 16) || !out) return MPCASM_ERR_ARG;
+  *out = (int64_t)polish_lds_bytes(no, nc);
+  return *out > RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
+}
+
 int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_index, int nnz,
                   double* d_dst, int batch, void* stream) {
   if (nnz < 0 || batch < 0 || src_stride < 0) return MPCASM_ERR_ARG;

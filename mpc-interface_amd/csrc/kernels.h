@@ -154,6 +154,11 @@ int launch_qp_solve_wide(int no, int nc, const double* P, const double* q, const
                          double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
                          int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
                          int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err);
+// polish.hip: OSQP's polishing of solved instances (active-set KKT solve with refinement)
+size_t polish_lds_bytes(int no, int nc);
+int launch_qp_polish(int no, int nc, const double* P, const double* q, const double* G, const double* h,
+                     double* x, double* y, double* z, const int32_t* status, double delta, int refine_iters,
+                     int32_t* polish, double* res, int batch, hipStream_t stream, hipError_t* err);
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err);
 

@@ -39,6 +39,9 @@ QP_STATUS = {
     -4: "MPCASM_QP_DUAL_INFEASIBLE",
     -7: "MPCASM_QP_NON_CVX",
 }
+# per-instance outcomes of mpcasm_qp_polish
+POLISH_DONE, POLISH_SKIPPED, POLISH_REJECTED = 1, 0, -1
+POLISH_STATUS = {1: "MPCASM_POLISH_DONE", 0: "MPCASM_POLISH_SKIPPED", -1: "MPCASM_POLISH_REJECTED"}
 ROLL_GIVEN, ROLL_OPTIM, ROLL_STATE, ROLL_REC_WORDS = 0, 1, 2, 8   # records of mpcasm_ltv_rollout_compile
 ERR_ARG = -1
 GIVEN_KEEP, GIVEN_CONST = -1, -2     # given-map records of mpcasm_given_map_compile (a row: its index >= 0)
@@ -118,6 +121,10 @@ SIGNATURES = {
                              [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_qp_solve_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                                  ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_qp_polish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 + [ctypes.c_double, ctypes.c_int,
+                                                                                       _void_p, _void_p, ctypes.c_int,
+                                                                                       _void_p]),
+    "mpcasm_qp_polish_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,

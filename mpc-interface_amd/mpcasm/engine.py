@@ -162,12 +162,25 @@ def admm(P, q, G, h, x=None, y=None, z=None, iters=50, rho=OSQP_RHO, sigma=OSQP_
 
 QP_SOLVED, QP_MAX_ITER, QP_PRIMAL_INFEASIBLE, QP_DUAL_INFEASIBLE, QP_NON_CVX = (
     capi.QP_SOLVED, capi.QP_MAX_ITER, capi.QP_PRIMAL_INFEASIBLE, capi.QP_DUAL_INFEASIBLE, capi.QP_NON_CVX)
-QpSolution = collections.namedtuple("QpSolution", "x y z status iters res rho")
+POLISH_DONE, POLISH_SKIPPED, POLISH_REJECTED = capi.POLISH_DONE, capi.POLISH_SKIPPED, capi.POLISH_REJECTED
+OSQP_DELTA, OSQP_POLISH_REFINE = 1e-6, 3              # OSQP's defaults for the polishing step
+
+
+class QpSolution(collections.namedtuple("QpSolution", "x y z status iters res rho")):
+    """What :func:`solve_qp` returns; ``polish`` is None: nothing was polished."""
+    __slots__ = ()
+    polish = None
+
+
+class PolishedQpSolution(collections.namedtuple("QpSolution", "x y z status iters res rho polish")):
+    """:class:`QpSolution` of ``solve_qp(..., polish=True)``: a trailing field ``polish``, the ``(B,)`` int32 verdicts
+    ``POLISH_*`` of :func:`polish_qp`."""
+    __slots__ = ()
 
 
 def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
              eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None):
+             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False):
     """A batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h`` solved to tolerance on the device
     (``mpcasm_qp_solve``): :func:`admm`'s iteration with OSQP's termination tests and adaptive rho, every
     instance stopping on its own, nothing read back to the host (a tick can be captured in a graph).
@@ -180,9 +193,68 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
     the primal and dual residuals of the returned iterate.
     ``out``: for a COLD start, the caller's ``(x, y, z, status, iters, res)`` to write instead of new tensors
     (``(B, no)``, ``(B, nc)``, ``(B, nc)``, ``(B,)`` int32 twice, ``(B, 2)``: a loop that replays a graph keeps
-    them at fixed addresses); ``x, y, z`` are not read."""
-    return _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
-                     max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out)
+    them at fixed addresses); ``x, y, z`` are not read.
+    ``polish``: :func:`polish_qp` with OSQP's defaults after the solve, on the solved instances; ``x, y, z`` and
+    ``res`` of an instance whose polished point is accepted are that point's, and the solution grows a trailing field
+    ``polish``, the ``(B,)`` int32 verdicts ``POLISH_*`` (a :class:`PolishedQpSolution`; without polish ``sol.polish``
+    is None and the solution has the seven fields it always had)."""
+    sol = _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
+                    max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out)
+    if not polish:
+        return sol
+    verdict = polish_qp(P, q, G, h, sol, status=sol.status, stream=stream)[3]
+    return PolishedQpSolution(*sol, verdict)
+
+
+def polish_qp(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE, stream=None,
+              out=None):
+    """OSQP's solution polishing on a batch of iterates (``mpcasm_qp_polish``): per instance, the active set
+    guessed from the iterate (row ``i`` iff ``h_i - z_i < y_i``), the KKT system of the equality-constrained QP
+    on it solved with the regularisation ``delta`` and ``refine_iters`` steps of iterative refinement, and the
+    result kept when OSQP's rule calls it the better point and no multiplier is negative.
+    ``sol_or_xyz``: a :class:`QpSolution` or ``(x, y, z)`` -- device tensors, updated IN PLACE where a polished
+    point is accepted, untouched elsewhere.  ``status``: ``(B,)`` int32, only ``QP_SOLVED`` instances are
+    polished (None: every instance).  Returns ``(x, y, z, polish, res)``: ``polish`` ``(B,)`` int32
+    (``POLISH_DONE`` / ``POLISH_SKIPPED`` / ``POLISH_REJECTED``) and ``res`` ``(B, 2)``, written for accepted
+    instances only.  ``res`` is the solution's own when one is passed (else a new tensor of NaN).
+    ``out``: the caller's ``(polish, res)`` to write instead (fixed addresses for a replayed graph)."""
+    torch = require_device()
+    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
+        x, y, z, res = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z, sol_or_xyz.res
+    else:
+        (x, y, z), res = sol_or_xyz, None
+    if x is None or y is None or z is None:
+        raise ValueError("polish_qp takes the iterates x, y and z")
+    batch, no, nc, _warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, None, False)
+    verdict = None
+    if out is not None:
+        verdict, res = out
+    if verdict is None:
+        verdict = torch.empty((batch,), dtype=torch.int32, device=P.device)
+    if res is None:
+        res = torch.full((batch, 2), float("nan"), dtype=torch.float64, device=P.device)
+    for t, dtype, shape in ((verdict, torch.int32, (batch,)), (res, torch.float64, (batch, 2))) + \
+            (((status, torch.int32, (batch,)),) if status is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
+                and tuple(t.shape) == shape):
+            raise ValueError("status, polish (B,) int32 and res (B, 2) float64: contiguous, on P's device")
+    with torch.cuda.device(P.device):
+        rc = capi.load().mpcasm_qp_polish(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
+                                          x.data_ptr(), y.data_ptr(), z.data_ptr(),
+                                          status.data_ptr() if status is not None else None, float(delta),
+                                          int(refine_iters), verdict.data_ptr(), res.data_ptr(), batch,
+                                          _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_qp_polish")
+    return x, y, z, verdict, res
+
+
+def qp_polish_lds_bytes(no, nc):
+    """LDS bytes one instance of :func:`polish_qp` takes; ``MpcasmError`` with ``ERR_LIMIT`` when that is more
+    than a workgroup may have (``mpcasm_qp_polish_lds_bytes``)."""
+    out = ctypes.c_int64()
+    rc = capi.load().mpcasm_qp_polish_lds_bytes(int(no), int(nc), ctypes.byref(out))
+    capi.check(rc, "mpcasm_qp_polish_lds_bytes")
+    return int(out.value)
 
 
 def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,

@@ -96,15 +96,20 @@ class WalkerFleet:
       * ``"hold"`` (default): only SOLVED and MAX_ITER solutions are applied; any other walker keeps its
         ``given`` for that tick and tries again at the next one, its clock advancing as ever;
       * ``"apply"``: every solution is applied except NON_CVX, whose iterates are NaN.
+    ``polish``: :meth:`step` polishes every solved QP (:func:`mpcasm.engine.polish_qp`) between the solve and the
+    next ``given``; off by default.
     """
 
     def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False,
-                 on_unsolved="hold"):
+                 on_unsolved="hold", polish=False):
         from .engine import APPLY_ALL, APPLY_SOLVED, Assembler, require_device
 
         if on_unsolved not in ("hold", "apply"):
             raise ValueError("on_unsolved: 'hold' or 'apply', got %r" % (on_unsolved,))
         self.on_unsolved = on_unsolved
+        # polish=True: every solved QP is polished (engine.polish_qp, OSQP's defaults) before its solution
+        # becomes the walker's next `given`
+        self._polish = bool(polish)
         self._apply_mask = APPLY_SOLVED if on_unsolved == "hold" else APPLY_ALL
         self._step_graphs = {}
         self._torch = require_device()
@@ -293,7 +298,7 @@ class WalkerFleet:
     def _closed_bucket(self, item, entry, stream):
         """After a bucket's assembly, on its stream: a cold solve with OSQP's defaults into the bucket's own
         solver buffers, then its walkers' next ``given`` from the solution, by the fleet's rule."""
-        from .engine import OSQP_RHO, solve_qp
+        from .engine import OSQP_RHO, polish_qp, solve_qp
 
         bucket = self.buckets[item["p"]]
         asm, n = bucket["asm"], item["idx"].size
@@ -307,16 +312,24 @@ class WalkerFleet:
                                      iters=torch.zeros(B, **i32), res=torch.zeros((B, 2), **f),
                                      rho=torch.full((B,), OSQP_RHO, **f))
             bucket["gmap"] = asm.given_map(biped_given_rules(bucket["form"]))
+            if self._polish:
+                qp["polish"] = torch.zeros(B, **i32)
         cur = self._torch.cuda.current_stream(asm.device) if stream is None else stream
         with self._torch.cuda.stream(cur):
             rho = qp["rho"][:n]
             rho.fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
             sol = solve_qp(entry["P"], entry["q"], entry["G"], entry["h"], rho=rho, stream=stream,
                            out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")))
+            if self._polish:
+                polish_qp(entry["P"], entry["q"], entry["G"], entry["h"], sol, status=sol.status, stream=stream,
+                          out=(qp["polish"][:n], sol.res))
             asm.next_given(self.given_buffer(), sol.x, bucket["gmap"], index=item["index"], status=sol.status,
                            apply_mask=self._apply_mask, count=n, stream=stream)
-        return {"p": item["p"], "index": item["index"], "index_long": item["index_long"], "x": sol.x,
-                "status": sol.status, "iters": sol.iters}
+        out = {"p": item["p"], "index": item["index"], "index_long": item["index_long"], "x": sol.x,
+               "status": sol.status, "iters": sol.iters}
+        if self._polish:
+            out["polish"] = qp["polish"][:n]
+        return out
 
     def step(self):
         """One closed tick of the walking loop on :meth:`given_buffer` (biped_mpc_loop.py:50-95 for every
@@ -324,7 +337,7 @@ class WalkerFleet:
         with OSQP's defaults, and :meth:`~mpcasm.engine.Assembler.next_given` by the fleet's
         ``on_unsolved`` rule; then the clocks advance.  Nothing is read back: returns per bucket
         ``{"p", "index": walker ids, "x", "status", "iters"}`` (device tensors in the bucket's own buffers,
-        valid until the next step).  With ``graphs``, each place of the step cycle runs its whole closed
+        valid until the next step; with ``polish`` also ``"polish"``, the verdicts of the polishing step).  With ``graphs``, each place of the step cycle runs its whole closed
         tick as one graph (captured the first time the place comes round, after running it as it is)."""
         torch = self._torch
         given = self.given_buffer()
