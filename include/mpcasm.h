@@ -336,6 +336,28 @@ int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_d
  * that does not run on the sweep kernel. */
 int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int32_t out[8]);
 
+/* Diagnostic, needs no device: what mpcasm_fill_su launches for `batch` systems of these sizes (ltv: 0 / 1) when
+ * d_S and d_U are both 16-byte aligned (aligned16 = 1) or not (0: the QUAD and LTV_ROW kernels and the LTI
+ * kernel's PAD form are passed over; the kernels that take the launch instead still store 16-byte words where
+ * N n is even, at addresses that are then only 8-byte aligned).  The launch takes the decision from the same function, MPCASM_FILL_MIN_WAVES (read once per
+ * process) included.  out[0]: the kernel, MPCASM_FILL_*; out[1]: its integer template argument -- NS, the
+ * number of states as a constant, for QUAD, LTV_ROW and LTV_BLOCK (there 0 = any), TPI, the threads per system
+ * (64 or 256), for LTI and LTV, 0 otherwise; out[2]: flags, MPCASM_FILL_GENERIC | MPCASM_FILL_PAD (the LTI
+ * kernel's template arguments) | MPCASM_FILL_WHOLE_LINES (QUAD: rows of U are whole 128-byte lines and leave
+ * with nontemporal stores); out[3]: systems per wavefront (QUAD, TINY; else 0); out[4]: QUAD: log2 of the
+ * lanes that share a short row (rows per store instruction = 64 >> out[4]); out[5]: workgroups; out[6]:
+ * dynamic LDS bytes of a workgroup; out[7]: 1 when that is more than 64 KB.  MPCASM_ERR_LIMIT exactly where
+ * the launch returns it (out is zeroed): one system's tables beyond a CU's LDS, or per-step systems of more
+ * than 256 states.  MPCASM_ERR_ARG as mpcasm_fill_su (batch < 1 here: an empty batch launches nothing). */
+enum { MPCASM_FILL_QUAD = 1 /* n <= 4: recurrence in registers, several systems per wavefront */,
+       MPCASM_FILL_TINY = 2 /* n (m + n) <= 32: several systems per wavefront, recurrence in LDS */,
+       MPCASM_FILL_LTI = 3, MPCASM_FILL_LTV_ROW = 4 /* per-step, n <= 4: a wavefront per system */,
+       MPCASM_FILL_LTV_BLOCK = 5 /* per-step, a workgroup per system, every step's matrices in LDS */,
+       MPCASM_FILL_LTV_WAVE = 6 /* per-step, a wavefront per system, step matrices fetched a step ahead */,
+       MPCASM_FILL_LTV = 7 };
+enum { MPCASM_FILL_GENERIC = 1, MPCASM_FILL_PAD = 2, MPCASM_FILL_WHOLE_LINES = 4 };
+int mpcasm_fill_route(int batch, int N, int n, int m, int ltv, int aligned16, int32_t out[8]);
+
 /* Diagnostic, needs no device: what mpcasm_assemble launches for the tables of a plan that runs on the tiled
  * path (128 unknowns or more, not on chip, no dynamics compiled as ltv; tables validated as mpcasm_plan_create
  * does), for a launch of `batch` instances whose sources have the strides h_src_stride (as for mpcasm_assemble:

@@ -1184,6 +1184,26 @@ int mpcasm_fill_su(const double* d_A, const double* d_B, double* d_S, double* d_
   return rc;
 }
 
+int mpcasm_fill_route(int batch, int N, int n, int m, int ltv, int aligned16, int32_t out[8]) {
+  if (!out) return MPCASM_ERR_ARG;
+  memset(out, 0, 8 * sizeof(int32_t));
+  if (batch < 1 || N < 1 || n < 1 || m < 1 || (ltv != 0 && ltv != 1) || (aligned16 != 0 && aligned16 != 1))
+    return MPCASM_ERR_ARG;
+  FillChoice c;
+  const int rc = fill_choose(batch, N, n, m, ltv, aligned16 != 0, &c);
+  if (rc != MPCASM_OK) return rc;
+  out[0] = c.kernel;
+  out[1] = c.arg;
+  out[2] = (c.generic ? MPCASM_FILL_GENERIC : 0) | (c.pad ? MPCASM_FILL_PAD : 0) |
+           (c.whole_lines ? MPCASM_FILL_WHOLE_LINES : 0);
+  out[3] = c.spw;
+  out[4] = c.lshift;
+  out[5] = c.grid;
+  out[6] = (int32_t)c.lds;
+  out[7] = c.lds > 64 * 1024;
+  return MPCASM_OK;
+}
+
 int mpcasm_plan_create(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                        mpcasm_plan** out_plan) {
   if (!h_itab || !out_plan || (n_dtab && !h_dtab)) return MPCASM_ERR_ARG;

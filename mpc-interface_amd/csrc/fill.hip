@@ -561,18 +561,17 @@ __global__ __launch_bounds__(BLOCK) void fill_ltv_block_kernel(const double* __r
 // LTV, one wavefront per system (n <= 64, N n <= 1024): no workgroup barrier -- the
 // wavefront double-buffers the block row AND the step matrices in its own LDS slice,
 // loads (A_{k+1}, B_{k+1}) into registers while row k is being produced, and needs one
-// wave-level LDS sync per step.
-// ALL: every step's (A_k, B_k) of the system sits in LDS from the start (one wait, before the
-// first store); otherwise two slots, refilled from HBM a step ahead.  A wavefront that must
-// wait for a load while its row stores are in flight waits for the stores too (one vmcnt
-// counts both), i.e. one HBM write round trip per step: ALL is several times faster whenever
-// the N (n^2 + n m) doubles fit.
-__host__ __device__ inline size_t ltv_wave_lds_doubles(int N, int n, int m, bool all = false) {
+// wave-level LDS sync per step.  Two slots of step matrices, refilled from HBM a step ahead: a
+// wavefront that must wait for a load while its row stores are in flight waits for the stores
+// too (one vmcnt counts both), i.e. one HBM write round trip per step.  (Keeping every step's
+// (A_k, B_k) in LDS instead avoids that, and is what fill_ltv_block_kernel does: four
+// wavefronts' worth of it fits 80 KB exactly when one system's fits the block kernel's 20 KB,
+// so this kernel only ever sees the systems whose step matrices do not fit.)
+__host__ __device__ inline size_t ltv_wave_lds_doubles(int N, int n, int m) {
   return 2 * even_up((size_t)m * N * n) + 2 * even_up((size_t)n * n) +
-         (all ? (size_t)N : 2) * (even_up((size_t)n * n) + even_up((size_t)n * m));
+         2 * (even_up((size_t)n * n) + even_up((size_t)n * m));
 }
 
-template <bool ALL>
 __global__ __launch_bounds__(BLOCK) void fill_ltv_wave_kernel(const double* __restrict__ A,
                                                               const double* __restrict__ B,
                                                               double* __restrict__ S,
@@ -586,7 +585,7 @@ __global__ __launch_bounds__(BLOCK) void fill_ltv_wave_kernel(const double* __re
   const int rl = N * n, nn = n * n, nm = n * m;
   const size_t rstep = even_up((size_t)m * rl), pstep = even_up((size_t)nn);
   const size_t abstep = even_up((size_t)nn) + even_up((size_t)nm);
-  double* Rw = lds + (size_t)wave * ltv_wave_lds_doubles(N, n, m, ALL);  // [2][m][rl]
+  double* Rw = lds + (size_t)wave * ltv_wave_lds_doubles(N, n, m);  // [2][m][rl]
   double* Pk = Rw + 2 * rstep;                                      // [2][n][n] as [j][i]
   double* AB = Pk + 2 * pstep;                                      // [2]{A_k [n][n], B_k [n][m]}
 
@@ -602,18 +601,9 @@ __global__ __launch_bounds__(BLOCK) void fill_ltv_wave_kernel(const double* __re
 
   // both row buffers start as zeros: the blocks right of the diagonal are never written
   for (size_t e = lane; e < 2 * rstep; e += 64) Rw[e] = 0.0;
-  // step 0 matrices (ALL: those of every step)
-  {  // (flat, coalesced copies: the steps' matrices are contiguous in HBM)
-    const int na = (ALL ? N : 1) * nn, nb = (ALL ? N : 1) * nm;
-    for (int i = lane; i < na; i += 64) {
-      const int k = i / nn;
-      AB[k * abstep + (i - k * nn)] = Ab[i];
-    }
-    for (int i = lane; i < nb; i += 64) {
-      const int k = i / nm;
-      AB[k * abstep + even_up((size_t)nn) + (i - k * nm)] = Bb[i];
-    }
-  }
+  // step 0 matrices
+  for (int i = lane; i < nn; i += 64) AB[i] = Ab[i];
+  for (int i = lane; i < nm; i += 64) AB[even_up((size_t)nn) + i] = Bb[i];
   wave_lds_sync();
 
   auto stream_row = [&](const double* Rrow, int k) {
@@ -631,7 +621,7 @@ __global__ __launch_bounds__(BLOCK) void fill_ltv_wave_kernel(const double* __re
   };
 
   for (int k = 0; k < N; ++k) {
-    const double* Ak = AB + (ALL ? k : (k & 1)) * abstep;
+    const double* Ak = AB + (k & 1) * abstep;
     const double* Bk = Ak + even_up((size_t)nn);
     double* ABn = AB + ((k + 1) & 1) * abstep;
     const double* Rp = Rw + ((k + 1) & 1) * rstep;  // row k-1
@@ -642,7 +632,7 @@ __global__ __launch_bounds__(BLOCK) void fill_ltv_wave_kernel(const double* __re
     // next step's matrices leave HBM now (register staged; at most 2 + 1 values per lane
     // on the small shapes this kernel is dispatched for)
     double an[2] = {0.0, 0.0}, bn = 0.0;
-    const bool more = !ALL && k + 1 < N;
+    const bool more = k + 1 < N;
     if (more) {
       if (lane < nn) an[0] = Ab[(size_t)(k + 1) * nn + lane];
       if (lane + 64 < nn) an[1] = Ab[(size_t)(k + 1) * nn + lane + 64];
@@ -1035,35 +1025,41 @@ hipError_t allow_lds(K kernel, size_t bytes) {
   return allow_whole_lds(reinterpret_cast<const void*>(kernel));
 }
 
+// MPCASM_FILL_MIN_WAVES (tuning aid), read once per process: the route and the launch see the same value
+int fill_min_waves() {
+  static const int v = getenv("MPCASM_FILL_MIN_WAVES") ? atoi(getenv("MPCASM_FILL_MIN_WAVES")) : 8192;
+  return v;
+}
+
 }  // namespace
 
-int launch_fill_su(const double* A, const double* B, double* S, double* U, int batch, int N, int n,
-                   int m, int ltv, hipStream_t stream, hipError_t* err) {
-  *err = hipSuccess;
-  constexpr size_t LDS_MAX = 160 * 1024;
-  const bool aligned16 = (((uintptr_t)S | (uintptr_t)U) & 15) == 0;
+// the one decision, taken by launch_fill_su and reported by mpcasm_fill_route
+int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillChoice* out) {
+  *out = FillChoice{};
+  FillChoice c{};
+  constexpr size_t LDS_MAX = CU_LDS_BYTES;
   const bool pairs = ((N * n) & 1) == 0 && aligned16;   // rows of U are whole 16-byte words
+  const int by4 = (batch + 3) / 4;
   if (!ltv && n <= 4 && m + n <= 16 && pairs && ((N * n * n) & 1) == 0) {
     // few states: registers + DPP recurrence, constant-address write loop
     int spw = 16 / (m + n);
     while (spw > 1 && quad_lds_doubles(N, n, m, spw) * sizeof(double) > 40 * 1024) --spw;
     // (fewer systems per wavefront while the launch has fewer wavefronts than this: 8192 systems
     // as 8192 wavefronts of one reach 0.66 of HBM, as 2048 of four 0.59; tuning aid: the variable)
-    static const int SPW_MIN_WAVES = getenv("MPCASM_FILL_MIN_WAVES") ? atoi(getenv("MPCASM_FILL_MIN_WAVES")) : 8192;
-    while (spw > 1 && (batch + spw - 1) / spw < SPW_MIN_WAVES) --spw;
+    while (spw > 1 && (batch + spw - 1) / spw < fill_min_waves()) --spw;
     const size_t bytes = quad_lds_doubles(N, n, m, spw) * sizeof(double);
     if (bytes <= LDS_MAX) {
-      auto kernel = n == 1   ? fill_lti_quad_kernel<1>
-                    : n == 2 ? fill_lti_quad_kernel<2>
-                    : n == 3 ? fill_lti_quad_kernel<3>
-                             : fill_lti_quad_kernel<4>;
-      if ((*err = allow_lds(kernel, bytes)) != hipSuccess) return MPCASM_ERR_HIP;
       int lshift = 0;
       while (lshift < 6 && (1 << lshift) < (N * n) / 2) ++lshift;
-      hipLaunchKernelGGL(kernel, dim3((batch + spw - 1) / spw), dim3(64), bytes, stream, A, B, S, U,
-                         batch, N, m, spw, lshift, (N * n) % 16 == 0 ? 1 : 0);
-      *err = hipGetLastError();
-      return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+      c.kernel = MPCASM_FILL_QUAD;
+      c.arg = n;
+      c.spw = spw;
+      c.lshift = lshift;
+      c.whole_lines = (N * n) % 16 == 0 ? 1 : 0;
+      c.grid = (batch + spw - 1) / spw;
+      c.lds = bytes;
+      *out = c;
+      return MPCASM_OK;
     }
   }
   if (ltv && n <= 4 && n * m <= 64 && pairs) {
@@ -1072,13 +1068,12 @@ int launch_fill_su(const double* A, const double* B, double* S, double* U, int b
                           : n == 3 ? LtvRow<3>::lds_doubles(N, m)
                                    : LtvRow<4>::lds_doubles(N, m)) * sizeof(double);
     if (bytes <= 64 * 1024) {
-      auto kernel = n == 1   ? fill_ltv_row_kernel<1>
-                    : n == 2 ? fill_ltv_row_kernel<2>
-                    : n == 3 ? fill_ltv_row_kernel<3>
-                             : fill_ltv_row_kernel<4>;
-      hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), bytes, stream, A, B, S, U, N, m);
-      *err = hipGetLastError();
-      return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+      c.kernel = MPCASM_FILL_LTV_ROW;
+      c.arg = n;
+      c.grid = batch;
+      c.lds = bytes;
+      *out = c;
+      return MPCASM_OK;
     }
   }
   if (!ltv) {
@@ -1092,74 +1087,128 @@ int launch_fill_su(const double* A, const double* B, double* S, double* U, int b
     while (spw > 2 && (batch + 4 * spw - 1) / (4 * spw) < 512) --spw;
     const size_t tiny = tiny_lds_doubles(N, n, m) * sizeof(double) * 4 * (spw > 0 ? spw : 1);
     if (spw >= 2 && tiny <= 64 * 1024) {
-      const int per_block = 4 * spw;
-      const int blocks = (batch + per_block - 1) / per_block;
-      hipLaunchKernelGGL(fill_lti_tiny_kernel, dim3(blocks), dim3(BLOCK), tiny, stream, A, B, S, U,
-                         batch, N, n, m, spw);
+      c.kernel = MPCASM_FILL_TINY;
+      c.spw = spw;
+      c.grid = (batch + 4 * spw - 1) / (4 * spw);
+      c.lds = tiny;
     } else if (small) {
-      const size_t bytes = per * 4;
-      const int blocks = (batch + 3) / 4;
-      hipLaunchKernelGGL((fill_lti_kernel<64, false>), dim3(blocks), dim3(BLOCK), bytes, stream, A,
-                         B, S, U, batch, N, n, m);
+      c.kernel = MPCASM_FILL_LTI;
+      c.arg = 64;
+      c.grid = by4;
+      c.lds = per * 4;
     } else if (per > LDS_MAX) {
       return MPCASM_ERR_LIMIT;  // the A^d B table of one system must fit in LDS
-    } else if (xsz <= BLOCK * EPT) {
-      const size_t padded = per + (size_t)m * N * n * sizeof(double);
-      if (pairs && padded <= 78 * 1024) {  // (two workgroups still share a CU)
-        if ((*err = allow_lds(fill_lti_kernel<BLOCK, false, true>, padded)) != hipSuccess)
-          return MPCASM_ERR_HIP;
-        hipLaunchKernelGGL((fill_lti_kernel<BLOCK, false, true>), dim3(batch), dim3(BLOCK), padded,
-                           stream, A, B, S, U, batch, N, n, m);
-        *err = hipGetLastError();
-        return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
-      }
-      if ((*err = allow_lds(fill_lti_kernel<BLOCK, false>, per)) != hipSuccess)
-        return MPCASM_ERR_HIP;
-      hipLaunchKernelGGL((fill_lti_kernel<BLOCK, false>), dim3(batch), dim3(BLOCK), per, stream, A,
-                         B, S, U, batch, N, n, m);
     } else {
-      if ((*err = allow_lds(fill_lti_kernel<BLOCK, true>, per)) != hipSuccess)
-        return MPCASM_ERR_HIP;
-      hipLaunchKernelGGL((fill_lti_kernel<BLOCK, true>), dim3(batch), dim3(BLOCK), per, stream, A,
-                         B, S, U, batch, N, n, m);
+      c.kernel = MPCASM_FILL_LTI;
+      c.arg = BLOCK;
+      c.grid = batch;
+      c.lds = per;
+      if (xsz <= BLOCK * EPT) {
+        const size_t padded = per + (size_t)m * N * n * sizeof(double);
+        if (pairs && padded <= 78 * 1024) {  // (two workgroups still share a CU)
+          c.pad = 1;
+          c.lds = padded;
+        }
+      } else {
+        c.generic = 1;
+      }
     }
   } else {
     const size_t per = ltv_lds_doubles(N, n, m) * sizeof(double);
     const bool small = n <= 64 && per * 4 <= 64 * 1024 && N * n <= 1024;
     const size_t wper = ltv_wave_lds_doubles(N, n, m) * sizeof(double) * 4;
-    const size_t wall = ltv_wave_lds_doubles(N, n, m, true) * sizeof(double) * 4;
     const size_t bper = ltv_block_lds_doubles(N, n, m) * sizeof(double);
     if (n <= BLOCK && bper <= 20 * 1024) {
       // a workgroup per system, all step matrices resident, eight workgroups per CU
-      auto kernel = n == 2   ? fill_ltv_block_kernel<2>
-                    : n == 3 ? fill_ltv_block_kernel<3>
-                    : n == 4 ? fill_ltv_block_kernel<4>
-                             : fill_ltv_block_kernel<0>;
-      hipLaunchKernelGGL(kernel, dim3(batch), dim3(BLOCK), bper, stream, A, B, S, U, N, n, m);
-    } else if (n * n <= 128 && n * m <= 64 && wall <= 80 * 1024 && batch < 8192) {
-      // every step's (A_k, B_k) resident (two workgroups per CU still fit): measured faster
-      // while the batch leaves the CUs a single round of workgroups (C5: 0.43 against 0.35
-      // of HBM peak at 2 048 systems), slower beyond (0.43 against 0.53 at 16 384)
-      if ((*err = allow_lds(fill_ltv_wave_kernel<true>, wall)) != hipSuccess) return MPCASM_ERR_HIP;
-      const int blocks = (batch + 3) / 4;
-      hipLaunchKernelGGL(fill_ltv_wave_kernel<true>, dim3(blocks), dim3(BLOCK), wall, stream, A, B,
-                         S, U, batch, N, n, m);
+      c.kernel = MPCASM_FILL_LTV_BLOCK;
+      c.arg = n >= 2 && n <= 4 ? n : 0;
+      c.grid = batch;
+      c.lds = bper;
     } else if (n * n <= 128 && n * m <= 64 && wper <= 64 * 1024) {
-      const int blocks = (batch + 3) / 4;
-      hipLaunchKernelGGL(fill_ltv_wave_kernel<false>, dim3(blocks), dim3(BLOCK), wper, stream, A, B,
-                         S, U, batch, N, n, m);
+      // (a wavefront per system with every step's matrices resident would need the block kernel's
+      // LDS four times over within 80 KB: whatever fits that has gone to the block kernel above)
+      c.kernel = MPCASM_FILL_LTV_WAVE;
+      c.grid = by4;
+      c.lds = wper;
     } else if (small) {
-      const size_t bytes = per * 4;
-      const int blocks = (batch + 3) / 4;
-      hipLaunchKernelGGL(fill_ltv_kernel<64>, dim3(blocks), dim3(BLOCK), bytes, stream, A, B, S, U,
-                         batch, N, n, m);
+      c.kernel = MPCASM_FILL_LTV;
+      c.arg = 64;
+      c.grid = by4;
+      c.lds = per * 4;
     } else {
       if (n > BLOCK || per > LDS_MAX) return MPCASM_ERR_LIMIT;
-      if ((*err = allow_lds(fill_ltv_kernel<BLOCK>, per)) != hipSuccess) return MPCASM_ERR_HIP;
-      hipLaunchKernelGGL(fill_ltv_kernel<BLOCK>, dim3(batch), dim3(BLOCK), per, stream, A, B, S, U,
-                         batch, N, n, m);
+      c.kernel = MPCASM_FILL_LTV;
+      c.arg = BLOCK;
+      c.grid = batch;
+      c.lds = per;
     }
   }
+  *out = c;
+  return MPCASM_OK;
+}
+
+int launch_fill_su(const double* A, const double* B, double* S, double* U, int batch, int N, int n,
+                   int m, int ltv, hipStream_t stream, hipError_t* err) {
+  *err = hipSuccess;
+  FillChoice c;
+  const int rc = fill_choose(batch, N, n, m, ltv, (((uintptr_t)S | (uintptr_t)U) & 15) == 0, &c);
+  if (rc != MPCASM_OK) return rc;
+  // (kernels whose dynamic LDS can pass 64 KB get the whole-LDS attribute first)
+#define MPCASM_FILL_LAUNCH(KERNEL, THREADS, ...)                                                   \
+  do {                                                                                             \
+    if ((*err = allow_lds(KERNEL, c.lds)) != hipSuccess) return MPCASM_ERR_HIP;                    \
+    hipLaunchKernelGGL(KERNEL, dim3(c.grid), dim3(THREADS), c.lds, stream, A, B, S, U,             \
+                       __VA_ARGS__);                                                               \
+  } while (0)
+  switch (c.kernel) {
+    case MPCASM_FILL_QUAD: {
+      auto kernel = c.arg == 1   ? fill_lti_quad_kernel<1>
+                    : c.arg == 2 ? fill_lti_quad_kernel<2>
+                    : c.arg == 3 ? fill_lti_quad_kernel<3>
+                                 : fill_lti_quad_kernel<4>;
+      MPCASM_FILL_LAUNCH(kernel, 64, batch, N, m, c.spw, c.lshift, c.whole_lines);
+      break;
+    }
+    case MPCASM_FILL_TINY:
+      MPCASM_FILL_LAUNCH(fill_lti_tiny_kernel, BLOCK, batch, N, n, m, c.spw);
+      break;
+    case MPCASM_FILL_LTI:
+      if (c.arg == 64)
+        MPCASM_FILL_LAUNCH((fill_lti_kernel<64, false>), BLOCK, batch, N, n, m);
+      else if (c.pad)
+        MPCASM_FILL_LAUNCH((fill_lti_kernel<BLOCK, false, true>), BLOCK, batch, N, n, m);
+      else if (!c.generic)
+        MPCASM_FILL_LAUNCH((fill_lti_kernel<BLOCK, false>), BLOCK, batch, N, n, m);
+      else
+        MPCASM_FILL_LAUNCH((fill_lti_kernel<BLOCK, true>), BLOCK, batch, N, n, m);
+      break;
+    case MPCASM_FILL_LTV_ROW: {
+      auto kernel = c.arg == 1   ? fill_ltv_row_kernel<1>
+                    : c.arg == 2 ? fill_ltv_row_kernel<2>
+                    : c.arg == 3 ? fill_ltv_row_kernel<3>
+                                 : fill_ltv_row_kernel<4>;
+      MPCASM_FILL_LAUNCH(kernel, 64, N, m);
+      break;
+    }
+    case MPCASM_FILL_LTV_BLOCK: {
+      auto kernel = c.arg == 2   ? fill_ltv_block_kernel<2>
+                    : c.arg == 3 ? fill_ltv_block_kernel<3>
+                    : c.arg == 4 ? fill_ltv_block_kernel<4>
+                                 : fill_ltv_block_kernel<0>;
+      MPCASM_FILL_LAUNCH(kernel, BLOCK, N, n, m);
+      break;
+    }
+    case MPCASM_FILL_LTV_WAVE:
+      MPCASM_FILL_LAUNCH(fill_ltv_wave_kernel, BLOCK, batch, N, n, m);
+      break;
+    default:
+      if (c.arg == 64)
+        MPCASM_FILL_LAUNCH(fill_ltv_kernel<64>, BLOCK, batch, N, n, m);
+      else
+        MPCASM_FILL_LAUNCH(fill_ltv_kernel<BLOCK>, BLOCK, batch, N, n, m);
+      break;
+  }
+#undef MPCASM_FILL_LAUNCH
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

@@ -22,6 +22,17 @@ hipError_t allow_whole_lds(const void* fn);
 // fill.hip
 int launch_fill_su(const double* A, const double* B, double* S, double* U, int batch, int N, int n,
                    int m, int ltv, hipStream_t stream, hipError_t* err);
+// host only: what launch_fill_su launches (mpcasm_fill_route).  `kernel`: MPCASM_FILL_*; `arg`: the kernel's
+// integer template argument (NS of the quad, ltv-row and ltv-block kernels, TPI of the lti and ltv kernels, else
+// 0); `generic`, `pad`: fill_lti_kernel's GENERIC and PAD; `spw`: systems per wavefront (quad and tiny kernels);
+// `lshift`, `whole_lines`: the quad kernel's; `grid`: workgroups; `lds`: dynamic LDS of a workgroup.  What the
+// decision depends on beside the sizes: whether S and U are both 16-byte aligned, and MPCASM_FILL_MIN_WAVES.
+// MPCASM_ERR_LIMIT where nothing is launched.
+struct FillChoice {
+  int kernel, arg, generic, pad, spw, lshift, whole_lines, grid;
+  size_t lds;
+};
+int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillChoice* out);
 
 // assemble.hip
 size_t assemble_workspace_bytes(const PlanDev& p, int batch);

@@ -44,6 +44,9 @@ POLISH_DONE, POLISH_SKIPPED, POLISH_REJECTED = 1, 0, -1
 POLISH_STATUS = {1: "MPCASM_POLISH_DONE", 0: "MPCASM_POLISH_SKIPPED", -1: "MPCASM_POLISH_REJECTED"}
 ROLL_GIVEN, ROLL_OPTIM, ROLL_STATE, ROLL_REC_WORDS = 0, 1, 2, 8   # records of mpcasm_ltv_rollout_compile
 ERR_ARG = -1
+# mpcasm_fill_route: out[0] and the flags of out[2]
+FILL_QUAD, FILL_TINY, FILL_LTI, FILL_LTV_ROW, FILL_LTV_BLOCK, FILL_LTV_WAVE, FILL_LTV = 1, 2, 3, 4, 5, 6, 7
+FILL_GENERIC, FILL_PAD, FILL_WHOLE_LINES = 1, 2, 4
 GIVEN_KEEP, GIVEN_CONST = -1, -2     # given-map records of mpcasm_given_map_compile (a row: its index >= 0)
 
 
@@ -63,6 +66,7 @@ SIGNATURES = {
     "mpcasm_fill_su": (ctypes.c_int, [_void_p, _void_p, _void_p, _void_p, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       _void_p]),
+    "mpcasm_fill_route": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_plan_create": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
                                           ctypes.POINTER(_void_p)]),
     "mpcasm_plan_destroy": (ctypes.c_int, [_void_p]),

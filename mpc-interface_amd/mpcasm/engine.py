@@ -93,6 +93,23 @@ def fill_su(A, B, N, ltv=False, out=None, stream=None, device=None):
     return S, U
 
 
+FillRoute = collections.namedtuple("FillRoute", "kernel arg flags spw lshift grid lds whole_lds")
+
+
+def fill_route(batch, N, n, m, ltv=False, aligned16=True):
+    """What :func:`fill_su` launches for ``batch`` systems of these sizes -- ``mpcasm_fill_route``, the launch's
+    own decision, no device needed.  ``aligned16``: whether ``S`` and ``U`` both start on a 16-byte boundary
+    (tensors of their own do; views at an odd element offset do not).  A :class:`FillRoute`: ``kernel`` one of
+    ``capi.FILL_*``; ``arg`` the kernel's integer template argument (``NS`` or ``TPI``); ``flags`` of
+    ``capi.FILL_GENERIC | FILL_PAD | FILL_WHOLE_LINES``; ``spw`` systems per wavefront; ``lshift`` of the quad
+    kernel; ``grid`` workgroups; ``lds`` bytes and ``whole_lds`` (more than 64 KB).  Raises
+    :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the sizes."""
+    out = (ctypes.c_int32 * 8)()
+    capi.check(capi.load().mpcasm_fill_route(int(batch), int(N), int(n), int(m), 1 if ltv else 0,
+                                             1 if aligned16 else 0, out), "mpcasm_fill_route")
+    return FillRoute(*(int(x) for x in out))
+
+
 def fill_su_numpy(A, B, N, ltv=False):
     """:func:`fill_su` with numpy in / numpy out (single-instance drop-in path)."""
     S, U = fill_su(A, B, N, ltv=ltv)

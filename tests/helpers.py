@@ -100,8 +100,9 @@ def kappa(N, n):
     return 2 * N * (n + 1)
 
 
-def _premise(A, N, per_step):
-    """|Phi(k, l)| = prod |A_j| over the horizon, in long double (so that M tracks the results)."""
+def assert_cancellation_free(A, N, per_step=False):
+    """|Phi(k, l)| = prod |A_j| over the horizon, in long double (so that M tracks the results): ``A`` of a batch,
+    ``(batch, n, n)`` or per step ``(batch, N, n, n)``."""
     A = np.asarray(A, dtype=LD)
     batch, n = A.shape[0], A.shape[-1]
     eye = np.broadcast_to(np.eye(n, dtype=LD), (batch, n, n))
@@ -119,12 +120,30 @@ def _premise(A, N, per_step):
         assert np.array_equal(np.abs(R[:, :k + 1]), Ra[:, :k + 1]), "the plant is not free of cancellation"
 
 
-def cancellation_free_plants(rng, batch, n, m, rho, N, per_step=False):
+_premise = assert_cancellation_free
+
+
+def cancellation_free_plants(rng, batch, n, m, rho, N, per_step=False, at_once=False):
     """``batch`` plants ``A = S D A+ D S^-1``, ``B = S normal diag(logspace(-2, 2, m))``: ``A+ >= 0``
     with an upper-triangular coupling (non-normal), Perron root ``rho``; ``D`` a random +-1 diagonal,
     ``S`` a permuted diagonal from 1e-3 to 1e3 -- mixed signs, bad scaling, growth, and still
     ``|A^k| = |A|^k``.  ``per_step``: ``(batch, N, n, n)`` / ``(batch, N, n, m)``, the same ``S``, ``D``
-    at every step of an instance.  Asserts the premise over the horizon."""
+    at every step of an instance.  ``at_once`` (not per step): the same construction drawn for the whole batch
+    in one go, for batches of thousands (another sequence of draws than instance by instance).  Asserts the
+    premise over the horizon."""
+    if at_once:
+        assert not per_step
+        d = rng.uniform(0.3, 1.0, (batch, n))
+        Ap = np.triu(rng.uniform(0.0, 0.5, (batch, n, n)), 1)
+        Ap[:, np.arange(n), np.arange(n)] = d
+        Ap *= (rho / d.max(axis=1))[:, None, None]
+        perm = rng.permuted(np.tile(np.arange(n), (batch, 1)), axis=1)
+        Ap = np.take_along_axis(np.take_along_axis(Ap, perm[:, :, None], 1), perm[:, None, :], 2)
+        sd = rng.choice([-1.0, 1.0], (batch, n)) * 10.0 ** rng.uniform(-3, 3, (batch, n))
+        A = sd[:, :, None] * Ap / sd[:, None, :]
+        B = np.abs(sd)[:, :, None] * rng.standard_normal((batch, n, m)) * np.logspace(-2, 2, m)[None, None, :]
+        assert_cancellation_free(A, N)
+        return A, B
     steps = N if per_step else 1
     A = np.empty((batch, steps, n, n))
     B = np.empty((batch, steps, n, m))

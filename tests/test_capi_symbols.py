@@ -18,7 +18,7 @@ def declared_functions():
 
 def test_every_declared_symbol_is_exported_and_bound():
     names = declared_functions()
-    assert "mpcasm_fill_su" in names and "mpcasm_assemble" in names and len(names) >= 12
+    assert "mpcasm_fill_su" in names and "mpcasm_assemble" in names and "mpcasm_fill_route" in names and len(names) >= 12
     lib = ctypes.CDLL(capi.LIB_PATH)
     for name in names:
         assert hasattr(lib, name), "%s declared in mpcasm.h but not exported" % name
