@@ -43,8 +43,9 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 /* library / device ------------------------------------------------------- */
 
 /* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
- * mpcasm_ltv_rollout and mpcasm_ltv_advance (the project's tests pin the value): a client cannot tell from this
- * number whether those three entries are there -- look the symbols up (dlsym) instead. */
+ * mpcasm_ltv_rollout and mpcasm_ltv_advance, and for the one that added mpcasm_qp_polish_wide and
+ * mpcasm_qp_polish_wide_info (the project's tests pin the value): a client cannot tell from this number whether
+ * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
 /* Number of visible HIP devices (0 when none; never fails). */
 int mpcasm_device_count(void);
@@ -574,6 +575,39 @@ int mpcasm_qp_polish(int no, int nc, const double* d_P, const double* d_q, const
 /* Needs no device: the LDS bytes one instance of mpcasm_qp_polish takes (*out; MPCASM_ERR_LIMIT too when that
  * exceeds what a workgroup may have). */
 int mpcasm_qp_polish_lds_bytes(int no, int nc, int64_t* out);
+
+/* The most workgroups one launch of mpcasm_qp_polish_wide has: two per CU of an MI355X. */
+#define MPCASM_POLISH_WIDE_CAP 512
+
+/* The same polishing for QPs whose matrices do not fit on chip (C3, C5, C4), the iterates of
+ * mpcasm_qp_solve_wide: mpcasm_qp_polish's operands, steps, rule, sign test, verdicts and untouched outputs, per
+ * instance exactly as stated above.  G and P are read in place; the matrices of the KKT solve live in d_work, a
+ * device workspace of the caller's that is sized per WORKGROUP, not per instance: the launch has
+ * min(batch, MPCASM_POLISH_WIDE_CAP) workgroups, workgroup w takes the instances w, w + workgroups, ... and reuses
+ * its slice.  A slice is three no x no matrices -- (P + delta I)^-1, Y = G_A (P + delta I)^-1 and
+ * (Y G_A' + delta I)^-1, each inverse formed in place from a Cholesky factorisation (a pivot that is not positive:
+ * MPCASM_POLISH_REJECTED) -- and a solve of the KKT system is four matrix-vector products with them.  The points
+ * equal mpcasm_qp_polish's up to rounding (another method for the same system), not bit for bit.
+ * Workspace: workgroups * (3 no^2, rounded up to even) doubles; d_work 16-byte aligned, its contents neither
+ * read from an earlier call nor meaningful after this one.  Two calls that may run at once need a workspace each.
+ * LDS: one workgroup takes 14 no + 4 nc + 16 + ceil(no / 2) doubles, rounded up to even (the vectors, the partial
+ * sums, the active rows).
+ * Size limit: no <= 512 and that LDS within 156 KB -- every nc <= 2048 at every such no (nc <= 3132 at no = 512),
+ * what mpcasm_qp_solve_wide takes; nc = 0 is allowed.  MPCASM_ERR_LIMIT beyond it, nothing launched.
+ * MPCASM_ERR_ARG, before any device call: mpcasm_qp_polish's cases, a null d_work, a d_work that is not 16-byte
+ * aligned, work_bytes smaller than mpcasm_qp_polish_wide_info reports for (no, nc, batch).  batch == 0: MPCASM_OK. */
+int mpcasm_qp_polish_wide(int no, int nc, const double* d_P, const double* d_q, const double* d_G, const double* d_h,
+                          double* d_x, double* d_y, double* d_z, const int32_t* d_status, double delta,
+                          int refine_iters, int32_t* d_polish, double* d_res, int batch, void* d_work,
+                          size_t work_bytes, void* stream);
+/* Needs no device: for mpcasm_qp_polish_wide on batch instances with no unknowns and nc limits, the LDS bytes of a
+ * workgroup (*lds_bytes), the bytes of workspace the call needs (*work_bytes) and the workgroups it launches
+ * (*workgroups = min(batch, MPCASM_POLISH_WIDE_CAP)), by the formulas above.  The environment variable
+ * MPCASM_QP_POLISH_WIDE_GROUPS, read at every call of either entry, lowers the cap to its value (1 ... the cap: a
+ * tuning aid, tools/bench_qp_polish_wide.py).  MPCASM_ERR_LIMIT beyond the size limit (the outputs still written);
+ * MPCASM_ERR_ARG for no < 1, nc < 0, batch < 0 or a null output. */
+int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
+                               int32_t* workgroups);
 
 /* f2 + the loop  the next tick's `given` from a solution ------------------------------------------------
  * Replaces, for a batch of walkers, the end of every tick of the walking loop

@@ -1896,6 +1896,34 @@ int mpcasm_qp_polish_lds_bytes(int no, int nc, int64_t* out) {
   return *out > RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
 }
 
+int mpcasm_qp_polish_wide(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                          const double* d_h, double* d_x, double* d_y, double* d_z, const int32_t* d_status,
+                          double delta, int refine_iters, int32_t* d_polish, double* d_res, int batch,
+                          void* d_work, size_t work_bytes, void* stream) {
+  if (no < 1 || nc < 0 || batch < 0 || refine_iters < 0 || !(delta > 0.0) || !std::isfinite(delta) ||
+      no > (1 << 12) || nc > (1 << 16))
+    return MPCASM_ERR_ARG;
+  if (batch == 0) return MPCASM_OK;
+  if (!d_P || !d_q || !d_x || !d_polish || (nc > 0 && (!d_G || !d_h || !d_y || !d_z))) return MPCASM_ERR_ARG;
+  int64_t need = 0;
+  const int limit = qp_polish_wide_info(no, nc, batch, nullptr, &need, nullptr);
+  if (limit != MPCASM_OK) return limit;
+  if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0 || work_bytes < (size_t)need) return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_qp_polish_wide(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, d_status, delta, refine_iters,
+                                       d_polish, d_res, batch, static_cast<double*>(d_work),
+                                       static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
+int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
+                               int32_t* workgroups) {
+  if (no < 1 || nc < 0 || batch < 0 || no > (1 << 12) || nc > (1 << 16) || !lds_bytes || !work_bytes || !workgroups)
+    return MPCASM_ERR_ARG;
+  return qp_polish_wide_info(no, nc, batch, lds_bytes, work_bytes, workgroups);
+}
+
 int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_index, int nnz,
                   double* d_dst, int batch, void* stream) {
   if (nnz < 0 || batch < 0 || src_stride < 0) return MPCASM_ERR_ARG;

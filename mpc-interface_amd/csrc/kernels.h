@@ -170,6 +170,14 @@ size_t polish_lds_bytes(int no, int nc);
 int launch_qp_polish(int no, int nc, const double* P, const double* q, const double* G, const double* h,
                      double* x, double* y, double* z, const int32_t* status, double delta, int refine_iters,
                      int32_t* polish, double* res, int batch, hipStream_t stream, hipError_t* err);
+// polish_wide.hip: the same polish with G and P read in place and the matrices of the KKT solve in a workspace of
+// the caller's, one slice per workgroup of a launch of min(batch, POLISH_WIDE_CAP) workgroups
+constexpr int POLISH_WIDE_CAP = MPCASM_POLISH_WIDE_CAP;
+int qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes, int32_t* workgroups);
+int launch_qp_polish_wide(int no, int nc, const double* P, const double* q, const double* G, const double* h,
+                          double* x, double* y, double* z, const int32_t* status, double delta, int refine_iters,
+                          int32_t* polish, double* res, int batch, double* work, hipStream_t stream,
+                          hipError_t* err);
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err);
 

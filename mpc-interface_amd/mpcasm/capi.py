@@ -41,6 +41,7 @@ QP_STATUS = {
 }
 # per-instance outcomes of mpcasm_qp_polish
 POLISH_DONE, POLISH_SKIPPED, POLISH_REJECTED = 1, 0, -1
+POLISH_WIDE_CAP = 512          # MPCASM_POLISH_WIDE_CAP: the most workgroups of one mpcasm_qp_polish_wide launch
 POLISH_STATUS = {1: "MPCASM_POLISH_DONE", 0: "MPCASM_POLISH_SKIPPED", -1: "MPCASM_POLISH_REJECTED"}
 ROLL_GIVEN, ROLL_OPTIM, ROLL_STATE, ROLL_REC_WORDS = 0, 1, 2, 8   # records of mpcasm_ltv_rollout_compile
 ERR_ARG = -1
@@ -129,6 +130,12 @@ SIGNATURES = {
                                                                                        _void_p, _void_p, ctypes.c_int,
                                                                                        _void_p]),
     "mpcasm_qp_polish_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_qp_polish_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 +
+                              [ctypes.c_double, ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p,
+                               ctypes.c_size_t, _void_p]),
+    "mpcasm_qp_polish_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                                  ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,

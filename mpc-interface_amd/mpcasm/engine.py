@@ -274,6 +274,63 @@ def qp_polish_lds_bytes(no, nc):
     return int(out.value)
 
 
+def polish_qp_wide(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE,
+                   stream=None, out=None, work=None):
+    """:func:`polish_qp` for QPs whose matrices do not fit on chip (``mpcasm_qp_polish_wide``): the same arguments,
+    steps, verdicts and return value, up to 512 unknowns and 2 048 limits, for the iterates of
+    :func:`solve_qp_wide`.  ``G`` and ``P`` are read in place; the matrices of the KKT solve live in ``work``, a
+    contiguous uint8 or float64 device tensor of at least ``qp_polish_wide_info(no, nc, B)[1]`` bytes -- sized by
+    the launch's workgroups, not by the batch -- allocated here when None (a loop that replays a graph keeps one at
+    a fixed address; calls that may run at once need one each).  The polished points equal :func:`polish_qp`'s up
+    to rounding."""
+    torch = require_device()
+    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
+        x, y, z, res = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z, sol_or_xyz.res
+    else:
+        (x, y, z), res = sol_or_xyz, None
+    if x is None or y is None or z is None:
+        raise ValueError("polish_qp_wide takes the iterates x, y and z")
+    batch, no, nc, _warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, None, False)
+    verdict = None
+    if out is not None:
+        verdict, res = out
+    if verdict is None:
+        verdict = torch.empty((batch,), dtype=torch.int32, device=P.device)
+    if res is None:
+        res = torch.full((batch, 2), float("nan"), dtype=torch.float64, device=P.device)
+    for t, dtype, shape in ((verdict, torch.int32, (batch,)), (res, torch.float64, (batch, 2))) + \
+            (((status, torch.int32, (batch,)),) if status is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
+                and tuple(t.shape) == shape):
+            raise ValueError("status, polish (B,) int32 and res (B, 2) float64: contiguous, on P's device")
+    need = qp_polish_wide_info(no, nc, batch)[1]
+    if work is None:
+        work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=P.device)
+    if not (isinstance(work, torch.Tensor) and work.device == P.device and work.is_contiguous()
+            and work.dtype in (torch.uint8, torch.float64)):
+        raise ValueError("work: a contiguous uint8 or float64 tensor on P's device")
+    with torch.cuda.device(P.device):
+        rc = capi.load().mpcasm_qp_polish_wide(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
+                                               x.data_ptr(), y.data_ptr(), z.data_ptr(),
+                                               status.data_ptr() if status is not None else None, float(delta),
+                                               int(refine_iters), verdict.data_ptr(), res.data_ptr(), batch,
+                                               work.data_ptr(), work.numel() * work.element_size(),
+                                               _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_qp_polish_wide")
+    return x, y, z, verdict, res
+
+
+def qp_polish_wide_info(no, nc, batch):
+    """``(lds_bytes, work_bytes, workgroups)`` of :func:`polish_qp_wide` on ``batch`` instances: the LDS of a
+    workgroup, the workspace the call needs and the workgroups it launches, ``min(batch, capi.POLISH_WIDE_CAP)``;
+    ``MpcasmError`` with ``ERR_LIMIT`` past its size limit (``mpcasm_qp_polish_wide_info``).  Needs no device."""
+    lds, work, groups = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    rc = capi.load().mpcasm_qp_polish_wide_info(int(no), int(nc), int(batch), ctypes.byref(lds), ctypes.byref(work),
+                                                ctypes.byref(groups))
+    capi.check(rc, "mpcasm_qp_polish_wide_info")
+    return int(lds.value), int(work.value), int(groups.value)
+
+
 def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
               adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False):
     """:func:`solve_qp` and :func:`solve_qp_wide` through the C entry ``entry``; ``workspace``: allocate
@@ -329,15 +386,21 @@ def qp_solve_lds_bytes(no, nc):
 
 def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
                   eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None):
+                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False):
     """:func:`solve_qp` for QPs whose matrices do not fit on chip (``mpcasm_qp_solve_wide``): the same
     arguments, rules and :class:`QpSolution`, up to 512 unknowns and 2 048 limits (:func:`qp_solve_wide_info`).
     ``G`` is read in place once per iteration; ``K^-1`` lives in LDS where it fits, else in ``kinv`` -- a
     ``(B, no, no)`` workspace allocated here when the caller passes none (the environment variable
-    ``MPCASM_QP_WIDE_KINV`` = ``lds`` / ``global`` overrides where it lives)."""
-    return _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
-                     eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
-                     stream, out, workspace=True)
+    ``MPCASM_QP_WIDE_KINV`` = ``lds`` / ``global`` overrides where it lives).
+    ``polish``: :func:`polish_qp_wide` with OSQP's defaults after the solve, on the solved instances, as
+    :func:`solve_qp` does with :func:`polish_qp`: a :class:`PolishedQpSolution`."""
+    sol = _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
+                    eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
+                    stream, out, workspace=True)
+    if not polish:
+        return sol
+    verdict = polish_qp_wide(P, q, G, h, sol, status=sol.status, stream=stream)[3]
+    return PolishedQpSolution(*sol, verdict)
 
 
 def qp_solve_wide_info(no, nc):

@@ -5,12 +5,14 @@ formulation compiled with ``ltv=``:
     window [t, t + N) of every instance's (A_k, B_k)   Assembler.bind_ltv_window   (a pointer, nothing copied)
     P, q, G, h                                         Assembler.assemble          (csrc/sweep.hip)
     x, status                                          engine.solve_qp_wide        (cold, OSQP's defaults)
+    x polished where solved (polish=True only)         engine.polish_qp_wide       (csrc/polish_wide.hip)
     given <- x_1 = A_t x_0 + B_t u_0                   Assembler.advance           (csrc/rollout.hip)
 
 -- the reference's tick (biped_mpc_loop.py:50-95: assemble, ``osqp_solve_qp``, ``preview_all`` +
 ``update_given_collector``) with per-step dynamics, nothing read back to the host.  The loop runs launch by
 launch: the window's address changes every tick, which a captured graph would not follow."""
-from .engine import APPLY_ALL, APPLY_SOLVED, OSQP_RHO, Assembler, qp_solve_wide_info, solve_qp_wide
+from .engine import (APPLY_ALL, APPLY_SOLVED, OSQP_RHO, Assembler, polish_qp_wide, qp_polish_wide_info,
+                     qp_solve_wide_info, solve_qp_wide)
 
 
 class LtvLoop:
@@ -22,9 +24,11 @@ class LtvLoop:
     read the states out of it.  ``on_unsolved`` is :class:`~mpcasm.walkers.WalkerFleet`'s rule for an instance
     whose QP did not come back solved (or out of iterations): ``"hold"`` leaves its row of ``given`` as it was
     (``APPLY_SOLVED``), ``"apply"`` applies whatever iterate came back unless it is NaN (``APPLY_ALL``).
+    ``polish``: every solved QP is polished (:func:`~mpcasm.engine.polish_qp_wide`, OSQP's defaults) before its
+    solution becomes the next ``given``; the results of a tick then carry ``"polish"``, the verdicts.
     ``solver_kwargs`` go to :func:`~mpcasm.engine.solve_qp_wide` (``eps_abs``, ``max_iter``, ...)."""
 
-    def __init__(self, form, name, batch, A_seq, B_seq, on_unsolved="hold", **solver_kwargs):
+    def __init__(self, form, name, batch, A_seq, B_seq, on_unsolved="hold", polish=False, **solver_kwargs):
         if on_unsolved not in ("hold", "apply"):
             raise ValueError("on_unsolved: 'hold' or 'apply', got %r" % (on_unsolved,))
         self.on_unsolved = on_unsolved
@@ -48,11 +52,17 @@ class LtvLoop:
         # where K^-1 does not fit on chip it is the solver's workspace: allocated once, unless the caller brings one
         if "kinv" not in solver_kwargs and not qp_solve_wide_info(asm.no, asm.nc)[1]:
             self._solver_kwargs["kinv"] = torch.empty((B, asm.no, asm.no), **f)
+        # the polish's workspace and verdicts, allocated once
+        self.polish = bool(polish)
+        if self.polish:
+            self._polish_work = torch.empty((max(qp_polish_wide_info(asm.no, asm.nc, B)[1], 16) // 8,), **f)
+            self._polish_verdict = torch.zeros(B, **i32)
 
     def step(self):
         """One tick on :attr:`given`: the window at ``t``, the assembly, a cold solve, the next ``given`` by the
         loop's ``on_unsolved`` rule; then ``t`` advances.  Nothing is read back: returns ``{"x", "status",
-        "iters"}``, device tensors in the loop's own buffers, valid until the next step."""
+        "iters"}`` (a loop that polishes: and ``"polish"``), device tensors in the loop's own buffers, valid until
+        the next step."""
         if self.t >= self.ticks_possible:
             raise ValueError("the sequences hold %d steps: no window of %d steps starts at tick %d"
                              % (self.A_seq.shape[-3], self.horizon, self.t))
@@ -62,18 +72,24 @@ class LtvLoop:
         qp["rho"].fill_(OSQP_RHO)          # (the reference builds a fresh solver every tick)
         sol = solve_qp_wide(P, q, G, h, rho=qp["rho"], out=tuple(qp[k] for k in ("x", "y", "z", "status", "iters",
                                                                                   "res")), **self._solver_kwargs)
+        if self.polish:
+            polish_qp_wide(P, q, G, h, sol, status=sol.status, out=(self._polish_verdict, sol.res),
+                           work=self._polish_work)
         asm.advance(self.given, sol.x, status=sol.status, apply_mask=self._apply_mask)
         self.t += 1
+        if self.polish:
+            return {"x": sol.x, "status": sol.status, "iters": sol.iters, "polish": self._polish_verdict}
         return {"x": sol.x, "status": sol.status, "iters": sol.iters}
 
     def run(self, ticks, record=False):
         """:meth:`step` ``ticks`` times; returns device tensors ``status`` and ``iters`` ``(ticks, batch)`` int32
-        and, with ``record``, ``given`` ``(ticks + 1, batch, ng)``: :attr:`given` before the first tick and after
+        (a loop that polishes: and ``polish``, the verdicts, alike) and, with ``record``, ``given`` ``(ticks + 1, batch, ng)``: :attr:`given` before the first tick and after
         every tick (as :meth:`mpcasm.walkers.WalkerFleet.run` records them)."""
         torch, given = self._torch, self.given
         i32 = dict(dtype=torch.int32, device=given.device)
         status = torch.zeros((ticks, self.batch), **i32)
         iters = torch.zeros((ticks, self.batch), **i32)
+        verdicts = torch.zeros((ticks, self.batch), **i32) if self.polish else None
         trail = torch.empty((ticks + 1,) + tuple(given.shape), dtype=given.dtype, device=given.device) \
             if record else None
         if record:
@@ -82,9 +98,13 @@ class LtvLoop:
             out = self.step()
             status[t].copy_(out["status"])
             iters[t].copy_(out["iters"])
+            if self.polish:
+                verdicts[t].copy_(out["polish"])
             if record:
                 trail[t + 1].copy_(given)
         result = {"status": status, "iters": iters}
+        if self.polish:
+            result["polish"] = verdicts
         if record:
             result["given"] = trail
         return result
