@@ -609,6 +609,58 @@ int mpcasm_qp_polish_wide(int no, int nc, const double* d_P, const double* d_q, 
 int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
                                int32_t* workgroups);
 
+/* The loop's warm start  last tick's solution, moved one sample along, as this tick's start ----------------
+ * A receding-horizon loop solves, every tick, nearly the QP of the tick before with the horizon moved on by one
+ * sample; mpcasm_qp_solve and mpcasm_qp_solve_wide take `warm`, d_rho in/out and the iterates.  These two entries
+ * are the piece in between, for a loop whose structure (no, nc) changes from tick to tick and whose instances sit
+ * at other positions of other launches every tick.  Nothing is read back; both can be captured in a graph.
+ *
+ * The *warm store* is the caller's: one record per row (per walker, in walker order), as four device arrays
+ *   d_store_x    [store_rows][store_no] doubles   x, padded with zeros to store_no
+ *   d_store_y    [store_rows][store_nc] doubles   y, padded with zeros to store_nc
+ *   d_store_rho  [store_rows] doubles             the step the solve ended with
+ *   d_store_meta [store_rows][2] int32            the solve's status (MPCASM_QP_*), and a tag of the caller's choice
+ * 8-byte aligned; 1 <= store_no <= 512, 0 <= store_nc <= 2048 (d_store_y may be NULL when store_nc == 0).
+ *
+ * mpcasm_qp_warm_store, after a solve: instance b of a launch (no <= store_no, nc <= store_nc; d_x [count][no],
+ * d_y [count][nc], d_rho [count], d_status [count]) is written into row d_index[b] of the store with `tag`, the
+ * padding zeroed.  x, y and rho are stored bit for bit, and every instance is stored whatever its status: a stale
+ * record never survives a tick (mpcasm_qp_warm_start judges the status).  d_index (count entries; NULL: instance
+ * b is row b, store_rows >= count) follows the contract of mpcasm_next_given: DISTINCT entries in [0, store_rows),
+ * vouched for by the host that builds them; an entry outside that range is skipped.  nc == 0: d_y may be NULL.
+ *
+ * mpcasm_qp_warm_start, before a solve: writes the iterates d_x [count][no], d_y, d_z [count][nc] and the step
+ * d_rho [count] the solve starts from (pass them to mpcasm_qp_solve with warm = 1), and d_warm [count] int32: 1
+ * where the instance starts warm, 0 where cold.  It reads this tick's assembled d_G [count][nc][no] and d_h
+ * [count][nc] where they lie, the store, d_index (as above; an entry outside [0, store_rows) makes the instance
+ * cold) and two int32 device tables: d_col_src [no], entries in [-1, store_no), and d_row_src [nc], entries in
+ * [-1, store_nc) -- where unknown i and row j of this QP were in the record, -1: nowhere.  An entry outside its
+ * range counts as -1; nothing is read out of range whatever the tables and the index hold.
+ * Instance b with the record r = d_index[b] is WARM when all of these hold:
+ *   the record's tag equals expect_tag;  bit MPCASM_QP_BIT(status) of warm_mask is set;
+ *   its rho is finite and inside [1e-6, 1e6] (the range of the solve's adaptive rho);
+ *   every value it gathers is finite (a NaN in a column no table entry names does not matter).
+ * Then  x0[i] = d_col_src[i] >= 0 ? X[r][d_col_src[i]] : 0  and y0 likewise through d_row_src (copies, bit for
+ * bit),  z0 = min(G_b x0, h_b)  and  rho0 = rho[r].  Otherwise COLD:  x0 = 0, y0 = 0, z0 = min(0, h_b),
+ * rho0 = rho_cold -- exactly what mpcasm_qp_solve(warm = 0) starts from, so one launch with warm = 1 serves warm
+ * and cold instances alike.  nc == 0 is allowed: d_G, d_h, d_y, d_z, d_row_src may then be NULL.
+ * G is read once, in place (16-byte loads where no is even and d_G is 16-byte aligned, else 8-byte loads).
+ *
+ * Both: sizes up to mpcasm_qp_solve_wide's, no <= 512 and nc <= 2048.  MPCASM_ERR_ARG, before any device call:
+ * no < 1, nc < 0, count < 0, store_rows < 0, store_no < 1, store_nc < 0, a size beyond those limits, a null
+ * operand that is not excused above, a rho_cold that is not finite; for the store also no > store_no,
+ * nc > store_nc, and a NULL d_index with store_rows < count.  count == 0: MPCASM_OK, no device needed. */
+int mpcasm_qp_warm_store(int no, int nc, const double* d_x, const double* d_y, const double* d_rho,
+                         const int32_t* d_status, int tag, double* d_store_x, double* d_store_y, double* d_store_rho,
+                         int32_t* d_store_meta, int64_t store_rows, int store_no, int store_nc, const int32_t* d_index,
+                         int count, void* stream);
+int mpcasm_qp_warm_start(int no, int nc, const double* d_G, const double* d_h, const double* d_store_x,
+                         const double* d_store_y, const double* d_store_rho, const int32_t* d_store_meta,
+                         int64_t store_rows, int store_no, int store_nc, const int32_t* d_index,
+                         const int32_t* d_col_src, const int32_t* d_row_src, int expect_tag, uint32_t warm_mask,
+                         double rho_cold, double* d_x, double* d_y, double* d_z, double* d_rho, int32_t* d_warm,
+                         int count, void* stream);
+
 /* f2 + the loop  the next tick's `given` from a solution ------------------------------------------------
  * Replaces, for a batch of walkers, the end of every tick of the walking loop
  *   preview_all + update_given_collector       biped_mpc_loop.py:62-65, 81-92

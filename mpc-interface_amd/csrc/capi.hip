@@ -1924,6 +1924,47 @@ int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, in
   return qp_polish_wide_info(no, nc, batch, lds_bytes, work_bytes, workgroups);
 }
 
+int mpcasm_qp_warm_store(int no, int nc, const double* d_x, const double* d_y, const double* d_rho,
+                         const int32_t* d_status, int tag, double* d_store_x, double* d_store_y, double* d_store_rho,
+                         int32_t* d_store_meta, int64_t store_rows, int store_no, int store_nc, const int32_t* d_index,
+                         int count, void* stream) {
+  if (no < 1 || nc < 0 || count < 0 || store_rows < 0 || store_no < 1 || store_nc < 0 || no > 512 || nc > 2048 ||
+      store_no > 512 || store_nc > 2048 || no > store_no || nc > store_nc)
+    return MPCASM_ERR_ARG;
+  if (count == 0) return MPCASM_OK;
+  if (!d_x || !d_rho || !d_status || !d_store_x || !d_store_rho || !d_store_meta || (nc > 0 && !d_y) ||
+      (store_nc > 0 && !d_store_y) || (!d_index && store_rows < count))
+    return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_qp_warm_store(no, nc, d_x, d_y, d_rho, d_status, tag, d_store_x, d_store_y, d_store_rho,
+                                      d_store_meta, store_rows, store_no, store_nc, d_index, count,
+                                      static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
+int mpcasm_qp_warm_start(int no, int nc, const double* d_G, const double* d_h, const double* d_store_x,
+                         const double* d_store_y, const double* d_store_rho, const int32_t* d_store_meta,
+                         int64_t store_rows, int store_no, int store_nc, const int32_t* d_index,
+                         const int32_t* d_col_src, const int32_t* d_row_src, int expect_tag, uint32_t warm_mask,
+                         double rho_cold, double* d_x, double* d_y, double* d_z, double* d_rho, int32_t* d_warm,
+                         int count, void* stream) {
+  if (no < 1 || nc < 0 || count < 0 || store_rows < 0 || store_no < 1 || store_nc < 0 || no > 512 || nc > 2048 ||
+      store_no > 512 || store_nc > 2048 || !std::isfinite(rho_cold))
+    return MPCASM_ERR_ARG;
+  if (count == 0) return MPCASM_OK;
+  if (!d_store_x || !d_store_rho || !d_store_meta || !d_col_src || !d_x || !d_rho || !d_warm ||
+      (nc > 0 && (!d_G || !d_h || !d_row_src || !d_y || !d_z)) || (nc > 0 && store_nc > 0 && !d_store_y))
+    return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_qp_warm_start(no, nc, d_G, d_h, d_store_x, d_store_y, d_store_rho, d_store_meta, store_rows,
+                                      store_no, store_nc, d_index, d_col_src, d_row_src, expect_tag, warm_mask,
+                                      rho_cold, d_x, d_y, d_z, d_rho, d_warm, count,
+                                      static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
 int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_index, int nnz,
                   double* d_dst, int batch, void* stream) {
   if (nnz < 0 || batch < 0 || src_stride < 0) return MPCASM_ERR_ARG;

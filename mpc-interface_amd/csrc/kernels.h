@@ -178,6 +178,16 @@ int launch_qp_polish_wide(int no, int nc, const double* P, const double* q, cons
                           double* x, double* y, double* z, const int32_t* status, double delta, int refine_iters,
                           int32_t* polish, double* res, int batch, double* work, hipStream_t stream,
                           hipError_t* err);
+// warm.hip: a closed loop's warm store -- the scatter after a solve, the shifted start before the next
+int launch_qp_warm_store(int no, int nc, const double* x, const double* y, const double* rho, const int32_t* status,
+                         int tag, double* sx, double* sy, double* srho, int32_t* smeta, int64_t store_rows,
+                         int store_no, int store_nc, const int32_t* index, int count, hipStream_t stream,
+                         hipError_t* err);
+int launch_qp_warm_start(int no, int nc, const double* G, const double* h, const double* sx, const double* sy,
+                         const double* srho, const int32_t* smeta, int64_t store_rows, int store_no, int store_nc,
+                         const int32_t* index, const int32_t* col_src, const int32_t* row_src, int expect_tag,
+                         uint32_t warm_mask, double rho_cold, double* x, double* y, double* z, double* rho,
+                         int32_t* warm, int count, hipStream_t stream, hipError_t* err);
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err);
 

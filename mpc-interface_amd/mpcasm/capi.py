@@ -136,6 +136,13 @@ SIGNATURES = {
     "mpcasm_qp_polish_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                                   ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_qp_warm_store": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 4 + [ctypes.c_int] +
+                             [_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int,
+                                              _void_p]),
+    "mpcasm_qp_warm_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 6 +
+                             [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [_void_p] * 3 +
+                             [ctypes.c_int, ctypes.c_uint32, ctypes.c_double] + [_void_p] * 5 +
+                             [ctypes.c_int, _void_p]),
     "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,

@@ -197,7 +197,7 @@ class PolishedQpSolution(collections.namedtuple("QpSolution", "x y z status iter
 
 def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
              eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False):
+             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False, warm=False):
     """A batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h`` solved to tolerance on the device
     (``mpcasm_qp_solve``): :func:`admm`'s iteration with OSQP's termination tests and adaptive rho, every
     instance stopping on its own, nothing read back to the host (a tick can be captured in a graph).
@@ -210,13 +210,15 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
     the primal and dual residuals of the returned iterate.
     ``out``: for a COLD start, the caller's ``(x, y, z, status, iters, res)`` to write instead of new tensors
     (``(B, no)``, ``(B, nc)``, ``(B, nc)``, ``(B,)`` int32 twice, ``(B, 2)``: a loop that replays a graph keeps
-    them at fixed addresses); ``x, y, z`` are not read.
+    them at fixed addresses); ``x, y, z`` are not read -- unless ``warm``: then ``out``'s ``x, y, z`` hold the
+    start, as :func:`warm_start_qp` wrote it (cold instances among them), and ``rho`` the steps beside it.
     ``polish``: :func:`polish_qp` with OSQP's defaults after the solve, on the solved instances; ``x, y, z`` and
     ``res`` of an instance whose polished point is accepted are that point's, and the solution grows a trailing field
     ``polish``, the ``(B,)`` int32 verdicts ``POLISH_*`` (a :class:`PolishedQpSolution`; without polish ``sol.polish``
     is None and the solution has the seven fields it always had)."""
     sol = _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
-                    max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out)
+                    max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out,
+                    warm_out=warm)
     if not polish:
         return sol
     verdict = polish_qp(P, q, G, h, sol, status=sol.status, stream=stream)[3]
@@ -332,9 +334,11 @@ def qp_polish_wide_info(no, nc, batch):
 
 
 def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
-              adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False):
+              adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False, warm_out=False):
     """:func:`solve_qp` and :func:`solve_qp_wide` through the C entry ``entry``; ``workspace``: allocate
-    ``kinv`` when it is None (the wide path's K^-1 off chip)."""
+    ``kinv`` when it is None (the wide path's K^-1 off chip); ``warm_out``: ``out``'s iterates hold the start."""
+    if warm_out and out is None:
+        raise ValueError("warm=True is for out=: pass x, y, z for a warm start into new tensors")
     torch = require_device()
     if out is not None:
         if x is not None or y is not None or z is not None:
@@ -347,7 +351,7 @@ def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, e
                     and t.is_contiguous() and tuple(t.shape) == shape):
                 raise ValueError("out: status, iters (B,) int32 and res (B, 2) float64, contiguous, on P's device")
     batch, no, nc, warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid)
-    warm = warm and out is None
+    warm = warm and (out is None or bool(warm_out))
     if isinstance(rho, torch.Tensor):
         if not (rho.device == P.device and rho.dtype == torch.float64 and rho.is_contiguous()
                 and tuple(rho.shape) == (batch,)):
@@ -386,7 +390,7 @@ def qp_solve_lds_bytes(no, nc):
 
 def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
                   eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False):
+                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False, warm=False):
     """:func:`solve_qp` for QPs whose matrices do not fit on chip (``mpcasm_qp_solve_wide``): the same
     arguments, rules and :class:`QpSolution`, up to 512 unknowns and 2 048 limits (:func:`qp_solve_wide_info`).
     ``G`` is read in place once per iteration; ``K^-1`` lives in LDS where it fits, else in ``kinv`` -- a
@@ -396,7 +400,7 @@ def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3
     :func:`solve_qp` does with :func:`polish_qp`: a :class:`PolishedQpSolution`."""
     sol = _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
                     eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
-                    stream, out, workspace=True)
+                    stream, out, workspace=True, warm_out=warm)
     if not polish:
         return sol
     verdict = polish_qp_wide(P, q, G, h, sol, status=sol.status, stream=stream)[3]
@@ -410,6 +414,132 @@ def qp_solve_wide_info(no, nc):
     rc = capi.load().mpcasm_qp_solve_wide_info(int(no), int(nc), ctypes.byref(lds), ctypes.byref(on))
     capi.check(rc, "mpcasm_qp_solve_wide_info")
     return int(lds.value), bool(on.value)
+
+
+# --------------------------------------------------------------------------
+# the loops' warm start: the store after a solve, the shifted start before the next
+# --------------------------------------------------------------------------
+WARM_SOLVED = capi.qp_bit(QP_SOLVED)      # warm_mask: only a solved record starts the next tick warm
+
+
+class WarmStore:
+    """The warm store of a closed loop (``mpcasm_qp_warm_store`` / ``mpcasm_qp_warm_start``): one record per row
+    (per walker, in walker order) on ``device`` -- ``x (rows, no_max)`` and ``y (rows, nc_max)`` float64, padded
+    with zeros, ``rho (rows,)`` float64 and ``meta (rows, 2)`` int32, the solve's status and a tag of the
+    caller's choice.  The tags start at -1, the statuses at 0 (no ``QP_*`` value) and rho at 0: nothing is warm
+    before its first store."""
+
+    def __init__(self, rows, no_max, nc_max, device=None):
+        torch = require_device()
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        rows, no_max, nc_max = int(rows), int(no_max), int(nc_max)
+        if rows < 0 or not 1 <= no_max <= 512 or not 0 <= nc_max <= 2048:
+            raise ValueError("WarmStore: rows >= 0, 1 <= no_max <= 512, 0 <= nc_max <= 2048")
+        self.rows, self.no, self.nc = rows, no_max, nc_max
+        self.x = torch.zeros((rows, no_max), dtype=torch.float64, device=device)
+        self.device = device = self.x.device
+        self.y = torch.zeros((rows, nc_max), dtype=torch.float64, device=device)
+        self.rho = torch.zeros((rows,), dtype=torch.float64, device=device)
+        self.meta = torch.zeros((rows, 2), dtype=torch.int32, device=device)
+        self.reset()
+
+    def reset(self):
+        """Forget every record (a loop that starts over): tags -1, statuses 0, rho 0; asynchronous."""
+        self.meta.zero_()
+        self.meta[:, 1] = -1
+        self.rho.zero_()
+
+    def _args(self):
+        return (self.x.data_ptr(), self.y.data_ptr() if self.nc else None, self.rho.data_ptr(),
+                self.meta.data_ptr(), self.rows, self.no, self.nc)
+
+
+def _warm_tensor(torch, t, dtype, shape, device, what):
+    if not (isinstance(t, torch.Tensor) and t.device == device and t.dtype == dtype and t.is_contiguous()
+            and tuple(t.shape) == tuple(shape)):
+        raise ValueError("%s: a contiguous %s tensor of shape %s on the store's device"
+                         % (what, str(dtype).replace("torch.", ""), tuple(shape)))
+    return t
+
+
+def _warm_index(torch, store, index, count):
+    """A device index as it is (int32, ``count`` entries: the caller vouches for it, as for ``next_given``), one
+    from the host checked and copied."""
+    if index is None:
+        if store.rows < count:
+            raise ValueError("a store of %d rows takes no launch of %d instances without an index"
+                             % (store.rows, count))
+        return None
+    if not isinstance(index, torch.Tensor):
+        index = torch.as_tensor(checked_index(index, store.rows), device=store.device)
+    return _warm_tensor(torch, index, torch.int32, (count,), store.device, "index")
+
+
+def warm_store_qp(store, sol, tag, index=None, stream=None):
+    """After a solve: instance ``b`` of ``sol`` (a :class:`QpSolution`, or ``(x, y, rho, status)``) into row
+    ``index[b]`` of ``store`` (None: row ``b``) with ``tag``, whatever its status (``mpcasm_qp_warm_store``).
+    ``index``: an int32 device tensor of distinct rows in range, or a host array (checked here)."""
+    torch = require_device()
+    x, y, rho, status = (sol.x, sol.y, sol.rho, sol.status) if hasattr(sol, "status") else sol
+    count, no = x.shape
+    nc = y.shape[1]
+    dev = store.device
+    _warm_tensor(torch, x, torch.float64, (count, no), dev, "x")
+    _warm_tensor(torch, y, torch.float64, (count, nc), dev, "y")
+    _warm_tensor(torch, rho, torch.float64, (count,), dev, "rho")
+    _warm_tensor(torch, status, torch.int32, (count,), dev, "status")
+    index = _warm_index(torch, store, index, count)
+    with torch.cuda.device(dev):
+        rc = capi.load().mpcasm_qp_warm_store(no, nc, x.data_ptr(), y.data_ptr() if nc else None, rho.data_ptr(),
+                                              status.data_ptr(), int(tag), *store._args(),
+                                              index.data_ptr() if index is not None else None, count,
+                                              _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_qp_warm_store")
+
+
+WarmStart = collections.namedtuple("WarmStart", "x y z rho warm")
+
+
+def warm_start_qp(store, G, h, col_src, row_src, expect_tag, index=None, warm_mask=WARM_SOLVED, rho_cold=OSQP_RHO,
+                  stream=None, out=None):
+    """Before a solve: the iterates and the step it starts from (``mpcasm_qp_warm_start``), for the assembled
+    ``G (B, nc, no)``, ``h (B, nc)``.  Instance ``b`` is warm when the record in row ``index[b]`` of ``store``
+    (None: row ``b``) carries ``expect_tag`` and a status in ``warm_mask``, a rho inside [1e-6, 1e6] and finite
+    values wherever the tables read it: then ``x0``, ``y0`` are the record's, gathered through ``col_src (no,)``
+    and ``row_src (nc,)`` (int32 device tensors, :func:`mpcasm.warm.shift_map`; -1: zero), ``z0 = min(G x0, h)``
+    and ``rho0`` the record's.  Otherwise the start is the cold one: ``0, 0, min(0, h)``, ``rho_cold``.
+    Returns a :class:`WarmStart` ``(x, y, z, rho, warm)``, ``warm (B,)`` int32 -- pass ``x, y, z, rho`` to
+    :func:`solve_qp`.  ``out``: the caller's ``(x, y, z, rho, warm)`` to write instead of new tensors."""
+    torch = require_device()
+    dev = store.device
+    if not (isinstance(G, torch.Tensor) and G.dim() == 3):
+        raise ValueError("G: a (B, nc, no) device tensor")
+    count, nc, no = G.shape
+    _warm_tensor(torch, G, torch.float64, (count, nc, no), dev, "G")
+    _warm_tensor(torch, h, torch.float64, (count, nc), dev, "h")
+    _warm_tensor(torch, col_src, torch.int32, (no,), dev, "col_src")
+    _warm_tensor(torch, row_src, torch.int32, (nc,), dev, "row_src")
+    if out is None:
+        f = dict(dtype=torch.float64, device=dev)
+        out = (torch.empty((count, no), **f), torch.empty((count, nc), **f), torch.empty((count, nc), **f),
+               torch.empty((count,), **f), torch.empty((count,), dtype=torch.int32, device=dev))
+    x, y, z, rho, warm = out
+    _warm_tensor(torch, x, torch.float64, (count, no), dev, "x")
+    _warm_tensor(torch, y, torch.float64, (count, nc), dev, "y")
+    _warm_tensor(torch, z, torch.float64, (count, nc), dev, "z")
+    _warm_tensor(torch, rho, torch.float64, (count,), dev, "rho")
+    _warm_tensor(torch, warm, torch.int32, (count,), dev, "warm")
+    index = _warm_index(torch, store, index, count) if index is not None else None
+    nul = lambda t: t.data_ptr() if nc else None
+    with torch.cuda.device(dev):
+        rc = capi.load().mpcasm_qp_warm_start(no, nc, nul(G), nul(h), *store._args(),
+                                              index.data_ptr() if index is not None else None,
+                                              col_src.data_ptr(), nul(row_src), int(expect_tag), int(warm_mask),
+                                              float(rho_cold), x.data_ptr(), nul(y), nul(z), rho.data_ptr(),
+                                              warm.data_ptr(), count, _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_qp_warm_start")
+    return WarmStart(x, y, z, rho, warm)
 
 
 # every outcome but NON_CVX (whose iterates are NaN) / the solved ones and those out of iterations: the

@@ -98,10 +98,14 @@ class WalkerFleet:
       * ``"apply"``: every solution is applied except NON_CVX, whose iterates are NaN.
     ``polish``: :meth:`step` polishes every solved QP (:func:`mpcasm.engine.polish_qp`) between the solve and the
     next ``given``; off by default.
+    ``warm``: :meth:`step` starts every solve from the walker's last solution moved one sample along
+    (:func:`mpcasm.warm.shift_map`, :func:`mpcasm.engine.warm_start_qp`), with the step ``rho`` it ended with,
+    where that solution was SOLVED; a walker whose last QP was not solved (or held), and every walker at its
+    first tick, starts cold.  Off by default: a cold solve with OSQP's defaults every tick.
     """
 
     def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False,
-                 on_unsolved="hold", polish=False):
+                 on_unsolved="hold", polish=False, warm=False):
         from .engine import APPLY_ALL, APPLY_SOLVED, Assembler, require_device
 
         if on_unsolved not in ("hold", "apply"):
@@ -110,6 +114,9 @@ class WalkerFleet:
         # polish=True: every solved QP is polished (engine.polish_qp, OSQP's defaults) before its solution
         # becomes the walker's next `given`
         self._polish = bool(polish)
+        # warm=True: one warm store for the fleet (a record per walker, sized by the widest bucket), built with
+        # the buckets' solver buffers; per place of the step cycle the shift maps are kept with its other inputs
+        self._warm, self._warm_store = bool(warm), None
         self._apply_mask = APPLY_SOLVED if on_unsolved == "hold" else APPLY_ALL
         self._step_graphs = {}
         self._torch = require_device()
@@ -163,6 +170,12 @@ class WalkerFleet:
     def given_len(self):
         return next(iter(self.buckets.values()))["asm"].ng
 
+    @property
+    def warm_store(self):
+        """The fleet's :class:`~mpcasm.engine.WarmStore` (a record per walker, in walker order); None for a
+        fleet that is not warm, and before its first :meth:`step`."""
+        return self._warm_store
+
     def structure_of(self):
         """Steps in the preview of every walker right now (its structure bucket)."""
         return steps_in_preview(self.clock.step_times, self.N).sum(axis=1)
@@ -185,6 +198,8 @@ class WalkerFleet:
                 idx = np.nonzero(p_of == p)[0]
                 if idx.size == 0:
                     continue
+                if self._warm:     # (walkers that share the bucket of the tick before side by side)
+                    idx, groups = self._shift_groups(p, idx)
                 asm = bucket["asm"]
                 dev = asm.device
                 times = self.clock.step_times[idx]
@@ -199,9 +214,37 @@ class WalkerFleet:
                 params = asm.params.clone()
                 params[:idx.size].index_copy_(1, bucket["center_cols"], centers.repeat(1, len(bucket["facets"])))
                 index = torch.as_tensor(checked_index(idx, self.batch), device=dev)
-                entry.append(dict(p=p, idx=idx, index=index, index_long=index.long(), E=E, params=params))
+                entry.append(dict(p=p, idx=idx, index=index, index_long=index.long(), E=E, params=params, key=key))
+                if self._warm:
+                    entry[-1]["groups"] = [(a, b, torch.as_tensor(col, device=dev), torch.as_tensor(row, device=dev))
+                                           for a, b, col, row in groups]
             self._cache[key] = entry
         return self._cache[key]
+
+    def _shift_groups(self, p, idx):
+        """The walkers ``idx`` of this place's bucket ``p``, reordered so that those that were in the same bucket
+        a tick ago lie side by side, and per such group ``(first, last + 1, col_src, row_src)``: its positions
+        in the bucket's launch and the shift maps from that bucket's form to this one's, built once on the host.
+        A walker's first previewed step was taken in between exactly when its clock has just wrapped (its first
+        step time is ``step_samples - 1`` again)."""
+        from .warm import shift_map
+        times = self.clock.step_times[idx]
+        left = times[:, 0] == self.conf.step_samples - 1
+        before = times + 1
+        before[left] -= self.conf.step_samples
+        p_before = steps_in_preview(before, self.N).sum(axis=1)
+        keys = 2 * p_before + left
+        order = np.argsort(keys, kind="stable")
+        idx, keys = idx[order], keys[order]
+        groups, new = [], self.buckets[p]
+        for key in np.unique(keys):
+            at = np.flatnonzero(keys == key)
+            prev = self.buckets[int(key) // 2]
+            col, row = shift_map(prev["form"], new["form"], bool(key % 2), horizon=self.N,
+                                 prev_rows=[n for _, n in prev["asm"].plan.limit_rows],
+                                 new_rows=[n for _, n in new["asm"].plan.limit_rows])
+            groups.append((int(at[0]), int(at[-1]) + 1, col, row))
+        return idx, groups
 
     def _launch(self, given, side_by_side=False, then=None):
         """This tick's launches for ``given`` (a device tensor): ONE assembly per structure bucket
@@ -293,12 +336,16 @@ class WalkerFleet:
             row[form.given_ID[var][0]] = self.conf.strt_y
         given = self.given_buffer()
         given.copy_(self._torch.as_tensor(row, device=given.device).expand_as(given))
+        if self._warm_store is not None:      # (a warm fleet forgets its records: the first tick is cold)
+            self._warm_store.reset()
         return given
 
     def _closed_bucket(self, item, entry, stream):
         """After a bucket's assembly, on its stream: a cold solve with OSQP's defaults into the bucket's own
-        solver buffers, then its walkers' next ``given`` from the solution, by the fleet's rule."""
-        from .engine import OSQP_RHO, polish_qp, solve_qp
+        solver buffers, then its walkers' next ``given`` from the solution, by the fleet's rule.  A warm fleet:
+        the start from the store (tag: the place before), the solve from it, the store (tag: this place) after
+        the polish when there is one."""
+        from .engine import OSQP_RHO, WARM_SOLVED, WarmStore, polish_qp, solve_qp, warm_start_qp, warm_store_qp
 
         bucket = self.buckets[item["p"]]
         asm, n = bucket["asm"], item["idx"].size
@@ -314,21 +361,38 @@ class WalkerFleet:
             bucket["gmap"] = asm.given_map(biped_given_rules(bucket["form"]))
             if self._polish:
                 qp["polish"] = torch.zeros(B, **i32)
+            if self._warm:
+                qp["warm"] = torch.zeros(B, **i32)
+                if self._warm_store is None:
+                    self._warm_store = WarmStore(B, max(b["asm"].no for b in self.buckets.values()),
+                                                 max(b["asm"].nc for b in self.buckets.values()), asm.device)
         cur = self._torch.cuda.current_stream(asm.device) if stream is None else stream
         with self._torch.cuda.stream(cur):
             rho = qp["rho"][:n]
-            rho.fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
-            sol = solve_qp(entry["P"], entry["q"], entry["G"], entry["h"], rho=rho, stream=stream,
+            if self._warm:
+                period = 2 * self.conf.step_samples
+                for a, b, col_src, row_src in item["groups"]:   # (one launch per bucket of the tick before)
+                    warm_start_qp(self._warm_store, entry["G"][a:b], entry["h"][a:b], col_src, row_src,
+                                  (item["key"] - 1) % period, index=item["index"][a:b], warm_mask=WARM_SOLVED,
+                                  rho_cold=OSQP_RHO, stream=stream,
+                                  out=tuple(qp[k][a:b] for k in ("x", "y", "z", "rho", "warm")))
+            else:
+                rho.fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
+            sol = solve_qp(entry["P"], entry["q"], entry["G"], entry["h"], rho=rho, stream=stream, warm=self._warm,
                            out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")))
             if self._polish:
                 polish_qp(entry["P"], entry["q"], entry["G"], entry["h"], sol, status=sol.status, stream=stream,
                           out=(qp["polish"][:n], sol.res))
+            if self._warm:
+                warm_store_qp(self._warm_store, sol, item["key"], index=item["index"], stream=stream)
             asm.next_given(self.given_buffer(), sol.x, bucket["gmap"], index=item["index"], status=sol.status,
                            apply_mask=self._apply_mask, count=n, stream=stream)
         out = {"p": item["p"], "index": item["index"], "index_long": item["index_long"], "x": sol.x,
                "status": sol.status, "iters": sol.iters}
         if self._polish:
             out["polish"] = qp["polish"][:n]
+        if self._warm:
+            out["warm"] = qp["warm"][:n]
         return out
 
     def step(self):
@@ -337,7 +401,8 @@ class WalkerFleet:
         with OSQP's defaults, and :meth:`~mpcasm.engine.Assembler.next_given` by the fleet's
         ``on_unsolved`` rule; then the clocks advance.  Nothing is read back: returns per bucket
         ``{"p", "index": walker ids, "x", "status", "iters"}`` (device tensors in the bucket's own buffers,
-        valid until the next step; with ``polish`` also ``"polish"``, the verdicts of the polishing step).  With ``graphs``, each place of the step cycle runs its whole closed
+        valid until the next step; with ``polish`` also ``"polish"``, the verdicts of the polishing step; a warm
+        fleet starts the solve from the store instead of cold and adds ``"warm"``, which walkers started warm).  With ``graphs``, each place of the step cycle runs its whole closed
         tick as one graph (captured the first time the place comes round, after running it as it is)."""
         torch = self._torch
         given = self.given_buffer()
