@@ -702,6 +702,43 @@ int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const
                       const int32_t* d_status, uint32_t apply_mask, const int32_t* d_map, int64_t map_words,
                       void* d_work, int count, void* stream);
 
+/* The loop's commands  per-walker commands into the parameter rows of a launch ------------------------------
+ * Replaces, for a batch of walkers, the start of every tick of the walking loop
+ *   Formulation.update(**kargs)                       body.py:142-147   (the user's callbacks)
+ *   tools.update_stepping_area / find_step_centers    tools.py:149-165
+ *   Cost.update(aim=, weight=)                        goal.py:106
+ *   Constraint.update(center=, extreme=)              restrictions.py:201
+ * where what changes is a number the user commands per walker (a target velocity, where to step): a *parameter
+ * map* from a command vector per walker to elements of the parameter rows mpcasm_assemble reads, applied on the
+ * device every tick, with nothing read back; it can be captured in the tick's graph, and a replay follows later
+ * edits of the commands (their address is what the graph holds).
+ *
+ * d_params [>= batch][n_params] doubles: the parameter rows of the launch, instance b in row b.
+ * d_cmd: the command table, row w at d_cmd + w cmd_stride, ncmd doubles each (cmd_stride == 0: one row shared by
+ * the launch).  Instance b reads row w = d_index ? d_index[b] : b -- d_index (batch int32) follows the contract of
+ * mpcasm_assemble_indexed: entries inside the command table, vouched for by the host that builds them, NOT checked
+ * by the kernel.  d_sign (batch doubles, by position in the launch; may be NULL): a factor per instance, e.g. the
+ * side (-1)^(step_count + 1) of tools.find_step_centers.
+ * Record r is four int32 in d_recs, (dst, col, flags, 0), and two doubles in d_coef, (c0, c1).  It writes ONE
+ * element of every instance's row:
+ *   t = (flags & MPCASM_PMAP_SIGNED) ? c1 * d_sign[b] : c1
+ *   v = t * d_cmd[w cmd_stride + col]
+ *   d_params[b n_params + dst] = (flags & MPCASM_PMAP_CONST) ? c0 + v : v
+ * every operation rounded on its own (no fused multiply-add): a restatement on the host gives the same bits, and
+ * with c1 and the sign in {+1, -1} the element is the host's side * alternation * length exactly.
+ * Nothing else is written: elements no record names, and rows >= batch, keep their bits.  A record with dst
+ * outside [0, n_params), col outside [0, ncmd) or a flag bit other than the two writes nothing, and so does a
+ * SIGNED record of a launch without d_sign (the given map's rule: a wrong table writes nothing it should not).
+ * The records of one map must name DISTINCT dst -- the caller's contract (mpcasm/engine.py param_map_records
+ * enforces it); two records on one element leave either value.
+ * MPCASM_ERR_ARG, before any device call: a null d_params; with nrecs > 0 a null d_recs, d_coef or d_cmd;
+ * n_params < 1, nrecs < 0, ncmd < 1, batch < 0, cmd_stride < 0 or 0 < cmd_stride < ncmd.
+ * batch == 0 or nrecs == 0: MPCASM_OK, nothing launched, no device needed. */
+enum { MPCASM_PMAP_SIGNED = 1, MPCASM_PMAP_CONST = 2 };
+int mpcasm_params_map(double* d_params, int64_t n_params, const int32_t* d_recs, const double* d_coef, int nrecs,
+                      const double* d_cmd, int64_t cmd_stride, int ncmd, const int32_t* d_index,
+                      const double* d_sign, int batch, void* stream);
+
 /* f2 + the loop, per-step dynamics  the preview rows and the next `given` of a plan compiled with ltv=[...] ----
  * Replaces, for a batch whose dynamics differ from step to step and from instance to instance
  * (x_{k+1} = A_k x_k + B_k u_k: the plans the sweep kernel assembles),

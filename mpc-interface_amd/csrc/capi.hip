@@ -1965,6 +1965,20 @@ int mpcasm_qp_warm_start(int no, int nc, const double* d_G, const double* d_h, c
   return rc;
 }
 
+int mpcasm_params_map(double* d_params, int64_t n_params, const int32_t* d_recs, const double* d_coef, int nrecs,
+                      const double* d_cmd, int64_t cmd_stride, int ncmd, const int32_t* d_index,
+                      const double* d_sign, int batch, void* stream) {
+  if (!d_params || n_params < 1 || nrecs < 0 || ncmd < 1 || batch < 0 || cmd_stride < 0 ||
+      (cmd_stride > 0 && cmd_stride < ncmd) || (nrecs > 0 && (!d_recs || !d_coef || !d_cmd)))
+    return MPCASM_ERR_ARG;
+  if (batch == 0 || nrecs == 0) return MPCASM_OK;
+  hipError_t err;
+  const int rc = launch_params_map(d_params, n_params, d_recs, d_coef, nrecs, d_cmd, cmd_stride, ncmd, d_index,
+                                   d_sign, batch, static_cast<hipStream_t>(stream), &err);
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
 int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_index, int nnz,
                   double* d_dst, int batch, void* stream) {
   if (nnz < 0 || batch < 0 || src_stride < 0) return MPCASM_ERR_ARG;

@@ -188,6 +188,10 @@ int launch_qp_warm_start(int no, int nc, const double* G, const double* h, const
                          const int32_t* index, const int32_t* col_src, const int32_t* row_src, int expect_tag,
                          uint32_t warm_mask, double rho_cold, double* x, double* y, double* z, double* rho,
                          int32_t* warm, int count, hipStream_t stream, hipError_t* err);
+// params.hip: a closed loop's commands -- per-walker command columns into the parameter rows of a launch
+int launch_params_map(double* params, int64_t n_params, const int32_t* recs, const double* coef, int nrecs,
+                      const double* cmd, int64_t cmd_stride, int ncmd, const int32_t* index, const double* sign,
+                      int batch, hipStream_t stream, hipError_t* err);
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err);
 

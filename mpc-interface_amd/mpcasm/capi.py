@@ -49,6 +49,7 @@ ERR_ARG = -1
 FILL_QUAD, FILL_TINY, FILL_LTI, FILL_LTV_ROW, FILL_LTV_BLOCK, FILL_LTV_WAVE, FILL_LTV = 1, 2, 3, 4, 5, 6, 7
 FILL_GENERIC, FILL_PAD, FILL_WHOLE_LINES = 1, 2, 4
 GIVEN_KEEP, GIVEN_CONST = -1, -2     # given-map records of mpcasm_given_map_compile (a row: its index >= 0)
+PMAP_SIGNED, PMAP_CONST = 1, 2       # flags of a parameter-map record (mpcasm_params_map)
 
 
 def qp_bit(status):
@@ -143,6 +144,8 @@ SIGNATURES = {
                              [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [_void_p] * 3 +
                              [ctypes.c_int, ctypes.c_uint32, ctypes.c_double] + [_void_p] * 5 +
                              [ctypes.c_int, _void_p]),
+    "mpcasm_params_map": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, _void_p, ctypes.c_int, _void_p,
+                                         ctypes.c_int64, ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,

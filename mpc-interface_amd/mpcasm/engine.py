@@ -586,6 +586,69 @@ def given_map_records(plan, rules):
 GivenMap = collections.namedtuple("GivenMap", "table words rows values plan")
 
 
+def param_map_records(plan, rules, columns):
+    """The records of a parameter map (``mpcasm_params_map``) for ``plan``: ``(recs, coef)``, int32 ``(nrecs, 4)``
+    ``(dst, col, flags, 0)`` and float64 ``(nrecs, 2)`` ``(c0, c1)`` -- record ``r`` makes element ``dst`` of every
+    instance's parameter row ``[c0 +] (c1 [* sign]) * command[col]``.  ``columns``: the names of the command
+    columns, in order.  ``rules``: a key of ``plan.param_slots`` (``(kind, name, field)``, e.g.
+    ``("cost", "track vel_x", "aim")`` or ``("limit", 3, "center")``) -> one entry per element of the slot, as a
+    ``(rows, cols)`` nest or flat in row-major order: ``None`` (the element is kept), a column name, or a dict
+    ``{"column": name, "c1": 1.0, "signed": False, "c0": None}`` (``c0`` None: no constant is added).
+    ``KeyError``: a slot or a column that is not there; ``ValueError``: a wrong number of entries, a coefficient
+    that is not finite, two entries that reach one element.  Host only: no device needed."""
+    columns = list(columns)
+    if len(set(columns)) != len(columns):
+        raise ValueError("columns: the names must differ")
+    recs, coef, seen = [], [], set()
+    for key, rule in rules.items():
+        if key not in plan.param_slots:
+            raise KeyError("%r is not a parameter slot of this plan" % (key,))
+        start, rows, cols = plan.param_slots[key]
+        rule = list(rule) if isinstance(rule, (list, tuple)) else [rule]
+        nested = [isinstance(entry, (list, tuple)) for entry in rule]
+        if any(nested):      # (a nest is rows of cols entries, a flat list the same in row-major order)
+            if not all(nested) or len(rule) != rows or any(len(entry) != cols for entry in rule):
+                raise ValueError("%r has %d x %d elements, the rule is not shaped so" % (key, rows, cols))
+            flat = [entry for row in rule for entry in row]
+        else:
+            flat = rule
+        if len(flat) != rows * cols:
+            raise ValueError("%r has %d x %d elements, the rule names %d" % (key, rows, cols, len(flat)))
+        for e, entry in enumerate(flat):
+            if entry is None:
+                continue
+            if not isinstance(entry, dict):
+                entry = {"column": entry}
+            unknown = set(entry) - {"column", "c1", "signed", "c0"}
+            if unknown or "column" not in entry:
+                raise ValueError("%r: an entry is None, a column or a dict with 'column' and optionally 'c1', "
+                                 "'signed', 'c0'; got %r" % (key, entry))
+            if entry["column"] not in columns:
+                raise KeyError("%r is not a command column (%s)" % (entry["column"], ", ".join(map(str, columns))))
+            c0, c1 = entry.get("c0"), float(entry.get("c1", 1.0))
+            if not np.isfinite(c1) or (c0 is not None and not np.isfinite(c0)):
+                raise ValueError("%r: the coefficients must be finite" % (key,))
+            dst = start + e
+            if dst in seen:
+                raise ValueError("%r: element %d of the parameters is reached twice" % (key, dst))
+            seen.add(dst)
+            flags = (capi.PMAP_SIGNED if entry.get("signed", False) else 0) | (capi.PMAP_CONST if c0 is not None else 0)
+            recs.append((dst, columns.index(entry["column"]), flags, 0))
+            coef.append((0.0 if c0 is None else float(c0), c1))
+    return (np.asarray(recs, dtype=np.int32).reshape(-1, 4), np.asarray(coef, dtype=np.float64).reshape(-1, 2))
+
+
+ParamMap = collections.namedtuple("ParamMap", "recs coef nrecs ncmd signed columns plan host_recs host_coef")
+
+
+def check_param_map_sign(recs, sign):
+    """``ValueError`` when the records ``recs`` of a parameter map hold a signed one and ``sign`` is None: the
+    launch would leave those elements unwritten (mpcasm.h), which no caller means.  Host only."""
+    recs = np.asarray(recs).reshape(-1, 4)
+    if sign is None and recs.size and (recs[:, 2] & capi.PMAP_SIGNED).any():
+        raise ValueError("sign: this map has a signed record, it needs a sign per instance")
+
+
 def checked_index(idx, rows):
     """``idx`` as the int32 index of a launch that writes (or reads) rows of a ``rows``-row buffer by it:
     ValueError unless its entries are distinct and in ``[0, rows)`` (mpcasm.h: the kernels do not check)."""
@@ -1204,6 +1267,70 @@ class Assembler:
         want = (capi.WANT_COST if want_cost else 0) | (capi.WANT_CONSTRAINTS if want_constraints and self.nc else 0)
         return tiled_route(self.plan, self.batch if count is None else int(count), self._src_stride, want,
                            getattr(self, "_opt_path", -1))
+
+    def param_map(self, rules, columns):
+        """The device tables of a parameter map for this assembler's plan (rules and columns as
+        :func:`param_map_records`): what :meth:`apply_param_map` reads.  A map belongs to one plan -- the buckets
+        of a fleet each build their own."""
+        torch = self._torch
+        recs, coef = param_map_records(self.plan, rules, columns)
+        signed = bool(recs.size and (recs[:, 2] & capi.PMAP_SIGNED).any())
+        return ParamMap(torch.as_tensor(recs, device=self.device), torch.as_tensor(coef, device=self.device),
+                        int(recs.shape[0]), len(list(columns)), signed, tuple(columns), self.plan, recs, coef)
+
+    def apply_param_map(self, pmap, commands, index=None, sign=None, count=None, params=None, stream=None):
+        """Per-instance commands into the parameters, IN PLACE (``mpcasm_params_map``; what the callbacks of
+        ``Formulation.update`` do on the host, body.py:142-147): for the first ``count`` rows ``b`` of ``params``
+        (default :attr:`params`) every record of ``pmap`` (:meth:`param_map`) writes its element from row
+        ``index[b]`` of ``commands`` -- ``(rows, ncmd)`` float64, e.g. a whole fleet's; ``(ncmd,)``: one row
+        shared by all -- times ``sign[b]`` where the record is signed.  ``index``: contiguous int32 device tensor,
+        ``count`` entries inside ``commands`` (None: instance ``b`` reads row ``b``; the caller that builds it
+        vouches for it, an index from the host is checked and copied).  ``sign``: ``(>= count,)`` float64, required
+        when the map has a signed record (``ValueError``).  Everything no record names stays bit for bit.
+        Nothing is read back.  Returns ``params``."""
+        torch = self._torch
+        n = self.batch if count is None else int(count)
+        if not 0 <= n <= self.batch:
+            raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
+        if not isinstance(pmap, ParamMap) or pmap.plan is not self.plan:
+            raise ValueError("pmap: a map this assembler's param_map built")
+        prm = self.params if params is None else params
+        if params is not None and (tuple(params.shape) != tuple(self.params.shape) or params.dtype != torch.float64
+                                   or params.device != self.device or not params.is_contiguous()):
+            raise ValueError("params: a contiguous float64 tensor of shape %s on %s"
+                             % (tuple(self.params.shape), self.device))
+        if not (torch.is_tensor(commands) and commands.dtype == torch.float64 and commands.device == self.device
+                and commands.is_contiguous() and commands.dim() in (1, 2) and commands.shape[-1] == pmap.ncmd):
+            raise ValueError("commands: a contiguous float64 (rows, %d) or (%d,) tensor on %s"
+                             % (pmap.ncmd, pmap.ncmd, self.device))
+        shared = commands.dim() == 1
+        if index is not None and shared:
+            raise ValueError("index: one shared command row takes none")
+        if index is not None and not torch.is_tensor(index):
+            index = np.asarray(index)
+            if index.ndim != 1 or index.size < n:
+                raise ValueError("index: %d entries" % n)
+            if index.size and (index[:n].min() < 0 or index[:n].max() >= commands.shape[0]):
+                raise ValueError("index: entries in [0, %d)" % commands.shape[0])
+            index = torch.as_tensor(index[:n].astype(np.int32), device=self.device)
+        if index is not None and not (index.dtype == torch.int32 and index.device == self.device
+                                      and index.is_contiguous() and index.dim() == 1 and index.numel() >= n):
+            raise ValueError("index: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
+        if index is None and not shared and commands.shape[0] < n:
+            raise ValueError("commands must have %d rows, got %d" % (n, commands.shape[0]))
+        check_param_map_sign(pmap.host_recs, sign)
+        if sign is not None and not (torch.is_tensor(sign) and sign.dtype == torch.float64
+                                     and sign.device == self.device and sign.is_contiguous() and sign.dim() == 1
+                                     and sign.numel() >= n):
+            raise ValueError("sign: a contiguous float64 tensor of >= %d entries on %s" % (n, self.device))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_params_map(
+                prm.data_ptr(), prm.shape[1], pmap.recs.data_ptr(), pmap.coef.data_ptr(), pmap.nrecs,
+                commands.data_ptr(), 0 if shared else pmap.ncmd, pmap.ncmd, ptr(index), ptr(sign), n,
+                _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_params_map")
+        return prm
 
     def given_map(self, rules):
         """The device table of a given map for this assembler's plan (``mpcasm_given_map_compile``; rules as

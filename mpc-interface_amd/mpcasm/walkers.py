@@ -16,6 +16,10 @@ centres (per-instance parameters) and the given vector.
 :meth:`WalkerFleet.step` closes the loop on the device (biped_mpc_loop.py:50-95 for every walker):
 assemble, solve to tolerance, and write each walker's next ``given`` from its solution
 (:func:`biped_given_rules`, the reference's update_given_collector), with nothing read back.
+
+``WalkerFleet(..., commands=True)`` steers the fleet: a device table of commands per walker (target velocity, where
+to step) becomes, every tick and on the device, the parameters the reference's ``Formulation.update`` callbacks set
+on the host (body.py:142-147, tools.update_stepping_area) -- :func:`biped_command_rules`, ``mpcasm_params_map``.
 """
 import numpy as np
 
@@ -63,6 +67,34 @@ def biped_given_rules(form):
     return rules
 
 
+# the commands of a walker on the biped formulation, in the order of the columns of WalkerFleet.commands
+COMMAND_COLUMNS = ("vel_x", "vel_y", "step_x", "step_y")
+
+
+def stepping_area_facets(form):
+    """Indices (as in ``("limit", k, field)`` of a plan's ``param_slots``) of the facets of the biped's stepping
+    area: it is the first box, so its facets are the first limits after the plain constraints."""
+    first = sum(len(group) for group in form.constraints.values())
+    return range(first, first + len(form.constraint_boxes["stepping area"].constraints))
+
+
+def biped_command_rules(form):
+    """What a walker's commands :data:`COMMAND_COLUMNS` set, as the rules of a parameter map
+    (:meth:`mpcasm.engine.Assembler.param_map`) for ``form``, a biped formulation updated to its place in the step
+    cycle: ``vel_x``, ``vel_y`` are the aims of the costs ``"track vel_x"``, ``"track vel_y"`` (the configuration's
+    ``target_vel``); ``step_x``, ``step_y`` (its ``stepping_center``) place the centres of every facet of the
+    ``"stepping area"`` box -- previewed step ``j``: ``center[j] = (step_x, sign * (+1, -1, +1, ...)[j] * step_y)``,
+    which is tools.find_step_centers (tools.py:158-165) with the walker's ``side = (-1)^(step_count + 1)``
+    supplied per instance as the launch's ``sign``."""
+    rules = {("cost", "track vel_x", "aim"): ["vel_x"], ("cost", "track vel_y", "aim"): ["vel_y"]}
+    box = form.constraint_boxes["stepping area"]
+    for k, limit in zip(stepping_area_facets(form), box.constraints):
+        p = np.atleast_2d(limit.center).shape[0]
+        rules[("limit", k, "center")] = [
+            ["step_x", {"column": "step_y", "signed": True, "c1": 1.0 if j % 2 == 0 else -1.0}] for j in range(p)]
+    return rules
+
+
 class FleetClock:
     """Vectorised step-time bookkeeping (biped_mpc_loop.py:41-45): every tick the step
     times count down; when the first reaches -1 they wrap by ``step_samples`` and the
@@ -102,10 +134,26 @@ class WalkerFleet:
     (:func:`mpcasm.warm.shift_map`, :func:`mpcasm.engine.warm_start_qp`), with the step ``rho`` it ended with,
     where that solution was SOLVED; a walker whose last QP was not solved (or held), and every walker at its
     first tick, starts cold.  Off by default: a cold solve with OSQP's defaults every tick.
+    ``commands``: the fleet can be steered.  :attr:`commands` is a device ``(batch, 4)`` float64 tensor in walker
+    order, one row of :data:`COMMAND_COLUMNS` per walker, that starts from ``conf`` (``target_vel[0]``,
+    ``target_vel[1]``, ``stepping_center[0]``, ``stepping_center[1]``); write it in place (or through
+    :meth:`set_commands`) at any time.  Every :meth:`tick` and :meth:`step`, per bucket and ahead of its assembly,
+    one :meth:`~mpcasm.engine.Assembler.apply_param_map` writes the walkers' commands into rows ``[:n]`` of the
+    bucket's own ``asm.params`` (:func:`biped_command_rules`), on the device, and the assembly reads
+    ``asm.params`` itself: no copy of the parameters is kept per place of the step cycle.  A captured graph holds
+    that launch and the address of :attr:`commands`, so replays follow later edits.  In this mode ``asm.params``
+    of each bucket is the authoritative tensor: an edit of a field that is not commanded, made on a bucket's
+    assembler (``fleet.buckets[p]["asm"].set_param("cost", "minimize jerk", "weight", ...)``), holds from the next
+    tick on, replays included (its rows are positions in the bucket's launch, not walkers: set such a field for
+    all rows alike, or command it).  ``command_rules = (rules_for_form, columns)`` or ``(rules_for_form, columns,
+    initial values)`` swaps in another map -- ``rules_for_form(form)`` returns a bucket's rules, for weights,
+    margins or any other parameter; columns that are none of :data:`COMMAND_COLUMNS` start at the initial values
+    (zero without).  Off by default: every walker keeps ``conf``'s gait and the parameters of a place are fixed
+    the first time it comes round.
     """
 
     def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False,
-                 on_unsolved="hold", polish=False, warm=False):
+                 on_unsolved="hold", polish=False, warm=False, commands=False, command_rules=None):
         from .engine import APPLY_ALL, APPLY_SOLVED, Assembler, require_device
 
         if on_unsolved not in ("hold", "apply"):
@@ -165,6 +213,22 @@ class WalkerFleet:
                 cols.extend(range(sl.start, sl.stop))
             self.buckets[p] = dict(form=form, asm=asm, E=E, facets=facets,
                                    center_cols=torch.as_tensor(cols, dtype=torch.int64, device=asm.device))
+        # commands=True: a parameter map per bucket and the fleet's command table, a row per walker
+        self._commands = bool(commands) or command_rules is not None
+        self.commands = self.command_columns = None
+        if self._commands:
+            rules_for, columns, initial = (tuple(command_rules) + (None,))[:3] if command_rules is not None \
+                else (biped_command_rules, COMMAND_COLUMNS, None)
+            columns = tuple(columns)
+            for bucket in self.buckets.values():
+                bucket["pmap"] = bucket["asm"].param_map(rules_for(bucket["form"]), columns)
+            known = dict(zip(COMMAND_COLUMNS, (self.conf.target_vel[0], self.conf.target_vel[1],
+                                               self.conf.stepping_center[0], self.conf.stepping_center[1])))
+            row = np.array([float(known.get(c, 0.0)) for c in columns]) if initial is None \
+                else np.asarray(initial, dtype=np.float64).reshape(len(columns))
+            dev = next(iter(self.buckets.values()))["asm"].device
+            self.command_columns = columns
+            self.commands = self._torch.as_tensor(np.tile(row, (self.batch, 1)), device=dev).contiguous()
 
     @property
     def given_len(self):
@@ -175,6 +239,25 @@ class WalkerFleet:
         """The fleet's :class:`~mpcasm.engine.WarmStore` (a record per walker, in walker order); None for a
         fleet that is not warm, and before its first :meth:`step`."""
         return self._warm_store
+
+    def set_commands(self, values, walkers=None):
+        """Write :attr:`commands` in place without waiting for the device: ``values`` (tensor or array) is
+        ``(batch, ncols)`` -- or ``(ncols,)``, the same for all -- or, with ``walkers`` (ids), one row per walker
+        named.  The next tick reads them, a replayed graph included."""
+        if not self._commands:
+            raise ValueError("this fleet takes no commands (WalkerFleet(..., commands=True))")
+        torch = self._torch
+        cmd = self.commands
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values, dtype=np.float64))
+        v = v.to(device=cmd.device, dtype=cmd.dtype, non_blocking=True)
+        if walkers is None:
+            cmd.copy_(v.expand_as(cmd))
+        else:
+            ids = np.asarray(walkers, dtype=np.int64).reshape(-1)
+            if ids.size and (ids.min() < 0 or ids.max() >= self.batch or np.unique(ids).size != ids.size):
+                raise ValueError("walkers: distinct ids in [0, %d)" % self.batch)
+            cmd.index_copy_(0, torch.as_tensor(ids, device=cmd.device), v.expand(ids.size, cmd.shape[1]))
+        return cmd
 
     def structure_of(self):
         """Steps in the preview of every walker right now (its structure bucket)."""
@@ -206,15 +289,24 @@ class WalkerFleet:
                 kept = times[steps_in_preview(times, self.N)].reshape(idx.size, p)
                 E = torch.zeros((self.batch, self.N, p, 1), dtype=torch.float64, device=dev)
                 E[:idx.size, :, :, 0] = torch.as_tensor(step_indicator(kept, self.N), device=dev)
-                centers = stepping_centers(self.clock.step_count[idx], p, self.conf.stepping_center)
-                centers = torch.as_tensor(centers.reshape(idx.size, -1), device=dev)
-                # the bucket's parameters at this place of the cycle: the assembler's own, with the centres
-                # of the stepping area of these walkers in their columns -- a tensor per place, so that a
-                # tick copies nothing (only the centres change with the place in the cycle)
-                params = asm.params.clone()
-                params[:idx.size].index_copy_(1, bucket["center_cols"], centers.repeat(1, len(bucket["facets"])))
                 index = torch.as_tensor(checked_index(idx, self.batch), device=dev)
-                entry.append(dict(p=p, idx=idx, index=index, index_long=index.long(), E=E, params=params, key=key))
+                if self._commands:
+                    # a steered fleet keeps no parameters per place: the walkers' side (tools.find_step_centers:
+                    # (-1)^(step_count + 1)), the sign of the tick's parameter map, is all the place adds
+                    side = (-1.0) ** (self.clock.step_count[idx] + 1)
+                    entry.append(dict(p=p, idx=idx, index=index, index_long=index.long(), E=E, params=None, key=key,
+                                      sign=torch.as_tensor(side, dtype=torch.float64, device=dev)))
+                else:
+                    centers = stepping_centers(self.clock.step_count[idx], p, self.conf.stepping_center)
+                    centers = torch.as_tensor(centers.reshape(idx.size, -1), device=dev)
+                    # the bucket's parameters at this place of the cycle: the assembler's own, with the centres
+                    # of the stepping area of these walkers in their columns -- a tensor per place, so that a
+                    # tick copies nothing (only the centres change with the place in the cycle)
+                    params = asm.params.clone()
+                    params[:idx.size].index_copy_(1, bucket["center_cols"],
+                                                  centers.repeat(1, len(bucket["facets"])))
+                    entry.append(dict(p=p, idx=idx, index=index, index_long=index.long(), E=E, params=params,
+                                      key=key))
                 if self._warm:
                     entry[-1]["groups"] = [(a, b, torch.as_tensor(col, device=dev), torch.as_tensor(row, device=dev))
                                            for a, b, col, row in groups]
@@ -277,6 +369,9 @@ class WalkerFleet:
                     stream.wait_stream(cur)
             elif self._side:
                 asm.set_option(capi.OPT_RESIDENT_GRID, -1)
+            if self._commands:   # (the walkers' commands into the bucket's own parameters, ahead of the assembly)
+                asm.apply_param_map(bucket["pmap"], self.commands, index=item["index"], sign=item["sign"],
+                                    count=idx.size, stream=stream)
             # (no gather, no copy: the walkers' rows of `given` by index, the place's own parameters)
             P, q, G, h = asm.assemble(given, count=idx.size, index=item["index"], params=item["params"],
                                       stream=stream)
