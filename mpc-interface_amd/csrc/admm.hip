@@ -32,15 +32,12 @@
 
 #include <algorithm>
 
-#include "device_prims.h"
 #include "kernels.h"
+#include "qp_prims.h"
 
 namespace mpcasm {
 
 namespace {
-
-constexpr int ADMM_BLOCK = 256;
-constexpr int ADMM_WAVES = ADMM_BLOCK / 64;
 
 struct AdmmLds {
   int mi, gs, x, q, z, y, h, v, r, xt, pa, pb, total, ld, lp;
@@ -59,51 +56,12 @@ __host__ __device__ inline AdmmLds admm_lds(int no, int nc) {
   L.v = L.h + nc;                     // rho z - y
   L.r = L.v + nc;                     // the right-hand side
   L.xt = L.r + no;
-  L.pa = L.xt + no;                   // [ADMM_WAVES][lp] partial sums of G'v, then of G xt
-  L.pb = L.pa + ADMM_WAVES * L.lp;    // [ADMM_WAVES][no] partial sums of K^-1 r
-  L.total = L.pb + ADMM_WAVES * no;
+  L.pa = L.xt + no;                   // [QP_WAVES][lp] partial sums of G'v, then of G xt
+  L.pb = L.pa + QP_WAVES * L.lp;    // [QP_WAVES][no] partial sums of K^-1 r
+  L.total = L.pb + QP_WAVES * no;
   L.total += L.total & 1;
   return L;
 }
-
-// sum_i a[i sa] b[i sb], i < n: four sums side by side, eight pairs of reads in flight -- the loop must
-// not be one dependent chain of read -> fma
-__device__ __forceinline__ double dot4(const double* a, int sa, const double* b, int sb, int n, double init) {
-  double s0 = init, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  int i = 0;
-  for (; i + 8 <= n; i += 8) {
-    double av[8], bv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) av[u] = a[(i + u) * sa], bv[u] = b[(i + u) * sb];
-    s0 = fma(av[0], bv[0], s0);
-    s1 = fma(av[1], bv[1], s1);
-    s2 = fma(av[2], bv[2], s2);
-    s3 = fma(av[3], bv[3], s3);
-    s0 = fma(av[4], bv[4], s0);
-    s1 = fma(av[5], bv[5], s1);
-    s2 = fma(av[6], bv[6], s2);
-    s3 = fma(av[7], bv[7], s3);
-  }
-  for (; i + 4 <= n; i += 4) {
-    const double a0 = a[i * sa], a1 = a[(i + 1) * sa], a2 = a[(i + 2) * sa], a3 = a[(i + 3) * sa];
-    const double b0 = b[i * sb], b1 = b[(i + 1) * sb], b2 = b[(i + 2) * sb], b3 = b[(i + 3) * sb];
-    s0 = fma(a0, b0, s0);
-    s1 = fma(a1, b1, s1);
-    s2 = fma(a2, b2, s2);
-    s3 = fma(a3, b3, s3);
-  }
-  for (; i < n; ++i) s0 = fma(a[i * sa], b[i * sb], s0);
-  return (s0 + s1) + (s2 + s3);
-}
-
-// what the solve mode adds to the kernel's arguments (unused by the plain iteration)
-struct SolveArgs {
-  double* rho;        // [batch] in: the step an instance starts with; out: the one it ended with
-  int32_t* status;    // [batch] MPCASM_QP_*
-  int32_t* iters;     // [batch] the iterations an instance ran
-  double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
-  int check_every, adaptive_rho_interval;
-};
 
 // One workgroup of four wavefronts per instance.  Everything that is a sum over rows or columns is cut in
 // four -- wavefront w takes the terms i = w, w + 4, ... -- and the partial sums meet in LDS behind a barrier:
@@ -112,7 +70,7 @@ struct SolveArgs {
 // SOLVE: `iters` is max_iter, rho is the instance's s.rho[inst] and the loop ends at the first check that
 // decides; the iterates of the plain iteration are the same as before.
 template <bool SOLVE>
-__global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
+__global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
     int no, int nc, const double* __restrict__ P, const double* __restrict__ q,
     const double* __restrict__ G, const double* __restrict__ h, double* __restrict__ X,
     double* __restrict__ Y, double* __restrict__ Z, double* __restrict__ res, double rho, double sigma,
@@ -139,7 +97,7 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
   const double* Pb = P + (size_t)inst * no * no;
   const double* Gb = G + (size_t)inst * nc * no;
   auto load_g = [&]() {
-    for (int e = tid; e < nc * no; e += ADMM_BLOCK) {
+    for (int e = tid; e < nc * no; e += QP_BLOCK) {
       const int r = e / no, c = e - r * no;
       Gs[r * ld + c] = Gb[e];
     }
@@ -151,11 +109,11 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
   if constexpr (SOLVE) rho = s.rho[inst];
   const bool reuse = Kinv != nullptr && kinv_valid != 0;
   load_g();
-  for (int e = tid; e < no; e += ADMM_BLOCK) {
+  for (int e = tid; e < no; e += QP_BLOCK) {
     qs[e] = q[(size_t)inst * no + e];
     xs[e] = warm ? X[(size_t)inst * no + e] : 0.0;
   }
-  for (int e = tid; e < nc; e += ADMM_BLOCK) {
+  for (int e = tid; e < nc; e += QP_BLOCK) {
     const double hv = h[(size_t)inst * nc + e];
     hs[e] = hv;
     ys[e] = warm ? Y[(size_t)inst * nc + e] : 0.0;
@@ -166,7 +124,7 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
   // K from G in LDS and P in memory, factored and inverted into Mi (false: K is not positive definite);
   // the solve mode calls it again when rho moves
   auto factor = [&]() -> bool {
-    for (int e = tid; e < no * no; e += ADMM_BLOCK) {
+    for (int e = tid; e < no * no; e += QP_BLOCK) {
       const int a = e / no, b = e - a * no;
       const double acc = dot4(Gs + a, ld, Gs + b, ld, nc, 0.0);
       Mi[a * ld + b] = fma(rho, acc, Pb[e]) + (a == b ? sigma : 0.0);
@@ -179,35 +137,35 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
       good = good && dkk > 0.0;
       const double d = sqrt(dkk > 0.0 ? dkk : 1.0);
       __syncthreads();
-      for (int i = k + tid; i < no; i += ADMM_BLOCK) Mi[i * ld + k] = i == k ? d : Mi[i * ld + k] / d;
+      for (int i = k + tid; i < no; i += QP_BLOCK) Mi[i * ld + k] = i == k ? d : Mi[i * ld + k] / d;
       __syncthreads();
       // the trailing block: wavefront w takes the rows k + 1 + w, + 4, ..., a lane the column k + 1 + lane
       // (+ 64, ... for more unknowns than lanes) up to the diagonal
       for (int j = k + 1 + lane; j < no; j += 64) {
         const double ljk = Mi[j * ld + k];
-        for (int i = k + 1 + wave + (j > k + 1 + wave ? ((j - k - 1 - wave + ADMM_WAVES - 1) / ADMM_WAVES) * ADMM_WAVES : 0);
-             i < no; i += ADMM_WAVES)
+        for (int i = k + 1 + wave + (j > k + 1 + wave ? ((j - k - 1 - wave + QP_WAVES - 1) / QP_WAVES) * QP_WAVES : 0);
+             i < no; i += QP_WAVES)
           Mi[i * ld + j] = fma(-Mi[i * ld + k], ljk, Mi[i * ld + j]);
       }
       __syncthreads();
     }
     // ---- T = L^-1: thread c solves L t = e_c (rows above c stay zero) --------------------------------
     double* T = Gs;
-    for (int c = tid; c < no; c += ADMM_BLOCK)
+    for (int c = tid; c < no; c += QP_BLOCK)
       for (int i = 0; i < no; ++i) {
         const double sv = (i == c ? 1.0 : 0.0) - (i > c ? dot4(Mi + i * ld + c, 1, T + c * ld + c, ld, i - c, 0.0) : 0.0);
         T[i * ld + c] = i < c ? 0.0 : sv / Mi[i * ld + i];
       }
     __syncthreads();
     // ---- K^-1 = T' T ---------------------------------------------------------------------------------
-    for (int e = tid; e < no * no; e += ADMM_BLOCK) {
+    for (int e = tid; e < no * no; e += QP_BLOCK) {
       const int a = e / no, b = e - a * no;
       const int i0 = a > b ? a : b;
       Mi[a * ld + b] = dot4(T + i0 * ld + a, ld, T + i0 * ld + b, ld, no - i0, 0.0);
     }
     __syncthreads();
     if (Kinv != nullptr)
-      for (int e = tid; e < no * no; e += ADMM_BLOCK)
+      for (int e = tid; e < no * no; e += QP_BLOCK)
         Kinv[(size_t)inst * no * no + e] = good ? Mi[(e / no) * ld + e % no] : __builtin_nan("");
     load_g();   // (the factorisation used G's place for L^-1)
     __syncthreads();
@@ -218,9 +176,9 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
   if (SOLVE && !(rho > 0.0)) {   // (no step to take: the solve calls the instance not convex)
     ok = false;
     if (Kinv != nullptr)
-      for (int e = tid; e < no * no; e += ADMM_BLOCK) Kinv[(size_t)inst * no * no + e] = __builtin_nan("");
+      for (int e = tid; e < no * no; e += QP_BLOCK) Kinv[(size_t)inst * no * no + e] = __builtin_nan("");
   } else if (reuse) {
-    for (int e = tid; e < no * no; e += ADMM_BLOCK) Mi[(e / no) * ld + e % no] = Kinv[(size_t)inst * no * no + e];
+    for (int e = tid; e < no * no; e += QP_BLOCK) Mi[(e / no) * ld + e % no] = Kinv[(size_t)inst * no * no + e];
     __syncthreads();
   } else {
     ok = factor();
@@ -230,10 +188,10 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
   // several reads in flight (dot4) -------------------------------------------------------------------------
   double inv_rho = 1.0 / rho;
   // wavefront w's share of a sum over `count` terms: i = w, w + 4, ...
-  const int rows_w = nc > wave ? (nc - wave + ADMM_WAVES - 1) / ADMM_WAVES : 0;
-  const int cols_w = no > wave ? (no - wave + ADMM_WAVES - 1) / ADMM_WAVES : 0;
+  const int rows_w = nc > wave ? (nc - wave + QP_WAVES - 1) / QP_WAVES : 0;
+  const int cols_w = no > wave ? (no - wave + QP_WAVES - 1) / QP_WAVES : 0;
   int status = ok ? MPCASM_QP_MAX_ITER : MPCASM_QP_NON_CVX, ran = ok ? iters : 0;
-  for (int r = tid; r < nc; r += ADMM_BLOCK) vs[r] = fma(rho, zs[r], -ys[r]);
+  for (int r = tid; r < nc; r += QP_BLOCK) vs[r] = fma(rho, zs[r], -ys[r]);
   __syncthreads();
   for (int it = 0; it < (SOLVE && !ok ? 0 : iters); ++it) {
     // (solve mode: a check after this iteration -- it keeps the step dx in pb, dy in pa)
@@ -241,16 +199,16 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     const bool due = SOLVE && (k % s.check_every == 0 || k == iters);
     // pa[w][c] = sum over this wavefront's rows of G[r][c] v[r]
     for (int c = lane; c < no; c += 64)
-      pa[wave * lp + c] = dot4(Gs + wave * ld + c, ADMM_WAVES * ld, vs + wave, ADMM_WAVES, rows_w, 0.0);
+      pa[wave * lp + c] = dot4(Gs + wave * ld + c, QP_WAVES * ld, vs + wave, QP_WAVES, rows_w, 0.0);
     __syncthreads();
-    for (int b = tid; b < no; b += ADMM_BLOCK)
+    for (int b = tid; b < no; b += QP_BLOCK)
       rv[b] = fma(sigma, xs[b], -qs[b]) + ((pa[b] + pa[lp + b]) + (pa[2 * lp + b] + pa[3 * lp + b]));
     __syncthreads();
     // pb[w][c] = sum over this wavefront's b of K^-1[c][b] r[b]
     for (int c = lane; c < no; c += 64)
-      pbuf[wave * no + c] = dot4(Mi + c * ld + wave, ADMM_WAVES, rv + wave, ADMM_WAVES, cols_w, 0.0);
+      pbuf[wave * no + c] = dot4(Mi + c * ld + wave, QP_WAVES, rv + wave, QP_WAVES, cols_w, 0.0);
     __syncthreads();
-    for (int c = tid; c < no; c += ADMM_BLOCK) {
+    for (int c = tid; c < no; c += QP_BLOCK) {
       const double xtc = (pbuf[c] + pbuf[no + c]) + (pbuf[2 * no + c] + pbuf[3 * no + c]);
       const double xo = xs[c], xn = fma(alpha, xtc, (1.0 - alpha) * xo);
       xt[c] = xtc;
@@ -260,9 +218,9 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     __syncthreads();
     // pa[w][r] = sum over this wavefront's c of G[r][c] xt[c]
     for (int r = lane; r < nc; r += 64)
-      pa[wave * lp + r] = dot4(Gs + r * ld + wave, ADMM_WAVES, xt + wave, ADMM_WAVES, cols_w, 0.0);
+      pa[wave * lp + r] = dot4(Gs + r * ld + wave, QP_WAVES, xt + wave, QP_WAVES, cols_w, 0.0);
     __syncthreads();
-    for (int r = tid; r < nc; r += ADMM_BLOCK) {
+    for (int r = tid; r < nc; r += QP_BLOCK) {
       const double zt = (pa[r] + pa[lp + r]) + (pa[2 * lp + r] + pa[3 * lp + r]);
       const double zr = fma(alpha, zt, (1.0 - alpha) * zs[r]);
       const double zn = fmin(fma(ys[r], inv_rho, zr), hs[r]);
@@ -316,21 +274,14 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
           if (wave == 0) pa[0] = a0, pa[1] = a1;
           else if (wave == 1) pa[2] = a0, pa[3] = a1;
           else if (wave == 2)
-            pbuf[0] = a0 > 1e-30 && a1 < -s.eps_prim_inf * a0 && a2 < s.eps_prim_inf * a0 ? 1.0 : 0.0;
+            pbuf[0] = qp_primal_infeasible(s, a0, a1, a2) ? 1.0 : 0.0;
           else
-            pbuf[1] = a0 > 1e-30 && a1 < -s.eps_dual_inf * a0 && a2 < s.eps_dual_inf * a0 &&
-                      a3 < s.eps_dual_inf * a0 ? 1.0 : 0.0;
+            pbuf[1] = qp_dual_infeasible(s, a0, a1, a2, a3) ? 1.0 : 0.0;
         }
         __syncthreads();
         const double rp = pa[0], sp = pa[1], rd = pa[2], sd = pa[3];
-        const int verdict = rp <= s.eps_abs + s.eps_rel * sp && rd <= s.eps_abs + s.eps_rel * sd ? MPCASM_QP_SOLVED
-                            : pbuf[0] != 0.0 ? MPCASM_QP_PRIMAL_INFEASIBLE
-                            : pbuf[1] != 0.0 ? MPCASM_QP_DUAL_INFEASIBLE : 0;
-        double rn = rho;   // (OSQP's step: the two residuals equally far from their tolerances; NaN: no move)
-        if (verdict == 0 && s.adaptive_rho_interval > 0 && k % s.adaptive_rho_interval == 0 && k < iters) {
-          rn = rho * sqrt((rp / (sp + 1e-30)) / (rd / (sd + 1e-30)));
-          rn = rn < 1e-6 ? 1e-6 : rn > 1e6 ? 1e6 : rn;
-        }
+        const int verdict = qp_verdict(s, rp, sp, rd, sd, pbuf[0] != 0.0, pbuf[1] != 0.0);
+        const double rn = qp_next_rho(s, rho, verdict, k, iters, rp, sp, rd, sd);
         __syncthreads();   // (the verdicts read by every thread: the next phase writes over them)
         if (verdict != 0) {
           status = verdict;
@@ -346,7 +297,7 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
             ran = k;
             break;
           }
-          for (int r = tid; r < nc; r += ADMM_BLOCK) vs[r] = fma(rho, zs[r], -ys[r]);
+          for (int r = tid; r < nc; r += QP_BLOCK) vs[r] = fma(rho, zs[r], -ys[r]);
           __syncthreads();
         }
       }
@@ -362,15 +313,15 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
 
   // ---- results; OSQP's residuals |Gx - z|_inf, |Px + q + G'y|_inf -------------------------------
   const double bad = __builtin_nan("");
-  for (int c = tid; c < no; c += ADMM_BLOCK) X[(size_t)inst * no + c] = ok ? xs[c] : bad;
-  for (int r = tid; r < nc; r += ADMM_BLOCK) {
+  for (int c = tid; c < no; c += QP_BLOCK) X[(size_t)inst * no + c] = ok ? xs[c] : bad;
+  for (int r = tid; r < nc; r += QP_BLOCK) {
     Y[(size_t)inst * nc + r] = ok ? ys[r] : bad;
     Z[(size_t)inst * nc + r] = ok ? zs[r] : bad;
   }
   if (res != nullptr) {
     double rp = 0.0, rd = 0.0;
-    for (int r = tid; r < nc; r += ADMM_BLOCK) rp = fmax(rp, fabs(dot4(Gs + r * ld, 1, xs, 1, no, 0.0) - zs[r]));
-    for (int c = tid; c < no; c += ADMM_BLOCK) {
+    for (int r = tid; r < nc; r += QP_BLOCK) rp = fmax(rp, fabs(dot4(Gs + r * ld, 1, xs, 1, no, 0.0) - zs[r]));
+    for (int c = tid; c < no; c += QP_BLOCK) {
       double acc = qs[c];
       for (int b = 0; b < no; ++b) acc = fma(Pb[(size_t)c * no + b], xs[b], acc);
       rd = fmax(rd, fabs(dot4(Gs + c, ld, ys, 1, nc, acc)));
@@ -381,13 +332,13 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
     }
     if (lane == 0) {
       pbuf[wave] = rp;
-      pbuf[ADMM_WAVES + wave] = rd;
+      pbuf[QP_WAVES + wave] = rd;
     }
     __syncthreads();
     if (tid == 0) {
-      for (int w = 1; w < ADMM_WAVES; ++w) {
+      for (int w = 1; w < QP_WAVES; ++w) {
         rp = fmax(rp, pbuf[w]);
-        rd = fmax(rd, pbuf[ADMM_WAVES + w]);
+        rd = fmax(rd, pbuf[QP_WAVES + w]);
       }
       res[inst * 2 + 0] = ok ? rp : bad;
       res[inst * 2 + 1] = ok ? rd : bad;
@@ -399,39 +350,17 @@ __global__ __launch_bounds__(ADMM_BLOCK) void admm_kernel(
 
 size_t admm_lds_bytes(int no, int nc) { return (size_t)admm_lds(no, nc).total * sizeof(double); }
 
-int launch_admm(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                double* x, double* y, double* z, double* res, double rho, double sigma, double alpha,
-                int iters, int warm, int batch, double* kinv, int kinv_valid, hipStream_t stream,
-                hipError_t* err) {
-  const size_t lds = admm_lds_bytes(no, nc);
-  if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
-  if (lds > 64 * 1024) {
-    *err = allow_whole_lds(reinterpret_cast<const void*>(admm_kernel<false>));
-    if (*err != hipSuccess) return MPCASM_ERR_HIP;
-  }
-  hipLaunchKernelGGL(admm_kernel<false>, dim3((unsigned)batch), dim3(ADMM_BLOCK), lds, stream, no, nc, P, q, G,
-                     h, x, y, z, res, rho, sigma, alpha, iters, warm, batch, kinv, kinv_valid, SolveArgs{});
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+int launch_admm(const QpBatch& b, double rho, const QpSolve& s, hipStream_t stream, hipError_t* err) {
+  return launch_with_lds(admm_kernel<false>, (unsigned)b.batch, QP_BLOCK, admm_lds_bytes(b.no, b.nc), stream, err,
+                         b.no, b.nc, b.P, b.q, b.G, b.h, b.x, b.y, b.z, s.res, rho, s.sigma, s.alpha, s.max_iter,
+                         s.warm, b.batch, s.kinv, s.kinv_valid, SolveArgs{});
 }
 
-int launch_qp_solve(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                    double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
-                    double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
-                    int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
-                    int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err) {
-  const size_t lds = admm_lds_bytes(no, nc);   // (the solve mode's scratch lies in the same layout)
-  if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
-  if (lds > 64 * 1024) {
-    *err = allow_whole_lds(reinterpret_cast<const void*>(admm_kernel<true>));
-    if (*err != hipSuccess) return MPCASM_ERR_HIP;
-  }
-  const SolveArgs s{rho, status, iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
-                    adaptive_rho_interval};
-  hipLaunchKernelGGL(admm_kernel<true>, dim3((unsigned)batch), dim3(ADMM_BLOCK), lds, stream, no, nc, P, q, G,
-                     h, x, y, z, res, 0.0, sigma, alpha, max_iter, warm, batch, kinv, kinv_valid, s);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+int launch_qp_solve(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipError_t* err) {
+  // (the solve mode's scratch lies in the same layout)
+  return launch_with_lds(admm_kernel<true>, (unsigned)b.batch, QP_BLOCK, admm_lds_bytes(b.no, b.nc), stream, err,
+                         b.no, b.nc, b.P, b.q, b.G, b.h, b.x, b.y, b.z, s.res, 0.0, s.sigma, s.alpha, s.max_iter,
+                         s.warm, b.batch, s.kinv, s.kinv_valid, static_cast<const SolveArgs&>(s));
 }
 
 }  // namespace mpcasm

@@ -29,13 +29,12 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "qp_prims.h"
 
 namespace mpcasm {
 
 namespace {
 
-constexpr int WIDE_BLOCK = 256;
-constexpr int WIDE_WAVES = WIDE_BLOCK / 64;
 constexpr int WIDE_ROWS = 4;   // rows of G a wavefront keeps in flight in the pass
 constexpr int WIDE_MAX_NO = 512;
 
@@ -51,42 +50,25 @@ __host__ __device__ inline WideLds wide_lds(int no, int nc, bool onchip) {
   L.xs = L.h + nc;             // x, for the rows of P x (checks)
   L.dx = L.xs + no;            // dx, for P dx (checks)
   L.rv = L.dx + no;            // r; the factorisation's column
-  L.pa = L.rv + no;            // [WIDE_WAVES][no] partial sums of G'v
-  L.pb = L.pa + WIDE_WAVES * no;   // of G'y (checks)
-  L.pc = L.pb + WIDE_WAVES * no;   // of G'dy (checks)
-  L.pk = L.pc + WIDE_WAVES * no;   // of K^-1 r; of P x (checks)
-  L.pe = L.pk + WIDE_WAVES * no;   // of P dx (checks)
-  L.red = L.pe + WIDE_WAVES * no;  // [WIDE_WAVES][16] a wavefront's row verdict terms
-  L.mi = L.red + WIDE_WAVES * 16;
+  L.pa = L.rv + no;            // [QP_WAVES][no] partial sums of G'v
+  L.pb = L.pa + QP_WAVES * no;   // of G'y (checks)
+  L.pc = L.pb + QP_WAVES * no;   // of G'dy (checks)
+  L.pk = L.pc + QP_WAVES * no;   // of K^-1 r; of P x (checks)
+  L.pe = L.pk + QP_WAVES * no;   // of P dx (checks)
+  L.red = L.pe + QP_WAVES * no;  // [QP_WAVES][16] a wavefront's row verdict terms
+  L.mi = L.red + QP_WAVES * 16;
   L.total = L.mi + (onchip ? no * L.ld : 0);
   L.total += L.total & 1;
   return L;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);   // (every lane the same bits)
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-struct WideArgs {
-  double* rho;
-  int32_t* status;
-  int32_t* iters;
-  double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
-  int check_every, adaptive_rho_interval;
-};
-
 // NCH: columns per lane (no <= 64 NCH); ONCHIP: K^-1 in LDS
 template <int NCH, bool ONCHIP>
-__global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
+__global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
     int no, int nc, const double* __restrict__ P, const double* __restrict__ q, const double* __restrict__ G,
     const double* __restrict__ h, double* __restrict__ X, double* __restrict__ Y, double* __restrict__ Z,
     double* __restrict__ res, double sigma, double alpha, int iters, int warm, int batch, double* Kinv,
-    int kinv_valid, WideArgs s) {
+    int kinv_valid, SolveArgs s) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -120,7 +102,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     qr[c] = j < no ? q[(size_t)inst * no + j] : 0.0;
     xr[c] = j < no && warm ? X[(size_t)inst * no + j] : 0.0;
   }
-  for (int e = tid; e < nc; e += WIDE_BLOCK) {
+  for (int e = tid; e < nc; e += QP_BLOCK) {
     const double hv = h[(size_t)inst * nc + e];
     hs[e] = hv;
     ys[e] = warm ? Y[(size_t)inst * nc + e] : 0.0;
@@ -133,7 +115,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     const int lda = kld;
     __syncthreads();
     // wavefront w forms the rows a = w + 4 t, four at a time: one sweep over G's rows serves the four
-    for (int a0 = wave; a0 < no; a0 += WIDE_WAVES * 4) {
+    for (int a0 = wave; a0 < no; a0 += QP_WAVES * 4) {
       double acc[4][NCH];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -144,7 +126,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
         double ga[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const int a = a0 + WIDE_WAVES * u;
+          const int a = a0 + QP_WAVES * u;
           ga[u] = a < no ? gr[a] : 0.0;
         }
 #pragma unroll
@@ -157,7 +139,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const int a = a0 + WIDE_WAVES * u;
+        const int a = a0 + QP_WAVES * u;
         if (a >= no) break;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -174,13 +156,13 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
       good = good && dkk > 0.0;
       const double d = sqrt(dkk > 0.0 ? dkk : 1.0);
       __syncthreads();
-      for (int i = k + tid; i < no; i += WIDE_BLOCK) {
+      for (int i = k + tid; i < no; i += QP_BLOCK) {
         const double v = i == k ? d : A[(size_t)i * lda + k] / d;
         A[(size_t)i * lda + k] = v;
         rv[i] = v;
       }
       __syncthreads();
-      for (int i = k + 1 + wave; i < no; i += WIDE_WAVES) {
+      for (int i = k + 1 + wave; i < no; i += QP_WAVES) {
         const double li = rv[i];
         for (int j = k + 1 + lane; j <= i; j += 64) A[(size_t)i * lda + j] = fma(-li, rv[j], A[(size_t)i * lda + j]);
       }
@@ -189,10 +171,10 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     // ---- trtri: L^-1 in place, column j from the inverted trailing block --------------------------------
     for (int j = no - 1; j >= 0; --j) {
       const double ljj = A[(size_t)j * lda + j];
-      for (int i = j + 1 + tid; i < no; i += WIDE_BLOCK) rv[i] = A[(size_t)i * lda + j];
+      for (int i = j + 1 + tid; i < no; i += QP_BLOCK) rv[i] = A[(size_t)i * lda + j];
       __syncthreads();
       const double ajj = 1.0 / ljj;
-      for (int i = j + 1 + wave; i < no; i += WIDE_WAVES) {
+      for (int i = j + 1 + wave; i < no; i += QP_WAVES) {
         double sacc = 0.0;
         for (int k = j + 1 + lane; k <= i; k += 64) sacc = fma(A[(size_t)i * lda + k], rv[k], sacc);
         sacc = wave_sum(sacc);
@@ -203,9 +185,9 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     }
     // ---- lauum: K^-1 = L^-T L^-1, row i from the rows >= i (not yet overwritten) ----------------------------
     for (int i = 0; i < no; ++i) {
-      for (int k = i + tid; k < no; k += WIDE_BLOCK) rv[k] = A[(size_t)k * lda + i];
+      for (int k = i + tid; k < no; k += QP_BLOCK) rv[k] = A[(size_t)k * lda + i];
       __syncthreads();
-      for (int b = tid; b <= i; b += WIDE_BLOCK) {
+      for (int b = tid; b <= i; b += QP_BLOCK) {
         double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
         int k = i;
         for (; k + 4 <= no; k += 4) {
@@ -220,18 +202,18 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
       __syncthreads();
     }
     // the upper triangle from the lower: the iteration reads whole rows
-    for (int e = tid; e < no * no; e += WIDE_BLOCK) {
+    for (int e = tid; e < no * no; e += QP_BLOCK) {
       const int a = e / no, b = e - a * no;
       if (b > a) A[(size_t)a * lda + b] = A[(size_t)b * lda + a];
     }
     __syncthreads();
     if (ONCHIP && Kg != nullptr) {
-      for (int e = tid; e < no * no; e += WIDE_BLOCK) {
+      for (int e = tid; e < no * no; e += QP_BLOCK) {
         const int a = e / no, b = e - a * no;
         Kg[e] = good ? A[(size_t)a * lda + b] : bad;
       }
     } else if (!good) {
-      for (int e = tid; e < no * no; e += WIDE_BLOCK) {
+      for (int e = tid; e < no * no; e += QP_BLOCK) {
         const int a = e / no, b = e - a * no;
         A[(size_t)a * lda + b] = bad;
       }
@@ -250,11 +232,11 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
 #pragma unroll
     for (int c = 0; c < NCH; ++c) cv[c] = cy[c] = cd[c] = 0.0;
     double rp = 0.0, sp = 0.0, ndy = 0.0, hdy = 0.0, mgdx = -INFINITY;
-    for (int i0 = wave; i0 < nc; i0 += WIDE_WAVES * WIDE_ROWS) {
+    for (int i0 = wave; i0 < nc; i0 += QP_WAVES * WIDE_ROWS) {
       double g[WIDE_ROWS][NCH];
 #pragma unroll
       for (int u = 0; u < WIDE_ROWS; ++u) {
-        const int i = i0 + WIDE_WAVES * u;
+        const int i = i0 + QP_WAVES * u;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const int j = lane + 64 * c;
@@ -280,7 +262,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
       }
 #pragma unroll
       for (int u = 0; u < WIDE_ROWS; ++u) {
-        const int i = i0 + WIDE_WAVES * u;
+        const int i = i0 + QP_WAVES * u;
         if (i >= nc) break;
         double zn = zs[i], yn = ys[i], dy = 0.0;
         if (UPD) {
@@ -331,7 +313,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     double ca[NCH], cb[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) ca[c] = cb[c] = 0.0;
-    for (int b = wave; b < no; b += WIDE_WAVES) {
+    for (int b = wave; b < no; b += QP_WAVES) {
       const double ab = av[b], bb = bv[b];
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
@@ -354,10 +336,10 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
   if (!(rho > 0.0)) {   // (no step to take: the instance is not convex)
     ok = false;
     if (Kg != nullptr)
-      for (int e = tid; e < no * no; e += WIDE_BLOCK) Kg[e] = bad;
+      for (int e = tid; e < no * no; e += QP_BLOCK) Kg[e] = bad;
   } else if (Kinv != nullptr && kinv_valid != 0) {
     if (ONCHIP)
-      for (int e = tid; e < no * no; e += WIDE_BLOCK) Km[(e / no) * kld + e % no] = Kg[e];
+      for (int e = tid; e < no * no; e += QP_BLOCK) Km[(e / no) * kld + e % no] = Kg[e];
   } else {
     ok = factor();
   }
@@ -390,15 +372,15 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
 #pragma unroll
       for (int c = 0; c < NCH; ++c) acc[c] = 0.0;
       int b = wave;
-      for (; b + 3 * WIDE_WAVES < no; b += 4 * WIDE_WAVES) {
+      for (; b + 3 * QP_WAVES < no; b += 4 * QP_WAVES) {
         double kv[4][NCH], rb[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          rb[u] = rv[b + u * WIDE_WAVES];
+          rb[u] = rv[b + u * QP_WAVES];
 #pragma unroll
           for (int c = 0; c < NCH; ++c) {
             const int j = lane + 64 * c;
-            kv[u][c] = j < no ? Km[(size_t)(b + u * WIDE_WAVES) * kld + j] : 0.0;
+            kv[u][c] = j < no ? Km[(size_t)(b + u * QP_WAVES) * kld + j] : 0.0;
           }
         }
 #pragma unroll
@@ -406,7 +388,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
 #pragma unroll
           for (int c = 0; c < NCH; ++c) acc[c] = fma(kv[u][c], rb[u], acc[c]);
       }
-      for (; b < no; b += WIDE_WAVES) {
+      for (; b < no; b += QP_WAVES) {
         const double rb = rv[b];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -464,24 +446,16 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     rd = wave_max(rd), sd = wave_max(sd), ndx = wave_max(ndx), qdx = wave_sum(qdx);
     npdx = wave_max(npdx), ngdy = wave_max(ngdy);
     double rp = 0.0, sp = 0.0, ndy = 0.0, hdy = 0.0, mgdx = -INFINITY;
-    for (int w = 0; w < WIDE_WAVES; ++w) {
+    for (int w = 0; w < QP_WAVES; ++w) {
       rp = fmax(rp, red[w * 16 + 0]);
       sp = fmax(sp, red[w * 16 + 1]);
       ndy = fmax(ndy, red[w * 16 + 2]);
       hdy += red[w * 16 + 3];
       mgdx = fmax(mgdx, red[w * 16 + 4]);
     }
-    const bool pinf = ndy > 1e-30 && hdy < -s.eps_prim_inf * ndy && ngdy < s.eps_prim_inf * ndy;
-    const bool dinf = ndx > 1e-30 && qdx < -s.eps_dual_inf * ndx && npdx < s.eps_dual_inf * ndx &&
-                      mgdx < s.eps_dual_inf * ndx;
-    const int verdict = rp <= s.eps_abs + s.eps_rel * sp && rd <= s.eps_abs + s.eps_rel * sd ? MPCASM_QP_SOLVED
-                        : pinf ? MPCASM_QP_PRIMAL_INFEASIBLE
-                        : dinf ? MPCASM_QP_DUAL_INFEASIBLE : 0;
-    double rn = rho;
-    if (verdict == 0 && s.adaptive_rho_interval > 0 && k % s.adaptive_rho_interval == 0 && k < iters) {
-      rn = rho * sqrt((rp / (sp + 1e-30)) / (rd / (sd + 1e-30)));
-      rn = rn < 1e-6 ? 1e-6 : rn > 1e6 ? 1e6 : rn;
-    }
+    const int verdict = qp_verdict(s, rp, sp, rd, sd, qp_primal_infeasible(s, ndy, hdy, ngdy),
+                                   qp_dual_infeasible(s, ndx, qdx, npdx, mgdx));
+    const double rn = qp_next_rho(s, rho, verdict, k, iters, rp, sp, rd, sd);
     if (verdict != 0) {
       status = verdict;
       ran = k;
@@ -512,7 +486,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
     const int j = lane + 64 * c;
     if (wave == 0 && j < no) X[(size_t)inst * no + j] = ok ? xr[c] : bad;
   }
-  for (int r = tid; r < nc; r += WIDE_BLOCK) {
+  for (int r = tid; r < nc; r += QP_BLOCK) {
     Y[(size_t)inst * nc + r] = ok ? ys[r] : bad;
     Z[(size_t)inst * nc + r] = ok ? zs[r] : bad;
   }
@@ -539,7 +513,7 @@ __global__ __launch_bounds__(WIDE_BLOCK) void admm_wide_kernel(
         if (lane + 64 * c < no) rd = fmax(rd, fabs(px[c] + qr[c] + gty[c]));
       rd = wave_max(rd);
       double rp = 0.0;
-      for (int w = 0; w < WIDE_WAVES; ++w) rp = fmax(rp, red[w * 16 + 0]);
+      for (int w = 0; w < QP_WAVES; ++w) rp = fmax(rp, red[w * 16 + 0]);
       if (lane == 0) {
         res[inst * 2 + 0] = ok ? rp : bad;
         res[inst * 2 + 1] = ok ? rd : bad;
@@ -559,35 +533,10 @@ bool wide_kinv_on_chip(int no, int nc) {
 }
 
 template <int NCH, bool ONCHIP>
-hipError_t launch_wide(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                       double* x, double* y, double* z, double* res, double sigma, double alpha, int max_iter,
-                       int warm, int batch, double* kinv, int kinv_valid, const WideArgs& s, size_t lds,
-                       hipStream_t stream) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = allow_whole_lds(reinterpret_cast<const void*>(admm_wide_kernel<NCH, ONCHIP>));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((admm_wide_kernel<NCH, ONCHIP>), dim3((unsigned)batch), dim3(WIDE_BLOCK), lds, stream, no,
-                     nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv, kinv_valid, s);
-  return hipGetLastError();
-}
-
-template <bool ONCHIP>
-hipError_t launch_wide_nch(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                           double* x, double* y, double* z, double* res, double sigma, double alpha,
-                           int max_iter, int warm, int batch, double* kinv, int kinv_valid, const WideArgs& s,
-                           size_t lds, hipStream_t stream) {
-  if (no <= 64)
-    return launch_wide<1, ONCHIP>(no, nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv,
-                                  kinv_valid, s, lds, stream);
-  if (no <= 128)
-    return launch_wide<2, ONCHIP>(no, nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv,
-                                  kinv_valid, s, lds, stream);
-  if (no <= 256)
-    return launch_wide<4, ONCHIP>(no, nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv,
-                                  kinv_valid, s, lds, stream);
-  return launch_wide<8, ONCHIP>(no, nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv,
-                                kinv_valid, s, lds, stream);
+int launch_wide(const QpBatch& b, const QpSolve& s, size_t lds, hipStream_t stream, hipError_t* err) {
+  return launch_with_lds(admm_wide_kernel<NCH, ONCHIP>, (unsigned)b.batch, QP_BLOCK, lds, stream, err, b.no, b.nc,
+                         b.P, b.q, b.G, b.h, b.x, b.y, b.z, s.res, s.sigma, s.alpha, s.max_iter, s.warm, b.batch,
+                         s.kinv, s.kinv_valid, static_cast<const SolveArgs&>(s));
 }
 
 }  // namespace
@@ -600,23 +549,18 @@ int qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip
   return no > WIDE_MAX_NO || lds > (size_t)RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
 }
 
-int launch_qp_solve_wide(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                         double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
-                         double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
-                         int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
-                         int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err) {
+int launch_qp_solve_wide(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipError_t* err) {
   int64_t lds = 0;
   int32_t on = 0;
-  const int rc = qp_solve_wide_info(no, nc, &lds, &on);
+  const int rc = qp_solve_wide_info(b.no, b.nc, &lds, &on);
   if (rc != MPCASM_OK) return rc;
-  if (!on && kinv == nullptr) return MPCASM_ERR_ARG;   // (d_kinv is the factorisation's workspace)
-  const WideArgs s{rho, status, iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
-                   adaptive_rho_interval};
-  *err = on ? launch_wide_nch<true>(no, nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv,
-                                    kinv_valid, s, (size_t)lds, stream)
-            : launch_wide_nch<false>(no, nc, P, q, G, h, x, y, z, res, sigma, alpha, max_iter, warm, batch, kinv,
-                                     kinv_valid, s, (size_t)lds, stream);
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  if (!on && s.kinv == nullptr) return MPCASM_ERR_ARG;   // (d_kinv is the factorisation's workspace)
+  // the instantiation: K^-1's home, and the columns a lane holds
+  using Launch = int (*)(const QpBatch&, const QpSolve&, size_t, hipStream_t, hipError_t*);
+  static const Launch table[2][4] = {
+      {launch_wide<1, true>, launch_wide<2, true>, launch_wide<4, true>, launch_wide<8, true>},
+      {launch_wide<1, false>, launch_wide<2, false>, launch_wide<4, false>, launch_wide<8, false>}};
+  return table[on ? 0 : 1][b.no <= 64 ? 0 : b.no <= 128 ? 1 : b.no <= 256 ? 2 : 3](b, s, (size_t)lds, stream, err);
 }
 
 }  // namespace mpcasm

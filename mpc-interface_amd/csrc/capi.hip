@@ -45,6 +45,27 @@ int hip_fail(hipError_t e) {
   g_last_hip = (int)e;
   return MPCASM_ERR_HIP;
 }
+// what an entry returns after a launch (err is read only where the launch set it)
+int launched(int rc, const hipError_t& err) {
+  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
+  return rc;
+}
+
+// ---- the checks the QP entries share (every one of them decided before any device call) -------------------
+bool qp_sizes_ok(int no, int nc) { return no >= 1 && nc >= 0 && no <= (1 << 12) && nc <= (1 << 16); }
+bool qp_pointers_ok(const QpBatch& b) {
+  return b.P && b.q && b.x && (b.nc == 0 || (b.G && b.h && b.y && b.z));
+}
+bool qp_steps_ok(double sigma, double alpha) { return sigma > 0.0 && alpha > 0.0 && alpha < 2.0; }
+bool qp_solve_settings_ok(const QpSolve& s) {
+  for (double eps : {s.eps_abs, s.eps_rel, s.eps_prim_inf, s.eps_dual_inf})
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return false;
+  return s.max_iter >= 0 && s.check_every >= 1 && s.adaptive_rho_interval >= 0 &&
+         s.adaptive_rho_interval % s.check_every == 0 && qp_steps_ok(s.sigma, s.alpha);
+}
+bool qp_polish_settings_ok(const QpPolish& p) {
+  return p.refine_iters >= 0 && p.delta > 0.0 && std::isfinite(p.delta);
+}
 
 // section [off, off + len) must lie inside [H_WORDS, n)
 bool in_range(int64_t off, int64_t len, int64_t n, int64_t lo) {
@@ -1180,8 +1201,7 @@ int mpcasm_fill_su(const double* d_A, const double* d_B, double* d_S, double* d_
   hipError_t err;
   const int rc = launch_fill_su(d_A, d_B, d_S, d_U, batch, N, n, m, ltv,
                                 static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_fill_route(int batch, int N, int n, int m, int ltv, int aligned16, int32_t out[8]) {
@@ -1436,9 +1456,8 @@ static int assemble_impl(const mpcasm_plan* plan, const double* const* h_src,
   rc = launch_assemble(d, src, d_params, d_given, d_P, d_q, d_G, d_h, d_work, batch,
                        plan->num_cus, static_cast<hipStream_t>(stream), &err, plan->h_itab.data(),
                        plan->device, d_given_index != nullptr);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
   if (rc == MPCASM_OK) plan->last_kernel = t_last_kernel;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_assemble(const mpcasm_plan* plan, const double* const* h_src,
@@ -1471,8 +1490,7 @@ int mpcasm_preview_matrices(const mpcasm_plan* plan, const double* const* h_src,
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
   rc = launch_preview_matrices(plan->dev, src, d_PM, batch, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_preview(const double* d_PM, const double* d_given, const double* d_optim, double* d_out,
@@ -1483,8 +1501,7 @@ int mpcasm_preview(const double* d_PM, const double* d_given, const double* d_op
   hipError_t err;
   const int rc = launch_preview(d_PM, d_given, d_optim, d_out, batch, rows, ng, no,
                                 static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_preview_direct(const mpcasm_plan* plan, const double* const* h_src,
@@ -1510,8 +1527,7 @@ int mpcasm_preview_direct(const mpcasm_plan* plan, const double* const* h_src,
   if (rc != MPCASM_OK) return rc;
   rc = launch_preview_direct(d, eff, d_given, d_optim, d_out, batch, plan->num_cus,
                              static_cast<hipStream_t>(stream), &err, plan->h_itab.data());
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
@@ -1648,8 +1664,7 @@ int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const
   if (rc != MPCASM_OK) return rc;
   rc = launch_next_given(d, eff, d_map, map_words, d_given, rows, d_optim, d_index, d_status, apply_mask, count,
                          plan->num_cus, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_ltv_rollout_compile(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
@@ -1698,8 +1713,7 @@ int rollout_impl(const mpcasm_plan* plan, const double* const* h_src, const int6
   hipError_t err;
   rc = launch_ltv_rollout(d, src, d_table, table_words, d_given, rows, d_optim, d_index, d_status, apply_mask, d_out,
                           write_given, count, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 }  // namespace
 
@@ -1744,8 +1758,7 @@ int mpcasm_preview_goal_distance(const mpcasm_plan* plan, const double* const* h
   if (rc != MPCASM_OK) return rc;
   rc = launch_preview_goals(d, eff, d_given, d_optim, d_params, d.nparams, d_terms, nterms, ngoals, d_out,
                             batch, plan->num_cus, static_cast<hipStream_t>(stream), &err, plan->h_itab.data());
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_goal_distance(const double* d_preview, int64_t preview_stride, const double* d_params,
@@ -1757,8 +1770,7 @@ int mpcasm_goal_distance(const double* d_preview, int64_t preview_stride, const 
   hipError_t err;
   const int rc = launch_goal_distance(d_preview, preview_stride, d_params, n_params, d_terms, nterms,
                                       ngoals, d_out, batch, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_box_transform(double* d_params, int64_t n_params, int batch, const int32_t* d_facets,
@@ -1772,8 +1784,7 @@ int mpcasm_box_transform(double* d_params, int64_t n_params, int batch, const in
   hipError_t err;
   const int rc = launch_box_transform(d_params, n_params, batch, d_facets, nfacets, op, d_arg,
                                       arg_stride, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_box_transform_ss(double* d_params, int64_t n_params, int batch,
@@ -1789,54 +1800,56 @@ int mpcasm_box_transform_ss(double* d_params, int64_t n_params, int batch,
   const int rc = launch_box_transform_ss(d_params, n_params, batch, d_facets, nfacets, op, d_L,
                                          lrows, ss_dim, d_arg, arg_stride,
                                          static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_admm(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
                 const double* d_h, double* d_x, double* d_y, double* d_z, double* d_res, double rho,
                 double sigma, double alpha, int iters, int warm, int batch, double* d_kinv, int kinv_valid,
                 void* stream) {
-  if (no < 1 || nc < 0 || batch < 0 || iters < 0 || !(rho > 0.0) || !(sigma > 0.0) || !(alpha > 0.0) ||
-      !(alpha < 2.0) || no > (1 << 12) || nc > (1 << 16))
-    return MPCASM_ERR_ARG;
+  if (!qp_sizes_ok(no, nc) || batch < 0 || iters < 0 || !(rho > 0.0) || !qp_steps_ok(sigma, alpha)) return MPCASM_ERR_ARG;
   if (batch == 0) return MPCASM_OK;
-  if (!d_P || !d_q || !d_x || (nc > 0 && (!d_G || !d_h || !d_y || !d_z))) return MPCASM_ERR_ARG;
-  hipError_t err;
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  if (!qp_pointers_ok(b)) return MPCASM_ERR_ARG;
   if (kinv_valid != 0 && d_kinv == nullptr) return MPCASM_ERR_ARG;
-  const int rc = launch_admm(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, d_res, rho, sigma, alpha, iters,
-                             warm != 0, batch, d_kinv, kinv_valid != 0, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  QpSolve s{};
+  s.sigma = sigma, s.alpha = alpha, s.max_iter = iters, s.warm = warm != 0;
+  s.kinv = d_kinv, s.kinv_valid = kinv_valid != 0, s.res = d_res;
+  hipError_t err;
+  return launched(launch_admm(b, rho, s, static_cast<hipStream_t>(stream), &err), err);
 }
 
+// mpcasm_qp_solve and mpcasm_qp_solve_wide: the same arguments, checked in the same order; the wide entry also
+// asks its launch where K^-1 lives, before it looks at the batch
+static int qp_solve_entry(bool wide, const QpBatch& b, const QpSolve& s, void* stream) {
+  if (!qp_solve_settings_ok(s) || !qp_sizes_ok(b.no, b.nc) || b.batch < 0) return MPCASM_ERR_ARG;
+  int32_t on_chip = 1;
+  if (wide) {
+    const int limit = qp_solve_wide_info(b.no, b.nc, nullptr, &on_chip);
+    if (limit != MPCASM_OK) return limit;
+  }
+  if (b.batch == 0) return MPCASM_OK;
+  if (!qp_pointers_ok(b) || !s.rho || !s.status || !s.iters) return MPCASM_ERR_ARG;
+  if ((s.kinv_valid != 0 || on_chip == 0) && s.kinv == nullptr) return MPCASM_ERR_ARG;
+  hipError_t err;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  return launched(wide ? launch_qp_solve_wide(b, s, st, &err) : launch_qp_solve(b, s, st, &err), err);
+}
 int mpcasm_qp_solve(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
                     const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
                     double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
                     double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
                     int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
                     int kinv_valid, void* stream) {
-  for (double eps : {eps_abs, eps_rel, eps_prim_inf, eps_dual_inf})
-    if (!(eps >= 0.0) || !std::isfinite(eps)) return MPCASM_ERR_ARG;
-  if (no < 1 || nc < 0 || batch < 0 || max_iter < 0 || check_every < 1 || adaptive_rho_interval < 0 ||
-      adaptive_rho_interval % check_every != 0 || !(sigma > 0.0) || !(alpha > 0.0) || !(alpha < 2.0) ||
-      no > (1 << 12) || nc > (1 << 16))
-    return MPCASM_ERR_ARG;
-  if (batch == 0) return MPCASM_OK;
-  if (!d_P || !d_q || !d_x || !d_rho || !d_status || !d_iters || (nc > 0 && (!d_G || !d_h || !d_y || !d_z)))
-    return MPCASM_ERR_ARG;
-  if (kinv_valid != 0 && d_kinv == nullptr) return MPCASM_ERR_ARG;
-  hipError_t err;
-  const int rc = launch_qp_solve(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm != 0, d_rho, sigma, alpha,
-                                 eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
-                                 adaptive_rho_interval, d_status, d_iters, d_res, batch, d_kinv,
-                                 kinv_valid != 0, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
+                   adaptive_rho_interval},
+                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
+  return qp_solve_entry(false, b, s, stream);
 }
 
 int mpcasm_qp_solve_lds_bytes(int no, int nc, int64_t* out) {
-  if (no < 1 || nc < 0 || no > (1 << 12) || nc > (1 << 16) || !out) return MPCASM_ERR_ARG;
+  if (!qp_sizes_ok(no, nc) || !out) return MPCASM_ERR_ARG;
   *out = (int64_t)admm_lds_bytes(no, nc);
   return *out > RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
 }
@@ -1847,51 +1860,42 @@ int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, c
                          double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
                          int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
                          int kinv_valid, void* stream) {
-  for (double eps : {eps_abs, eps_rel, eps_prim_inf, eps_dual_inf})
-    if (!(eps >= 0.0) || !std::isfinite(eps)) return MPCASM_ERR_ARG;
-  if (no < 1 || nc < 0 || batch < 0 || max_iter < 0 || check_every < 1 || adaptive_rho_interval < 0 ||
-      adaptive_rho_interval % check_every != 0 || !(sigma > 0.0) || !(alpha > 0.0) || !(alpha < 2.0) ||
-      no > (1 << 12) || nc > (1 << 16))
-    return MPCASM_ERR_ARG;
-  int32_t on_chip = 0;
-  const int limit = qp_solve_wide_info(no, nc, nullptr, &on_chip);
-  if (limit != MPCASM_OK) return limit;
-  if (batch == 0) return MPCASM_OK;
-  if (!d_P || !d_q || !d_x || !d_rho || !d_status || !d_iters || (nc > 0 && (!d_G || !d_h || !d_y || !d_z)))
-    return MPCASM_ERR_ARG;
-  if ((kinv_valid != 0 || on_chip == 0) && d_kinv == nullptr) return MPCASM_ERR_ARG;
-  hipError_t err;
-  const int rc = launch_qp_solve_wide(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm != 0, d_rho, sigma, alpha,
-                                      eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
-                                      adaptive_rho_interval, d_status, d_iters, d_res, batch, d_kinv,
-                                      kinv_valid != 0, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
+                   adaptive_rho_interval},
+                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
+  return qp_solve_entry(true, b, s, stream);
 }
 
 int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
-  if (no < 1 || nc < 0 || no > (1 << 12) || nc > (1 << 16) || !lds_bytes || !kinv_on_chip) return MPCASM_ERR_ARG;
+  if (!qp_sizes_ok(no, nc) || !lds_bytes || !kinv_on_chip) return MPCASM_ERR_ARG;
   return qp_solve_wide_info(no, nc, lds_bytes, kinv_on_chip);
+}
+
+// what the two polish entries decide alike: MPCASM_OK with *go set where there is something to launch
+static int qp_polish_checks(const QpBatch& b, const QpPolish& p, bool* go) {
+  *go = false;
+  if (!qp_sizes_ok(b.no, b.nc) || b.batch < 0 || !qp_polish_settings_ok(p)) return MPCASM_ERR_ARG;
+  if (b.batch == 0) return MPCASM_OK;
+  if (!qp_pointers_ok(b) || !p.polish) return MPCASM_ERR_ARG;
+  *go = true;
+  return MPCASM_OK;
 }
 
 int mpcasm_qp_polish(int no, int nc, const double* d_P, const double* d_q, const double* d_G, const double* d_h,
                      double* d_x, double* d_y, double* d_z, const int32_t* d_status, double delta,
                      int refine_iters, int32_t* d_polish, double* d_res, int batch, void* stream) {
-  if (no < 1 || nc < 0 || batch < 0 || refine_iters < 0 || !(delta > 0.0) || !std::isfinite(delta) ||
-      no > (1 << 12) || nc > (1 << 16))
-    return MPCASM_ERR_ARG;
-  if (batch == 0) return MPCASM_OK;
-  if (!d_P || !d_q || !d_x || !d_polish || (nc > 0 && (!d_G || !d_h || !d_y || !d_z))) return MPCASM_ERR_ARG;
-  if (polish_lds_bytes(no, nc) > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
-  hipError_t err;
-  const int rc = launch_qp_polish(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, d_status, delta, refine_iters,
-                                  d_polish, d_res, batch, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpPolish p{d_status, delta, refine_iters, d_polish, d_res};
+  bool go;
+  const int rc = qp_polish_checks(b, p, &go);
+  if (!go) return rc;
+  hipError_t err;   // (past the LDS a workgroup may have: the launch's MPCASM_ERR_LIMIT)
+  return launched(launch_qp_polish(b, p, static_cast<hipStream_t>(stream), &err), err);
 }
 
 int mpcasm_qp_polish_lds_bytes(int no, int nc, int64_t* out) {
-  if (no < 1 || nc < 0 || no > (1 << 12) || nc > (1 << 16) || !out) return MPCASM_ERR_ARG;
+  if (!qp_sizes_ok(no, nc) || !out) return MPCASM_ERR_ARG;
   *out = (int64_t)polish_lds_bytes(no, nc);
   return *out > RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
 }
@@ -1900,27 +1904,23 @@ int mpcasm_qp_polish_wide(int no, int nc, const double* d_P, const double* d_q, 
                           const double* d_h, double* d_x, double* d_y, double* d_z, const int32_t* d_status,
                           double delta, int refine_iters, int32_t* d_polish, double* d_res, int batch,
                           void* d_work, size_t work_bytes, void* stream) {
-  if (no < 1 || nc < 0 || batch < 0 || refine_iters < 0 || !(delta > 0.0) || !std::isfinite(delta) ||
-      no > (1 << 12) || nc > (1 << 16))
-    return MPCASM_ERR_ARG;
-  if (batch == 0) return MPCASM_OK;
-  if (!d_P || !d_q || !d_x || !d_polish || (nc > 0 && (!d_G || !d_h || !d_y || !d_z))) return MPCASM_ERR_ARG;
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpPolish p{d_status, delta, refine_iters, d_polish, d_res};
+  bool go;
+  const int rc = qp_polish_checks(b, p, &go);
+  if (!go) return rc;
   int64_t need = 0;
   const int limit = qp_polish_wide_info(no, nc, batch, nullptr, &need, nullptr);
   if (limit != MPCASM_OK) return limit;
   if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0 || work_bytes < (size_t)need) return MPCASM_ERR_ARG;
   hipError_t err;
-  const int rc = launch_qp_polish_wide(no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, d_status, delta, refine_iters,
-                                       d_polish, d_res, batch, static_cast<double*>(d_work),
-                                       static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(launch_qp_polish_wide(b, p, static_cast<double*>(d_work), static_cast<hipStream_t>(stream), &err),
+                  err);
 }
 
 int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
                                int32_t* workgroups) {
-  if (no < 1 || nc < 0 || batch < 0 || no > (1 << 12) || nc > (1 << 16) || !lds_bytes || !work_bytes || !workgroups)
-    return MPCASM_ERR_ARG;
+  if (!qp_sizes_ok(no, nc) || batch < 0 || !lds_bytes || !work_bytes || !workgroups) return MPCASM_ERR_ARG;
   return qp_polish_wide_info(no, nc, batch, lds_bytes, work_bytes, workgroups);
 }
 
@@ -1939,8 +1939,7 @@ int mpcasm_qp_warm_store(int no, int nc, const double* d_x, const double* d_y, c
   const int rc = launch_qp_warm_store(no, nc, d_x, d_y, d_rho, d_status, tag, d_store_x, d_store_y, d_store_rho,
                                       d_store_meta, store_rows, store_no, store_nc, d_index, count,
                                       static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_qp_warm_start(int no, int nc, const double* d_G, const double* d_h, const double* d_store_x,
@@ -1961,8 +1960,7 @@ int mpcasm_qp_warm_start(int no, int nc, const double* d_G, const double* d_h, c
                                       store_no, store_nc, d_index, d_col_src, d_row_src, expect_tag, warm_mask,
                                       rho_cold, d_x, d_y, d_z, d_rho, d_warm, count,
                                       static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_params_map(double* d_params, int64_t n_params, const int32_t* d_recs, const double* d_coef, int nrecs,
@@ -1975,8 +1973,7 @@ int mpcasm_params_map(double* d_params, int64_t n_params, const int32_t* d_recs,
   hipError_t err;
   const int rc = launch_params_map(d_params, n_params, d_recs, d_coef, nrecs, d_cmd, cmd_stride, ncmd, d_index,
                                    d_sign, batch, static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_index, int nnz,
@@ -1987,8 +1984,7 @@ int mpcasm_gather(const double* d_src, int64_t src_stride, const int32_t* d_inde
   hipError_t err;
   const int rc = launch_gather(d_src, src_stride, d_index, nnz, d_dst, batch,
                                static_cast<hipStream_t>(stream), &err);
-  if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
-  return rc;
+  return launched(rc, err);
 }
 
 }  // extern "C"

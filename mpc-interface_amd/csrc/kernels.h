@@ -148,36 +148,67 @@ int launch_box_transform_ss(double* params, long long nparams, int batch, const 
                             hipError_t* err);
 int launch_gather(const double* src, long long src_stride, const int32_t* index, int nnz,
                   double* dst, int batch, hipStream_t stream, hipError_t* err);
+// ---- the QP solvers (admm.hip, admm_wide.hip, polish.hip, polish_wide.hip) ----------------------------------
+// a batch of dense QPs  min 1/2 x'Px + q'x  s.t.  Gx <= h  and its iterates, as the C entries take them
+struct QpBatch {
+  int no, nc, batch;
+  const double *P, *q, *G, *h;
+  double *x, *y, *z;
+};
+// what the solve mode adds to a kernel's arguments (unused by the plain iteration)
+struct SolveArgs {
+  double* rho;        // [batch] in: the step an instance starts with; out: the one it ended with
+  int32_t* status;    // [batch] MPCASM_QP_*
+  int32_t* iters;     // [batch] the iterations an instance ran
+  double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
+  int check_every, adaptive_rho_interval;
+};
+// the settings of a solve: the kernel's own part and what the launch passes beside it (mpcasm_admm: max_iter is
+// `iters`, the step a scalar of its own)
+struct QpSolve : SolveArgs {
+  double sigma, alpha;
+  int max_iter, warm;
+  double* kinv;
+  int kinv_valid;
+  double* res;
+};
+struct QpPolish {
+  const int32_t* status;
+  double delta;
+  int refine_iters;
+  int32_t* polish;
+  double* res;
+};
+
+// the launch of a kernel with dynamic LDS: more than a workgroup may have -> MPCASM_ERR_LIMIT; more than 64 KiB ->
+// allow_whole_lds first; *err is the runtime's word where MPCASM_ERR_HIP comes back
+template <typename... Params, typename... Args>
+int launch_with_lds(void (*kernel)(Params...), unsigned grid, int block, size_t lds, hipStream_t stream,
+                    hipError_t* err, Args... args) {
+  if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
+  if (lds > 64 * 1024) {
+    *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
+    if (*err != hipSuccess) return MPCASM_ERR_HIP;
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3((unsigned)block), lds, stream, args...);
+  *err = hipGetLastError();
+  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+}
+
 size_t admm_lds_bytes(int no, int nc);   // (one instance of mpcasm_admm or mpcasm_qp_solve)
-int launch_admm(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                double* x, double* y, double* z, double* res, double rho, double sigma, double alpha,
-                int iters, int warm, int batch, double* kinv, int kinv_valid, hipStream_t stream,
-                hipError_t* err);
-int launch_qp_solve(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                    double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
-                    double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
-                    int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
-                    int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err);
+int launch_admm(const QpBatch& b, double rho, const QpSolve& s, hipStream_t stream, hipError_t* err);
+int launch_qp_solve(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipError_t* err);
 // admm_wide.hip: the solve to tolerance with G read in place and K^-1 in LDS or in d_kinv
 int qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
-int launch_qp_solve_wide(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                         double* x, double* y, double* z, int warm, double* rho, double sigma, double alpha,
-                         double eps_abs, double eps_rel, double eps_prim_inf, double eps_dual_inf, int max_iter,
-                         int check_every, int adaptive_rho_interval, int32_t* status, int32_t* iters, double* res,
-                         int batch, double* kinv, int kinv_valid, hipStream_t stream, hipError_t* err);
+int launch_qp_solve_wide(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipError_t* err);
 // polish.hip: OSQP's polishing of solved instances (active-set KKT solve with refinement)
 size_t polish_lds_bytes(int no, int nc);
-int launch_qp_polish(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                     double* x, double* y, double* z, const int32_t* status, double delta, int refine_iters,
-                     int32_t* polish, double* res, int batch, hipStream_t stream, hipError_t* err);
+int launch_qp_polish(const QpBatch& b, const QpPolish& p, hipStream_t stream, hipError_t* err);
 // polish_wide.hip: the same polish with G and P read in place and the matrices of the KKT solve in a workspace of
 // the caller's, one slice per workgroup of a launch of min(batch, POLISH_WIDE_CAP) workgroups
 constexpr int POLISH_WIDE_CAP = MPCASM_POLISH_WIDE_CAP;
 int qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes, int32_t* workgroups);
-int launch_qp_polish_wide(int no, int nc, const double* P, const double* q, const double* G, const double* h,
-                          double* x, double* y, double* z, const int32_t* status, double delta, int refine_iters,
-                          int32_t* polish, double* res, int batch, double* work, hipStream_t stream,
-                          hipError_t* err);
+int launch_qp_polish_wide(const QpBatch& b, const QpPolish& p, double* work, hipStream_t stream, hipError_t* err);
 // warm.hip: a closed loop's warm store -- the scatter after a solve, the shifted start before the next
 int launch_qp_warm_store(int no, int nc, const double* x, const double* y, const double* rho, const int32_t* status,
                          int tag, double* sx, double* sy, double* srho, int32_t* smeta, int64_t store_rows,

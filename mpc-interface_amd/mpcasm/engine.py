@@ -237,34 +237,7 @@ def polish_qp(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine_iter
     (``POLISH_DONE`` / ``POLISH_SKIPPED`` / ``POLISH_REJECTED``) and ``res`` ``(B, 2)``, written for accepted
     instances only.  ``res`` is the solution's own when one is passed (else a new tensor of NaN).
     ``out``: the caller's ``(polish, res)`` to write instead (fixed addresses for a replayed graph)."""
-    torch = require_device()
-    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
-        x, y, z, res = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z, sol_or_xyz.res
-    else:
-        (x, y, z), res = sol_or_xyz, None
-    if x is None or y is None or z is None:
-        raise ValueError("polish_qp takes the iterates x, y and z")
-    batch, no, nc, _warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, None, False)
-    verdict = None
-    if out is not None:
-        verdict, res = out
-    if verdict is None:
-        verdict = torch.empty((batch,), dtype=torch.int32, device=P.device)
-    if res is None:
-        res = torch.full((batch, 2), float("nan"), dtype=torch.float64, device=P.device)
-    for t, dtype, shape in ((verdict, torch.int32, (batch,)), (res, torch.float64, (batch, 2))) + \
-            (((status, torch.int32, (batch,)),) if status is not None else ()):
-        if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
-                and tuple(t.shape) == shape):
-            raise ValueError("status, polish (B,) int32 and res (B, 2) float64: contiguous, on P's device")
-    with torch.cuda.device(P.device):
-        rc = capi.load().mpcasm_qp_polish(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
-                                          x.data_ptr(), y.data_ptr(), z.data_ptr(),
-                                          status.data_ptr() if status is not None else None, float(delta),
-                                          int(refine_iters), verdict.data_ptr(), res.data_ptr(), batch,
-                                          _stream_handle(torch, stream))
-    capi.check(rc, "mpcasm_qp_polish")
-    return x, y, z, verdict, res
+    return _polish_qp("mpcasm_qp_polish", P, q, G, h, sol_or_xyz, status, delta, refine_iters, stream, out)
 
 
 def qp_polish_lds_bytes(no, nc):
@@ -285,13 +258,20 @@ def polish_qp_wide(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine
     the launch's workgroups, not by the batch -- allocated here when None (a loop that replays a graph keeps one at
     a fixed address; calls that may run at once need one each).  The polished points equal :func:`polish_qp`'s up
     to rounding."""
+    return _polish_qp("mpcasm_qp_polish_wide", P, q, G, h, sol_or_xyz, status, delta, refine_iters, stream, out,
+                      wide=True, work=work)
+
+
+def _polish_qp(entry, P, q, G, h, sol_or_xyz, status, delta, refine_iters, stream, out, wide=False, work=None):
+    """:func:`polish_qp` and :func:`polish_qp_wide` through the C entry ``entry``; ``wide``: the entry takes the
+    workspace ``work`` (allocated when None) and its size in bytes."""
     torch = require_device()
     if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
         x, y, z, res = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z, sol_or_xyz.res
     else:
         (x, y, z), res = sol_or_xyz, None
     if x is None or y is None or z is None:
-        raise ValueError("polish_qp_wide takes the iterates x, y and z")
+        raise ValueError("%s takes the iterates x, y and z" % ("polish_qp_wide" if wide else "polish_qp"))
     batch, no, nc, _warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, None, False)
     verdict = None
     if out is not None:
@@ -305,20 +285,22 @@ def polish_qp_wide(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine
         if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
                 and tuple(t.shape) == shape):
             raise ValueError("status, polish (B,) int32 and res (B, 2) float64: contiguous, on P's device")
-    need = qp_polish_wide_info(no, nc, batch)[1]
-    if work is None:
-        work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=P.device)
-    if not (isinstance(work, torch.Tensor) and work.device == P.device and work.is_contiguous()
-            and work.dtype in (torch.uint8, torch.float64)):
-        raise ValueError("work: a contiguous uint8 or float64 tensor on P's device")
+    extra = ()
+    if wide:
+        need = qp_polish_wide_info(no, nc, batch)[1]
+        if work is None:
+            work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=P.device)
+        if not (isinstance(work, torch.Tensor) and work.device == P.device and work.is_contiguous()
+                and work.dtype in (torch.uint8, torch.float64)):
+            raise ValueError("work: a contiguous uint8 or float64 tensor on P's device")
+        extra = (work.data_ptr(), work.numel() * work.element_size())
     with torch.cuda.device(P.device):
-        rc = capi.load().mpcasm_qp_polish_wide(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
-                                               x.data_ptr(), y.data_ptr(), z.data_ptr(),
-                                               status.data_ptr() if status is not None else None, float(delta),
-                                               int(refine_iters), verdict.data_ptr(), res.data_ptr(), batch,
-                                               work.data_ptr(), work.numel() * work.element_size(),
-                                               _stream_handle(torch, stream))
-    capi.check(rc, "mpcasm_qp_polish_wide")
+        rc = getattr(capi.load(), entry)(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
+                                         x.data_ptr(), y.data_ptr(), z.data_ptr(),
+                                         status.data_ptr() if status is not None else None, float(delta),
+                                         int(refine_iters), verdict.data_ptr(), res.data_ptr(), batch, *extra,
+                                         _stream_handle(torch, stream))
+    capi.check(rc, entry)
     return x, y, z, verdict, res
 
 
