@@ -43,8 +43,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 /* library / device ------------------------------------------------------- */
 
 /* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
- * mpcasm_ltv_rollout and mpcasm_ltv_advance, and for the one that added mpcasm_qp_polish_wide and
- * mpcasm_qp_polish_wide_info (the project's tests pin the value): a client cannot tell from this number whether
+ * mpcasm_ltv_rollout and mpcasm_ltv_advance, for the one that added mpcasm_qp_polish_wide and
+ * mpcasm_qp_polish_wide_info, and for the one that added mpcasm_ltv_rollout_info (the project's tests pin the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
 /* Number of visible HIP devices (0 when none; never fails). */
@@ -791,6 +791,19 @@ int mpcasm_ltv_advance(const mpcasm_plan* plan, const double* const* h_src, cons
                        double* d_given, int64_t rows, const double* d_optim, const int32_t* d_index,
                        const int32_t* d_status, uint32_t apply_mask, const int32_t* d_table, int64_t table_words,
                        int count, void* stream);
+
+/* Needs no device: the geometry of the launch mpcasm_ltv_rollout (rows_out = 1) or mpcasm_ltv_advance
+ * (rows_out = 0) makes for count instances of the plan with these tables (validated as mpcasm_plan_create does)
+ * and a row table of table_words words -- the one function the launch itself takes it from.  A workgroup takes
+ * *group consecutive instances: as many as fit in 52 KB of LDS beside the table, at most 8, at most count, at
+ * least 1; *lds_bytes its dynamic LDS (the shared part + *group times what an instance stages); *workgroups =
+ * ceil(count / *group).  The plan's tables and not a plan handle, as mpcasm_ltv_rollout_compile: a handle needs a
+ * device.  The launch's own answers: MPCASM_ERR_ARG for a plan without a dynamics compiled as ltv, a
+ * table_words that is no row table's, a negative count, rows_out not 0 or 1, a null output; MPCASM_ERR_LIMIT when
+ * one instance does not fit in a CU's LDS.  count == 0: MPCASM_OK, all three 0. */
+int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                            int64_t table_words, int rows_out, int count, int32_t* group, int64_t* lds_bytes,
+                            int32_t* workgroups);
 
 #ifdef __cplusplus
 }

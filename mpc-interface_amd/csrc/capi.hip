@@ -1732,6 +1732,31 @@ int mpcasm_ltv_advance(const mpcasm_plan* plan, const double* const* h_src, cons
                       table_words, nullptr, 1, count, stream);
 }
 
+int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                            int64_t table_words, int rows_out, int count, int32_t* group, int64_t* lds_bytes,
+                            int32_t* workgroups) {
+  if (!h_itab || (n_dtab && !h_dtab) || !group || !lds_bytes || !workgroups || table_words < 0 ||
+      (rows_out != 0 && rows_out != 1) || count < 0)
+    return MPCASM_ERR_ARG;
+  *group = 0;
+  *lds_bytes = 0;
+  *workgroups = 0;
+  const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
+  if (rc != MPCASM_OK) return rc;
+  PlanDev d;
+  memset(&d, 0, sizeof d);
+  plan_dev_from_tables(h_itab, &d);
+  if (!d.sw_ok) return MPCASM_ERR_ARG;  // (as rollout_impl)
+  if (count == 0 || (rows_out && d.pmrows == 0)) return MPCASM_OK;
+  RolloutGeometry geo;
+  const int made = ltv_rollout_geometry(d, table_words, rows_out != 0, count, &geo);
+  if (made != MPCASM_OK) return made;
+  *group = geo.group;
+  *lds_bytes = (int64_t)geo.lds;
+  *workgroups = (int32_t)geo.grid;
+  return MPCASM_OK;
+}
+
 int mpcasm_preview_goal_distance(const mpcasm_plan* plan, const double* const* h_src,
                                  const int64_t* h_src_stride, const double* d_given,
                                  const double* d_optim, const double* d_params, const int32_t* d_terms,

@@ -104,6 +104,12 @@ int compile_given_map(const PlanDev& p, const int32_t* h_itab, const int32_t* ro
 // rollout.hip: the preview rows and the next given of a plan compiled as ltv, by the forward recursion
 int compile_rollout_table(const PlanDev& p, const int32_t* recs, int nrec, const double* cvec, int ncvec,
                           std::vector<int32_t>* out);
+struct RolloutGeometry {
+  int group;       // instances of one workgroup
+  size_t lds;      // dynamic LDS bytes of a workgroup
+  unsigned grid;   // workgroups
+};
+int ltv_rollout_geometry(const PlanDev& p, long long table_words, bool rows_out, int count, RolloutGeometry* geo);
 int launch_ltv_rollout(const PlanDev& p, const SrcTable& src, const int32_t* table, long long table_words,
                        double* given, long long rows, const double* optim, const int32_t* index,
                        const int32_t* status, unsigned apply_mask, double* out, int write_given, int count,

@@ -325,30 +325,41 @@ int compile_rollout_table(const PlanDev& p, const int32_t* recs, int nrec, const
   return MPCASM_OK;
 }
 
+// the geometry of a launch of `count` >= 1 instances, with the rows (all N steps, optim staged) or without (the
+// advance: one step): the instances of a workgroup, its LDS bytes, the workgroups -- host only, what the launch
+// below runs and mpcasm_ltv_rollout_info reports
+int ltv_rollout_geometry(const PlanDev& p, long long table_words, bool rows_out, int count, RolloutGeometry* geo) {
+  const int n = p.sw_n, m = p.sw_m, naxes = p.sw_naxes;
+  if (n < 1 || n > SW_NMAX || m < 1 || m > SW_MMAX || naxes < 1 || naxes > SW_AXMAX) return MPCASM_ERR_LIMIT;
+  if (table_words < RT_HDR || table_words - RT_HDR > RO_TABLE_MAX) return MPCASM_ERR_ARG;
+  const RollLds L = roll_lds(p, (int)(table_words - RT_HDR), rows_out ? p.sw_horizon : 1, rows_out);
+  const size_t shared = (size_t)L.inst0 * sizeof(double), per = (size_t)L.per * sizeof(double);
+  if (shared + per > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
+  int group = shared + per >= (size_t)RO_GROUP_LDS ? 1 : (int)((RO_GROUP_LDS - shared) / per);
+  group = std::max(1, std::min({group, RO_GROUP_MAX, count}));
+  geo->group = group;
+  geo->lds = shared + group * per;
+  geo->grid = (unsigned)((count + group - 1) / group);
+  return MPCASM_OK;
+}
+
 int launch_ltv_rollout(const PlanDev& p, const SrcTable& src, const int32_t* table, long long table_words,
                        double* given, long long rows, const double* optim, const int32_t* index,
                        const int32_t* status, unsigned apply_mask, double* out, int write_given, int count,
                        hipStream_t stream, hipError_t* err) {
   *err = hipSuccess;
   if (count == 0) return MPCASM_OK;
-  const int n = p.sw_n, m = p.sw_m, naxes = p.sw_naxes;
-  if (n < 1 || n > SW_NMAX || m < 1 || m > SW_MMAX || naxes < 1 || naxes > SW_AXMAX) return MPCASM_ERR_LIMIT;
-  if (table_words < RT_HDR || table_words - RT_HDR > RO_TABLE_MAX) return MPCASM_ERR_ARG;
-  const bool rows_out = out != nullptr;
-  const RollLds L = roll_lds(p, (int)(table_words - RT_HDR), rows_out ? p.sw_horizon : 1, rows_out);
-  const size_t shared = (size_t)L.inst0 * sizeof(double), per = (size_t)L.per * sizeof(double);
-  if (shared + per > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
-  int group = shared + per >= (size_t)RO_GROUP_LDS ? 1 : (int)((RO_GROUP_LDS - shared) / per);
-  group = std::max(1, std::min({group, RO_GROUP_MAX, count}));
-  const size_t lds = shared + group * per;
-  if (lds > 64 * 1024) {
+  RolloutGeometry geo;
+  const int rc = ltv_rollout_geometry(p, table_words, out != nullptr, count, &geo);
+  if (rc != MPCASM_OK) return rc;
+  if (geo.lds > 64 * 1024) {
     *err = allow_whole_lds(reinterpret_cast<const void*>(ltv_rollout_kernel));
     if (*err != hipSuccess) return MPCASM_ERR_HIP;
   }
   const RollArgs a{src.ptr[p.sw_src_a], src.stride[p.sw_src_a], src.ptr[p.sw_src_b], src.stride[p.sw_src_b],
-                   table, table_words, given, rows, optim, index, status, apply_mask, out, write_given, count, group};
-  const unsigned grid = (unsigned)((count + group - 1) / group);
-  hipLaunchKernelGGL(ltv_rollout_kernel, dim3(grid), dim3(RO_BLOCK), lds, stream, p, a);
+                   table, table_words, given, rows, optim, index, status, apply_mask, out, write_given, count,
+                   geo.group};
+  hipLaunchKernelGGL(ltv_rollout_kernel, dim3(geo.grid), dim3(RO_BLOCK), geo.lds, stream, p, a);
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

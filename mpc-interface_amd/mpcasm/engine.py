@@ -740,6 +740,23 @@ def rollout_table(plan, records=None, cvec=None, sizes=None):
     return host
 
 
+def rollout_info(plan, rows=True, count=1, table_words=None):
+    """``(group, lds_bytes, workgroups)`` of the launch ``mpcasm_ltv_rollout`` (``rows``) or ``mpcasm_ltv_advance``
+    (not ``rows``) makes for ``count`` instances of ``plan`` (compiled with ``ltv=``): the instances of a workgroup,
+    its dynamic LDS bytes, the workgroups -- ``mpcasm_ltv_rollout_info``, host only, no device needed.
+    ``table_words``: the words of the row table (default: :func:`rollout_table`'s).  :class:`capi.MpcasmError` with
+    the launch's own ``MPCASM_ERR_ARG`` / ``MPCASM_ERR_LIMIT``."""
+    if table_words is None:
+        table_words = rollout_table(plan).size
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    group, lds, groups = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
+    capi.check(capi.load().mpcasm_ltv_rollout_info(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, int(table_words),
+        1 if rows else 0, int(count), ctypes.byref(group), ctypes.byref(lds), ctypes.byref(groups)),
+        "mpcasm_ltv_rollout_info")
+    return group.value, lds.value, groups.value
+
+
 STREAMING_LAUNCH_BYTES = 560e6    # results per launch from which P is collected in LDS (resident.hip)
 
 
@@ -1384,6 +1401,12 @@ class Assembler:
         if getattr(self, "_roll", None) is None:
             self._roll = self._torch.as_tensor(rollout_table(self.plan), device=self.device)
         return self._roll
+
+    def rollout_info(self, rows=True, count=None):
+        """``(group, lds_bytes, workgroups)`` of the launch :meth:`rollout` (``rows``) or :meth:`advance` (not
+        ``rows``) makes for ``count`` instances (default: the batch) -- :func:`rollout_info` on this plan's row
+        table; nothing is launched."""
+        return rollout_info(self.plan, rows, self.batch if count is None else count, self._rollout_table().numel())
 
     def _rollout_args(self, given, optim, index, n, writes):
         torch = self._torch

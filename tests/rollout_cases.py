@@ -1,7 +1,8 @@
 """What the tests of the forward rollout of a plan compiled with ``ltv=`` share (csrc/rollout.hip:
 ``Assembler.rollout`` / ``advance``, ``mpcasm.ltv_loop.LtvLoop``): the shapes, the bound, the long-double
-reference of the rows, and the inputs and the CPU restatement of the closed loop -- used by the CPU tests
-(test_ltv_rollout_cpu.py) and the GPU tests (test_gpu_ltv_rollout.py, test_gpu_ltv_loop.py)."""
+reference of the rows, the launch geometries, and the inputs and the CPU restatement of the closed loop -- used by
+the CPU tests (test_ltv_rollout_cpu.py) and the GPU tests (test_gpu_ltv_rollout.py, test_gpu_ltv_rollout_variants.py,
+test_gpu_ltv_loop.py)."""
 import numpy as np
 
 import sweep_cases as sc
@@ -14,6 +15,37 @@ GPU_SHAPES = ["one-1-1-1", "lipm-33", "two-n1", "four-a4-n4", "lipm-129", "four-
 EXTRA = {"wide-lds": sc.Shape("wide-lds", None, 4, 4, 256, 1, 0, False, False, 0, ())}
 # the shapes whose row table the CPU test compiles beside lipm_ltv at N = 1, 2, 33
 TABLE_SHAPES = ["one-1-1-1", "two-n1", "four-a4-n4", "desc"]
+
+# every instantiation roll_chain<NS, MS> of the kernel's switch: n, m in 1 .. 4 at N = 5 on two axes (the second
+# axis' columns of optim start behind the first's: non-zero ucol), no limits -- pmrows 42 .. 108, no = 10 m, ng = 2 n
+NM_SHAPES = ["nm-%d-%d" % (n, m) for n in range(1, 5) for m in range(1, 5)]
+EXTRA.update({"nm-%d-%d" % (n, m): sc.Shape("nm-%d-%d" % (n, m), None, n, m, 5, 2, 0, False, False, 0, ())
+              for n in range(1, 5) for m in range(1, 5)})
+NM_BATCH, NM_GIVEN_ROWS = 11, 14        # group 8: workgroups of 8 and 3; the advance by index into 14 rows
+
+# What mpcasm_ltv_rollout_info answers for GPU_SHAPES at count >= 8 (test_ltv_rollout_cpu.py asserts it on the
+# compiled plans): instances of a workgroup with the rows, LDS bytes an instance stages with the rows, instances of
+# a workgroup of the advance.  Derived from roll_lds and the launch in csrc/rollout.hip, not from a run.
+INFO = {"one-1-1-1": (8, 80, 8), "lipm-33": (8, 5360, 8), "two-n1": (8, 5232, 8), "four-a4-n4": (3, 17040, 8),
+        "lipm-129": (2, 20720, 8), "four-full": (1, 57456, 8), "wide-lds": (1, 81968, 8)}
+INFO_SHARED = {"lipm-33": 640}          # the bytes of a workgroup's shared part (the table's body, rowof) with the rows
+
+# The launch geometries test_gpu_ltv_rollout_variants.py runs the rows at: (shape, batch, {count: the live instances
+# of every workgroup}).  The splits are the claim of each case -- the GPU test holds Assembler.rollout_info to them
+# before it launches, the CPU test the entry on the compiled plan.
+GEOMETRY = [
+    # group 8: tails of 4 and 1 behind two full workgroups; exactly two, one past one, exactly one, one short, one
+    ("lipm-33", 20, {20: (8, 8, 4), 17: (8, 8, 1), 16: (8, 8), 9: (8, 1), 8: (8,), 7: (7,), 1: (1,)}),
+    # an odd group, inst0 = 3: tails of 1 and 2
+    ("four-a4-n4", 7, {7: (3, 3, 1), 6: (3, 3), 5: (3, 2)}),
+    # three workgroups of a group of 2
+    ("lipm-129", 5, {5: (2, 2, 1), 4: (2, 2)}),
+    # odd pmrows = 5, no = 1, a 1-double plant: every second instance's rows, optim, A and B start on an odd double
+    ("one-1-1-1", 19, {19: (8, 8, 3), 9: (8, 1)}),
+]
+ODD_START = [("lipm-33", 20, 17), ("one-1-1-1", 19, 19)]      # (shape, batch, count) of the runs 8 bytes off
+MISSING = ("lipm-33", 20, 17, 23, (8, 9, 16))     # ..., rows of given, the instances whose index points outside it
+ADVANCE = ("lipm-33", 20, 25, {20: (8, 8, 4), 17: (8, 8, 1), 9: (8, 1)})      # ..., rows of given, the advance's splits
 
 
 def kappa_rollout(N, n, m):

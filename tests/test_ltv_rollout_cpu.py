@@ -180,6 +180,112 @@ def test_compile_refuses_another_plan_and_mismatched_sizes(cpu_api):
     assert (small == -1).all() and words.value == 12 + recs.size + 2 * cvec.size
 
 
+def _shared_bytes(table_words):
+    """The shared part of a workgroup's LDS (roll_lds): the table's body behind its 12-word header, in doubles
+    rounded up to even, then RO_GROUP_MAX = 8 ints of rowof."""
+    doubles = (table_words - 12 + 1) // 2
+    return 8 * (doubles + (doubles & 1) + 4)
+
+
+def _split(group, count):
+    """The live instances of every workgroup of ``count`` instances in groups of ``group``."""
+    return tuple(min(group, count - first) for first in range(0, count, group))
+
+
+@pytest.mark.parametrize("name", rc.GPU_SHAPES)
+def test_the_launch_geometry_of_the_gpu_shapes(cpu_api, name):
+    """mpcasm_ltv_rollout_info, host only, on the compiled plan: the group, the LDS and the grid of rc.INFO."""
+    form, plan = sc.compile_case(cpu_api, np.random.default_rng(31), rc.shape_of(name))
+    words = engine.rollout_table(plan).size
+    group, per, advance_group = rc.INFO[name]
+    shared = _shared_bytes(words)
+    assert shared == rc.INFO_SHARED.get(name, shared)
+    assert engine.rollout_info(plan, True, 64) == (group, shared + group * per, -(-64 // group))
+    for count in (1, 3):
+        g = min(group, count)
+        assert engine.rollout_info(plan, True, count, words) == (g, shared + g * per, -(-count // g)), count
+    # the advance stages one step and no optim: 80 to 528 bytes an instance, so 8 of every shape share a workgroup
+    g, lds, workgroups = engine.rollout_info(plan, False, 64)
+    assert (g, workgroups) == (advance_group, 8) and (lds - shared) % g == 0 and 80 <= (lds - shared) // g <= 528
+    for count in (1, 3):
+        assert engine.rollout_info(plan, False, count)[::2] == (count, 1)
+
+
+def test_the_geometry_cases_are_what_they_claim(cpu_api):
+    """The premises of test_gpu_ltv_rollout_variants.py on the compiled plans: every split of rc.GEOMETRY and
+    rc.ADVANCE is the entry's answer, the sixteen nm shapes compile with the sizes the cases rely on."""
+    plans = {}
+
+    def plan_of(name):
+        if name not in plans:
+            plans[name] = sc.compile_case(cpu_api, np.random.default_rng(31), rc.shape_of(name))[1]
+        return plans[name]
+
+    for name, batch, counts in rc.GEOMETRY:
+        group = rc.INFO[name][0]
+        assert max(counts) == batch
+        for count, split in counts.items():
+            assert split == _split(group, count), (name, count)
+            assert engine.rollout_info(plan_of(name), True, count)[::2] == (max(split), len(split)), (name, count)
+    seen = {split for _, _, counts in rc.GEOMETRY for split in counts.values()}
+    assert any(len(s) > 1 and s[1] > 1 for s in seen)                     # a second workgroup of more than one
+    assert any(s[0] == 8 for s in seen)                                   # a full workgroup of 8
+    assert any(len(s) > 2 and s[0] > 2 and s[-1] < s[0] for s in seen)    # a partial one behind full ones, group > 2
+    name, batch, rows, counts = rc.ADVANCE
+    for count, split in counts.items():
+        assert split == _split(8, count)
+        assert engine.rollout_info(plan_of(name), False, count)[::2] == (8, len(split))
+    # the start on an odd double: pmrows = 5 is odd (and no = 1, a plant of one double), 402 even
+    assert plan_of("one-1-1-1").pmrows == 5 and plan_of("one-1-1-1").no == 1 and plan_of("lipm-33").pmrows == 402
+    runs = {(name, batch, count) for name, batch, counts in rc.GEOMETRY for count in counts}
+    assert set(rc.ODD_START) <= runs and rc.MISSING[:3] in runs             # (the aligned runs they are compared with)
+    name, batch, count, rows, missing = rc.MISSING                          # the second workgroup's first instance, one
+    assert missing == (8, 9, 16) and rc.GEOMETRY[0][2][count] == (8, 8, 1) and rows > batch     # inside it, the last
+    # every roll_chain<NS, MS>: the sizes, a row table, groups of 8 and 3 at 11 instances, rows and advance
+    sizes = set()
+    for name in rc.NM_SHAPES:
+        shape, plan = rc.shape_of(name), plan_of(name)
+        sw = plan.sweep
+        assert (sw["n"], sw["m"], sw["N"], sw["axes"].shape[0]) == (shape.n, shape.m, 5, 2)
+        assert (plan.no, plan.ng) == (10 * shape.m, 2 * shape.n) and 42 <= plan.pmrows <= 108
+        assert [int(sw["axes"][a, 1]) for a in range(2)] == [0, 5 * shape.m]       # (the second axis: ucol != 0)
+        sizes.add((shape.n, shape.m))
+        for rows in (True, False):
+            assert engine.rollout_info(plan, rows, rc.NM_BATCH)[::2] == (8, 2)
+    assert sizes == {(n, m) for n in range(1, 5) for m in range(1, 5)}
+    assert {plan_of(n).pmrows for n in rc.NM_SHAPES} >= {42, 108}
+
+
+def test_the_geometry_query_refuses_what_the_launch_refuses(cpu_api):
+    import ctypes
+
+    rng = np.random.default_rng(7)
+    form = sc.build(cpu_api, rng, rc.shape_of("desc"))
+    plan, plain = compile_plan(form, ltv=["plant"]), compile_plan(form)
+    words = engine.rollout_table(plan).size
+
+    def refused(*args):
+        with pytest.raises(capi.MpcasmError) as err:
+            engine.rollout_info(*args)
+        return err.value.status
+
+    assert refused(plain, True, 4, words) == capi.ERR_ARG                   # no dynamics compiled as ltv
+    assert refused(plan, True, -1, words) == capi.ERR_ARG
+    assert refused(plan, True, 4, 11) == capi.ERR_ARG                       # shorter than a table's header
+    assert refused(plan, True, 4, 12 + 4096 + 1) == capi.ERR_ARG            # longer than any table
+    assert engine.rollout_info(plan, True, 0, words) == (0, 0, 0)
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    group, lds, groups = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
+    out = (ctypes.byref(group), ctypes.byref(lds), ctypes.byref(groups))
+    call = capi.load().mpcasm_ltv_rollout_info
+    tables = (itab.ctypes.data, itab.size, dtab.ctypes.data, dtab.size)
+    assert call(*tables, words, 2, 4, *out) == capi.ERR_ARG                 # rows_out: 0 or 1
+    assert call(None, 0, None, 0, words, 1, 4, *out) == capi.ERR_ARG
+    for i in range(3):
+        assert call(*tables, words, 1, 4, *(None if j == i else o for j, o in enumerate(out))) == capi.ERR_ARG
+    assert call(*tables, words, 1, 4, *out) == capi.OK and group.value >= 1
+
+
 def test_the_restated_loop_exercises_both_branches(cpu_api):
     """The inputs of test_gpu_ltv_loop.py on the CPU: the oracle's assembly on the windowed per-step plant,
     osqp_restatement.solve, x_1 -- instance 1 primal infeasible (held) and the others solved, at every tick, no
