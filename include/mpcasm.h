@@ -44,7 +44,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 
 /* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
  * mpcasm_ltv_rollout and mpcasm_ltv_advance, for the one that added mpcasm_qp_polish_wide and
- * mpcasm_qp_polish_wide_info, and for the one that added mpcasm_ltv_rollout_info (the project's tests pin the value): a client cannot tell from this number whether
+ * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info and for the one that added mpcasm_ltv_lqr,
+ * mpcasm_ltv_close and mpcasm_ltv_true_inputs (the project's tests pin the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
 /* Number of visible HIP devices (0 when none; never fails). */
@@ -804,6 +805,47 @@ int mpcasm_ltv_advance(const mpcasm_plan* plan, const double* const* h_src, cons
 int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                             int64_t table_words, int rows_out, int count, int32_t* group, int64_t* lds_bytes,
                             int32_t* workgroups);
+
+/* Pre-stabilised (closed-loop) prediction for a dynamics compiled as ltv ---------------------------------------
+ * Condensing x_{k+1} = A_k x_k + B_k u_k over an unstable plant and a long horizon loses the Hessian's digits
+ * before a solver sees it.  With u_k = K_k x_k + v_k the unknowns of the plan are v and its recursions run on
+ *   A_cl_k = A_k + B_k K_k
+ * bound in A's source slot: mpcasm_assemble, mpcasm_ltv_rollout and mpcasm_ltv_advance are unchanged (the advance
+ * with A_cl_0 and v_0 gives the true x_1 = A_0 x_0 + B_0 u_0).  A cost or limit on the input variable is then one
+ * on v, the deviation from the feedback law; costs and limits on states are what they were.
+ * Sizes: 1 <= n <= 4 states, 1 <= m <= 4 inputs (the sweep kernel's), else MPCASM_ERR_LIMIT; a null or misaligned
+ * pointer or a negative size or stride: MPCASM_ERR_ARG.
+ *
+ * The gains, by a backward Riccati sweep over every instance's own sequence: A (batch, T, n, n), B (batch, T, n,
+ * m), a_stride / b_stride doubles between instances (0: one sequence shared); Q (n, n) and R (m, m) symmetric,
+ * shared by the batch; d_PT (n, n) the terminal P, NULL: Q.  For k = T - 1 .. 0, in this order,
+ *   S = R + B_k^T P B_k (the upper triangle, mirrored);  S = L L^T;  K_k = -S^-1 (B_k^T P A_k) by the two triangular
+ *   solves;  A_cl_k = A_k + B_k K_k;  P <- Q + A_k^T (P A_cl_k);  P <- (P + P^T) / 2.
+ * d_K (batch, T, m, n), d_Acl (batch, T, n, n; NULL: not wanted), d_info (batch) int32: -1, or the step k whose
+ * pivot was not positive (NaN too) -- that step's K and A_cl and every earlier step's are NaN, the later ones
+ * stand.  One lane per instance: the batch is the parallelism. */
+int mpcasm_ltv_lqr(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
+                   int64_t b_stride, const double* d_Q, const double* d_R, const double* d_PT, double* d_K,
+                   double* d_Acl, int32_t* d_info, void* stream);
+
+/* A_cl = A + B K (batch, T, n, n) for gains the caller brings: K at d_K + b k_stride + k k_step_stride, (m, n) --
+ * strides (k_stride, k_step_stride) = (0, 0): one gain; (m n, 0): one per instance; (T m n, m n): one per instance
+ * and step.  A, B and their strides as for mpcasm_ltv_lqr. */
+int mpcasm_ltv_close(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
+                     int64_t b_stride, const double* d_K, int64_t k_stride, int64_t k_step_stride, double* d_Acl,
+                     void* stream);
+
+/* The true inputs of a plan compiled with ltv= whose two source slots hold the closed-loop window (A_cl (N, n, n),
+ * B (N, n, m) per instance): for every instance b and axis, along x_{k+1} = A_cl_k x_k + B_k v_k from the axis'
+ * initial state in row d_index[b] of d_given (rows x ng; NULL: row b, rows >= count) with v the axis' unknowns in
+ * row b of d_optim (count x no), u_k = K_k x_k + v_k for all N steps into d_out (count, axes, N, m).  d_K: the
+ * window's gains (N, m, n) per instance, k_stride doubles between instances (0: shared).  The axes, the column of
+ * the initial state and the columns of the inputs come from the plan's sweep tables, as for mpcasm_ltv_advance; an
+ * instance whose index lies outside d_given writes nothing.  h_src / h_src_stride as for mpcasm_assemble.
+ * MPCASM_ERR_ARG for a plan without a dynamics compiled as ltv. */
+int mpcasm_ltv_true_inputs(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                           const double* d_K, int64_t k_stride, const double* d_given, int64_t rows,
+                           const double* d_optim, const int32_t* d_index, double* d_out, int count, void* stream);
 
 #ifdef __cplusplus
 }

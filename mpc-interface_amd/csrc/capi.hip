@@ -1757,6 +1757,64 @@ int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* 
   return MPCASM_OK;
 }
 
+namespace {
+bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+}  // namespace
+
+int mpcasm_ltv_lqr(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
+                   int64_t b_stride, const double* d_Q, const double* d_R, const double* d_PT, double* d_K,
+                   double* d_Acl, int32_t* d_info, void* stream) {
+  if (n < 1 || m < 1 || T < 0 || batch < 0 || a_stride < 0 || b_stride < 0) return MPCASM_ERR_ARG;
+  if (n > SW_NMAX || m > SW_MMAX) return MPCASM_ERR_LIMIT;
+  if (!d_A || !d_B || !d_Q || !d_R || !d_K || !d_info || misaligned(d_A, 7) || misaligned(d_B, 7) ||
+      misaligned(d_Q, 7) || misaligned(d_R, 7) || misaligned(d_PT, 7) || misaligned(d_K, 7) ||
+      misaligned(d_Acl, 7) || misaligned(d_info, 3))
+    return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_ltv_lqr(n, m, T, batch, d_A, a_stride, d_B, b_stride, d_Q, d_R, d_PT, d_K, d_Acl, d_info,
+                                static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
+}
+
+int mpcasm_ltv_close(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
+                     int64_t b_stride, const double* d_K, int64_t k_stride, int64_t k_step_stride, double* d_Acl,
+                     void* stream) {
+  if (n < 1 || m < 1 || T < 0 || batch < 0 || a_stride < 0 || b_stride < 0 || k_stride < 0 || k_step_stride < 0)
+    return MPCASM_ERR_ARG;
+  if (n > SW_NMAX || m > SW_MMAX) return MPCASM_ERR_LIMIT;
+  if (!d_A || !d_B || !d_K || !d_Acl || misaligned(d_A, 7) || misaligned(d_B, 7) || misaligned(d_K, 7) ||
+      misaligned(d_Acl, 7))
+    return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_ltv_close(n, m, T, batch, d_A, a_stride, d_B, b_stride, d_K, k_stride, k_step_stride, d_Acl,
+                                  static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
+}
+
+int mpcasm_ltv_true_inputs(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                           const double* d_K, int64_t k_stride, const double* d_given, int64_t rows,
+                           const double* d_optim, const int32_t* d_index, double* d_out, int count, void* stream) {
+  if (!plan || count < 0 || rows < 0 || k_stride < 0) return MPCASM_ERR_ARG;
+  const PlanDev& d = plan->dev;
+  if (!d.sw_ok) return MPCASM_ERR_ARG;  // (no dynamics compiled as ltv: as rollout_impl)
+  if (count == 0) return MPCASM_OK;
+  if (!d_K || !d_given || !d_optim || !d_out || !h_src || !h_src_stride || misaligned(d_K, 7) ||
+      misaligned(d_given, 7) || misaligned(d_optim, 7) || misaligned(d_out, 7) || misaligned(d_index, 3))
+    return MPCASM_ERR_ARG;
+  if (!d_index && rows < count) return MPCASM_ERR_ARG;
+  {  // the plan's tables live on the device it was created on
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  }
+  SrcTable src;
+  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  hipError_t err;
+  rc = launch_ltv_true_inputs(d, src, d_K, k_stride, d_given, rows, d_optim, d_index, d_out, count,
+                              static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
+}
+
 int mpcasm_preview_goal_distance(const mpcasm_plan* plan, const double* const* h_src,
                                  const int64_t* h_src_stride, const double* d_given,
                                  const double* d_optim, const double* d_params, const int32_t* d_terms,

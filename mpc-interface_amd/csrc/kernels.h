@@ -114,6 +114,17 @@ int launch_ltv_rollout(const PlanDev& p, const SrcTable& src, const int32_t* tab
                        double* given, long long rows, const double* optim, const int32_t* index,
                        const int32_t* status, unsigned apply_mask, double* out, int write_given, int count,
                        hipStream_t stream, hipError_t* err);
+// feedback.hip: pre-stabilised prediction for a dynamics compiled as ltv -- the gains of a backward Riccati sweep,
+// A_cl = A + B K, and the true inputs u_k = K_k x_k + v_k of a plan whose unknowns are v
+int launch_ltv_lqr(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
+                   long long strideB, const double* Q, const double* R, const double* PT, double* K, double* Acl,
+                   int32_t* info, hipStream_t stream, hipError_t* err);
+int launch_ltv_close(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
+                     long long strideB, const double* K, long long strideK, long long stepK, double* Acl,
+                     hipStream_t stream, hipError_t* err);
+int launch_ltv_true_inputs(const PlanDev& p, const SrcTable& src, const double* K, long long strideK,
+                           const double* given, long long rows, const double* optim, const int32_t* index,
+                           double* out, int count, hipStream_t stream, hipError_t* err);
 int launch_goal_distance(const double* preview, long long preview_stride, const double* params,
                          long long nparams, const int32_t* terms, int nterms, int ngoals,
                          double* out, int batch, hipStream_t stream, hipError_t* err);

@@ -163,6 +163,14 @@ SIGNATURES = {
     "mpcasm_ltv_rollout_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_ltv_lqr": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64] +
+                       [_void_p] * 7),
+    "mpcasm_ltv_close": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
+                                                             _void_p, ctypes.c_int64, ctypes.c_int64, _void_p,
+                                                             _void_p]),
+    "mpcasm_ltv_true_inputs": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64),
+                                              _void_p, ctypes.c_int64, _void_p, ctypes.c_int64, _void_p, _void_p,
+                                              _void_p, ctypes.c_int, _void_p]),
     "mpcasm_gather": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p,
                                      ctypes.c_int, _void_p]),
     "mpcasm_box_transform": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p,

@@ -757,6 +757,90 @@ def rollout_info(plan, rows=True, count=1, table_words=None):
     return group.value, lds.value, groups.value
 
 
+# --------------------------------------------------------------------------
+# pre-stabilised prediction (csrc/feedback.hip)
+# --------------------------------------------------------------------------
+def _ltv_sequences(torch, A_seq, B_seq):
+    """``n, m, T, batch (None: both shared), device`` of a pair of sequences ``(T, n, n)`` / ``(B, T, n, n)`` and
+    ``(T, n, m)`` / ``(B, T, n, m)``, checked as :meth:`Assembler.bind_ltv_window` checks them."""
+    for what, seq in (("A_seq", A_seq), ("B_seq", B_seq)):
+        if not (torch.is_tensor(seq) and seq.dtype == torch.float64 and seq.is_cuda and seq.is_contiguous()
+                and seq.dim() in (3, 4)):
+            raise ValueError("%s: a contiguous float64 device tensor of 3 or 4 dimensions" % what)
+    n, m, T = A_seq.shape[-1], B_seq.shape[-1], A_seq.shape[-3]
+    if A_seq.shape[-2] != n or tuple(B_seq.shape[-3:-1]) != (T, n) or B_seq.device != A_seq.device:
+        raise ValueError("A_seq (.., T, n, n) and B_seq (.., T, n, m) on one device, got %s and %s"
+                         % (tuple(A_seq.shape), tuple(B_seq.shape)))
+    batches = {seq.shape[0] for seq in (A_seq, B_seq) if seq.dim() == 4}
+    if len(batches) > 1:
+        raise ValueError("A_seq and B_seq of %d and %d instances" % (A_seq.shape[0], B_seq.shape[0]))
+    if not (1 <= n <= 4 and 1 <= m <= 4):
+        raise ValueError("1 <= n <= 4 states and 1 <= m <= 4 inputs (the sweep kernel's sizes), got n = %d, m = %d"
+                         % (n, m))
+    return n, m, T, (batches.pop() if batches else None), A_seq.device
+
+
+def _seq_stride(seq):
+    return int(np.prod(seq.shape[1:])) if seq.dim() == 4 else 0
+
+
+def ltv_lqr(A_seq, B_seq, Q, R, terminal=None, want_closed=True, stream=None):
+    """The gains that pre-stabilise per-step plants (``mpcasm_ltv_lqr``, csrc/feedback.hip): the backward Riccati
+    sweep ``K_k = -(R + B_k^T P B_k)^-1 B_k^T P A_k``, ``P <- Q + A_k^T P (A_k + B_k K_k)`` from ``P = terminal``
+    (default ``Q``) over every instance's own sequence.  ``A_seq (T, n, n)`` / ``(B, T, n, n)``, ``B_seq (T, n, m)``
+    / ``(B, T, n, m)``: contiguous float64 device tensors; ``Q (n, n)``, ``R (m, m)``, ``terminal (n, n)``
+    symmetric, shared by the batch (tensors or arrays).  Returns ``(K, A_cl, info)``: ``K (B, T, m, n)``,
+    ``A_cl = A + B K (B, T, n, n)`` (``None`` unless ``want_closed``) -- without the leading ``B`` where both
+    sequences are shared -- and ``info`` int32 ``(B,)``: -1, or the step whose pivot was not positive (its rows of
+    ``K`` and ``A_cl`` and every earlier step's are NaN).  Nothing is read back."""
+    torch = _torch()
+    n, m, T, batch, device = _ltv_sequences(torch, A_seq, B_seq)
+    lead = () if batch is None else (batch,)
+    mats = []
+    for what, mat, size in (("Q", Q, n), ("R", R, m), ("terminal", terminal, n)):
+        if mat is not None:
+            mat = _as_device(torch, mat, device)
+            if tuple(mat.shape) != (size, size):
+                raise ValueError("%s: (%d, %d), got %s" % (what, size, size, tuple(mat.shape)))
+        mats.append(mat)
+    f = dict(dtype=torch.float64, device=device)
+    K = torch.empty(lead + (T, m, n), **f)
+    Acl = torch.empty(lead + (T, n, n), **f) if want_closed else None
+    info = torch.empty((batch or 1,), dtype=torch.int32, device=device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(device):
+        rc = capi.load().mpcasm_ltv_lqr(n, m, T, batch or 1, A_seq.data_ptr(), _seq_stride(A_seq), B_seq.data_ptr(),
+                                        _seq_stride(B_seq), ptr(mats[0]), ptr(mats[1]), ptr(mats[2]), K.data_ptr(),
+                                        ptr(Acl), info.data_ptr(), _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_ltv_lqr")
+    return K, Acl, info
+
+
+def ltv_close(A_seq, B_seq, K, stream=None):
+    """``A_cl = A + B K`` for gains the caller brings (``mpcasm_ltv_close``): ``K`` ``(m, n)`` -- one gain --,
+    ``(B, m, n)`` -- one per instance -- or ``(B, T, m, n)`` -- one per instance and step --, a contiguous float64
+    tensor on the sequences' device; ``A_seq``, ``B_seq`` as for :func:`ltv_lqr`.  Returns ``(B, T, n, n)``, or
+    ``(T, n, n)`` where the sequences and the gain are shared."""
+    torch = _torch()
+    n, m, T, batch, device = _ltv_sequences(torch, A_seq, B_seq)
+    if not (torch.is_tensor(K) and K.dtype == torch.float64 and K.device == device and K.is_contiguous()
+            and K.dim() in (2, 3, 4) and tuple(K.shape[-2:]) == (m, n) and (K.dim() < 4 or K.shape[1] == T)
+            and (K.dim() == 2 or batch in (None, K.shape[0]))):
+        raise ValueError("K: a contiguous float64 tensor of shape (%d, %d), (B, %d, %d) or (B, %d, %d, %d) on %s, "
+                         "got %s" % (m, n, m, n, T, m, n, device,
+                                     tuple(K.shape) if torch.is_tensor(K) else type(K).__name__))
+    if K.dim() > 2:
+        batch = K.shape[0]
+    k_stride, k_step = {2: (0, 0), 3: (m * n, 0), 4: (T * m * n, m * n)}[K.dim()]
+    Acl = torch.empty((() if batch is None else (batch,)) + (T, n, n), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        rc = capi.load().mpcasm_ltv_close(n, m, T, batch or 1, A_seq.data_ptr(), _seq_stride(A_seq), B_seq.data_ptr(),
+                                          _seq_stride(B_seq), K.data_ptr(), k_stride, k_step, Acl.data_ptr(),
+                                          _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_ltv_close")
+    return Acl
+
+
 STREAMING_LAUNCH_BYTES = 560e6    # results per launch from which P is collected in LDS (resident.hip)
 
 
@@ -1488,6 +1572,43 @@ class Assembler:
                 _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_ltv_advance")
         return given
+
+    def true_inputs(self, K_seq, t, given, optim, index=None, out=None, count=None, stream=None):
+        """The true inputs of a plan whose bound window is a closed loop's (``mpcasm_ltv_true_inputs``): with
+        ``A_cl = A + B K`` bound in ``A``'s place (:meth:`bind_ltv_window`) the unknowns are ``v``, and along
+        ``x_{k+1} = A_cl_k x_k + B_k v_k`` from the axis' initial state in ``given`` this returns ``u_k = K_k x_k +
+        v_k`` for every instance, axis and step: ``(B, axes, N, m)``.  ``K_seq`` ``(T, m, n)`` / ``(B, T, m, n)``, a
+        contiguous float64 tensor on this device: the window ``[t, t + N)`` of it is taken by pointer, as
+        :meth:`bind_ltv_window` takes the matrices'.  ``given``, ``optim``, ``index``, ``count`` as for
+        :meth:`rollout`."""
+        torch = self._torch
+        self._rollout_table()        # (ValueError on an assembler without ltv=)
+        g = self.plan.ltv[0]
+        n, m, N = g["n"], g["m"], g["N"]
+        axes = self.plan.sweep["axes"].shape[0]
+        t = int(t)
+        T = K_seq.shape[-3] if torch.is_tensor(K_seq) and K_seq.dim() >= 3 else -1
+        if not 0 <= t <= T - N:
+            raise ValueError("the window [%d, %d) does not lie in the %d steps of the gains" % (t, t + N, T))
+        tail = (T, m, n)
+        if not (K_seq.dtype == torch.float64 and K_seq.device == self.device and K_seq.is_contiguous()
+                and tuple(K_seq.shape) in (tail, (self.batch,) + tail)):
+            raise ValueError("K_seq: a contiguous float64 tensor of shape %s or %s on %s"
+                             % (tail, (self.batch,) + tail, self.device))
+        cnt = self.batch if count is None else int(count)
+        index = self._rollout_args(given, optim, index, cnt, False)
+        if out is None:
+            out = torch.empty((self.batch, axes, N, m), dtype=torch.float64, device=self.device)
+        else:
+            _checked_out(torch, out, (cnt, axes, N, m), self.device, "true_inputs")
+        ptrs, strides = self._src_args()
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_ltv_true_inputs(
+                self._handle, ptrs, strides, K_seq.data_ptr() + 8 * t * m * n, T * m * n if K_seq.dim() == 4 else 0,
+                given.data_ptr(), given.shape[0], optim.data_ptr(), index.data_ptr() if index is not None else None,
+                out.data_ptr(), cnt, _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_ltv_true_inputs")
+        return out
 
     def goal_terms(self, form):
         """Device table of ``mpcasm_goal_distance`` for ``form.goals`` (the plan's costs): one

@@ -349,6 +349,14 @@ def lipm_ltv(api, N=100, tau=0.1, omega=3.3445, foot_corner=(0.1, 0.05), target_
     return form
 
 
+def lipm_feedback_weights(omega=3.3445):
+    """``Q (3, 3), R (1, 1)`` of the Riccati sweep that pre-stabilises the ``dP->CCC`` pendulum of
+    :func:`lipm_ltv` (``mpcasm.ltv_loop.LtvLoop(feedback={"Q": Q, "R": R})``): ``Q = C^T C + 1e-6 I`` with
+    ``C = [[1, 1 / omega, 0], [0, 0, 1]]`` -- the DCM and the CoP, the two quantities the formulation bounds --
+    and ``R = [[1e-2]]`` on the CoP's velocity."""
+    C = np.array([[1.0, 1.0 / omega, 0.0], [0.0, 0.0, 1.0]])
+    return C.T @ C + 1e-6 * np.eye(3), np.array([[1e-2]])
+
 
 def ltv_lipm_steps(api, N=100, tau=0.1, omega=3.3445, theta=0.0):
     """``(A_k, B_k)`` of the ``dP->CCC`` pendulum with a slowly varying natural
