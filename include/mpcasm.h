@@ -44,8 +44,9 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 
 /* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
  * mpcasm_ltv_rollout and mpcasm_ltv_advance, for the one that added mpcasm_qp_polish_wide and
- * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info and for the one that added mpcasm_ltv_lqr,
- * mpcasm_ltv_close and mpcasm_ltv_true_inputs (the project's tests pin the value): a client cannot tell from this number whether
+ * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info, for the one that added mpcasm_ltv_lqr,
+ * mpcasm_ltv_close and mpcasm_ltv_true_inputs and for the one that added mpcasm_ltv_augment (the project's tests pin
+ * the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
 /* Number of visible HIP devices (0 when none; never fails). */
@@ -811,8 +812,10 @@ int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* 
  * before a solver sees it.  With u_k = K_k x_k + v_k the unknowns of the plan are v and its recursions run on
  *   A_cl_k = A_k + B_k K_k
  * bound in A's source slot: mpcasm_assemble, mpcasm_ltv_rollout and mpcasm_ltv_advance are unchanged (the advance
- * with A_cl_0 and v_0 gives the true x_1 = A_0 x_0 + B_0 u_0).  A cost or limit on the input variable is then one
- * on v, the deviation from the feedback law; costs and limits on states are what they were.
+ * with A_cl_0 and v_0 gives the true x_1 = A_0 x_0 + B_0 u_0).  On these matrices a cost or limit on the input
+ * variable is one on v, the deviation from the feedback law; costs and limits on states are what they were.  Costs
+ * and limits on the true u are had from the plant augmented by one delay (mpcasm_ltv_augment, below), in which u is
+ * a state.
  * Sizes: 1 <= n <= 4 states, 1 <= m <= 4 inputs (the sweep kernel's), else MPCASM_ERR_LIMIT; a null or misaligned
  * pointer or a negative size or stride: MPCASM_ERR_ARG.
  *
@@ -834,6 +837,23 @@ int mpcasm_ltv_lqr(int n, int m, int T, int batch, const double* d_A, int64_t a_
 int mpcasm_ltv_close(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
                      int64_t b_stride, const double* d_K, int64_t k_stride, int64_t k_step_stride, double* d_Acl,
                      void* stream);
+
+/* The closed loop with the true input as a state: z_k = [x_k ; u_{k-1}] (n + m states), input v,
+ *   z_{k+1} = At_k z_k + Bt_k v_k,   At_k = [[A_k + B_k K_k, 0], [K_k, 0]],   Bt_k = [[B_k], [I_m]]
+ * so that sample k of the last m states is z_{k+1}[n:] = K_k x_k + v_k = u_k: a formulation written on (At, Bt)
+ * puts costs and limits on the true input as costs and limits on a state, and mpcasm_assemble, mpcasm_ltv_rollout
+ * and mpcasm_ltv_advance run on it unchanged (the advance leaves x_1 in the first n slots of an axis and u_0 in the
+ * last m).  A, B, K and their strides exactly as for mpcasm_ltv_close.  d_At (batch, T, n + m, n + m), d_Bt (batch,
+ * T, n + m, m), d_Kt (batch, T, m, n + m) = [K_k | 0], what mpcasm_ltv_true_inputs takes on the augmented plan
+ * (NULL: not wanted).  The A + B K block is summed in mpcasm_ltv_close's order (A first, then the products by FMA):
+ * on the same data it is that entry's result bit for bit; the K blocks and B are copies, every other element is
+ * exactly +0.0 or 1.0.  The initial u_{-1} of an axis must be finite and is otherwise without influence (its
+ * columns of At are zero).  n + m > 4 (the sweep kernel's states), or n or m not in 1 .. 4: MPCASM_ERR_LIMIT; a
+ * null (d_Kt excepted) or misaligned pointer, a negative size or stride: MPCASM_ERR_ARG; T == 0 or batch == 0:
+ * MPCASM_OK, nothing launched -- all decided on the host.  One lane per output element, one launch. */
+int mpcasm_ltv_augment(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
+                       int64_t b_stride, const double* d_K, int64_t k_stride, int64_t k_step_stride, double* d_At,
+                       double* d_Bt, double* d_Kt, void* stream);
 
 /* The true inputs of a plan compiled with ltv= whose two source slots hold the closed-loop window (A_cl (N, n, n),
  * B (N, n, m) per instance): for every instance b and axis, along x_{k+1} = A_cl_k x_k + B_k v_k from the axis'

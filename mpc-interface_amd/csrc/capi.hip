@@ -1791,6 +1791,21 @@ int mpcasm_ltv_close(int n, int m, int T, int batch, const double* d_A, int64_t 
   return launched(rc, err);
 }
 
+int mpcasm_ltv_augment(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
+                       int64_t b_stride, const double* d_K, int64_t k_stride, int64_t k_step_stride, double* d_At,
+                       double* d_Bt, double* d_Kt, void* stream) {
+  if (n < 0 || m < 0 || T < 0 || batch < 0 || a_stride < 0 || b_stride < 0 || k_stride < 0 || k_step_stride < 0)
+    return MPCASM_ERR_ARG;
+  if (n < 1 || m < 1 || n > SW_NMAX || m > SW_MMAX || n + m > SW_NMAX) return MPCASM_ERR_LIMIT;
+  if (!d_A || !d_B || !d_K || !d_At || !d_Bt || misaligned(d_A, 7) || misaligned(d_B, 7) || misaligned(d_K, 7) ||
+      misaligned(d_At, 7) || misaligned(d_Bt, 7) || misaligned(d_Kt, 7))
+    return MPCASM_ERR_ARG;
+  hipError_t err;
+  const int rc = launch_ltv_augment(n, m, T, batch, d_A, a_stride, d_B, b_stride, d_K, k_stride, k_step_stride, d_At,
+                                    d_Bt, d_Kt, static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
+}
+
 int mpcasm_ltv_true_inputs(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
                            const double* d_K, int64_t k_stride, const double* d_given, int64_t rows,
                            const double* d_optim, const int32_t* d_index, double* d_out, int count, void* stream) {

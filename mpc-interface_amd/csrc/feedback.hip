@@ -2,9 +2,10 @@
 // unstable plant loses the Hessian's digits before any solver sees it ("The loop at C5"), so the input
 // becomes u_k = K_k x_k + v_k, the unknowns become v, and sweep.hip / rollout.hip run unchanged on
 //     A_cl_k = A_k + B_k K_k
-// bound in A's source slot.  Three pieces:
+// bound in A's source slot.  Four pieces:
 //   ltv_lqr_kernel          the gains, by a backward Riccati sweep over each instance's own sequence -- once per loop
 //   ltv_close_kernel        A_cl = A + B K for gains the caller brings -- once per loop
+//   ltv_augment_kernel      the closed loop with the true input as a state, z = [x ; u_prev] -- once per loop
 //   ltv_true_inputs_kernel  u_k = K_k x_k + v_k along x_{k+1} = A_cl_k x_k + B_k v_k -- every tick
 //
 // The sweep is a dependent chain of T steps per instance, so the batch is the parallelism: one lane per instance,
@@ -238,6 +239,69 @@ __global__ __launch_bounds__(FB_CLOSE_BLOCK) void ltv_close_kernel(CloseArgs a) 
   a.Acl[e] = acc;
 }
 
+struct AugmentArgs {
+  const double* A;
+  long long strideA;
+  const double* B;
+  long long strideB;
+  const double* K;
+  long long strideK, stepK;
+  double* At;
+  double* Bt;
+  double* Kt;             // nullptr: not wanted (then totalK = 0)
+  int n, m, T;
+  long long totalA;       // batch T (n + m) (n + m)
+  long long totalB;       // batch T (n + m) m
+  long long totalK;       // batch T m (n + m)
+  unsigned blocksA, blocksB;
+};
+
+// The plant augmented by one delay, z_k = [x_k ; u_{k-1}] with u_k = K_k x_k + v_k:
+//     At_k = [[A_k + B_k K_k, 0], [K_k, 0]]    Bt_k = [[B_k], [I]]    Kt_k = [K_k | 0]
+// so that row k of the STATE u is z_{k+1}[n:] = K_k x_k + v_k, the true input.  One lane per output element; the
+// workgroups of At come first, then Bt's, then Kt's (a workgroup lies in one of them: the branch is uniform), so
+// a wavefront's stores are one contiguous run.  The A + B K block is summed as ltv_close_kernel sums it.
+__global__ __launch_bounds__(FB_CLOSE_BLOCK) void ltv_augment_kernel(AugmentArgs a) {
+  const int n = a.n, m = a.m, nz = n + m;
+  const unsigned blk = blockIdx.x;
+  if (blk < a.blocksA) {
+    const long long e = (long long)blk * FB_CLOSE_BLOCK + threadIdx.x;
+    if (e >= a.totalA) return;
+    const long long r = e / nz, kk = r / nz, b = kk / a.T;
+    const int j = (int)(e - r * nz), i = (int)(r - kk * nz), k = (int)(kk - b * a.T);
+    double v = 0.0;
+    if (j < n) {
+      const double* __restrict__ Kk = a.K + b * a.strideK + k * a.stepK;
+      if (i < n) {
+        const double* __restrict__ Ak = a.A + b * a.strideA + (long long)k * n * n;
+        const double* __restrict__ Bk = a.B + b * a.strideB + (long long)k * n * m;
+        v = Ak[i * n + j];
+        for (int s = 0; s < m; ++s) v = fma(Bk[i * m + s], Kk[s * n + j], v);
+      } else {
+        v = Kk[(i - n) * n + j];
+      }
+    }
+    a.At[e] = v;
+  } else if (blk < a.blocksA + a.blocksB) {
+    const long long e = (long long)(blk - a.blocksA) * FB_CLOSE_BLOCK + threadIdx.x;
+    if (e >= a.totalB) return;
+    const long long r = e / m, kk = r / nz, b = kk / a.T;
+    const int j = (int)(e - r * m), i = (int)(r - kk * nz), k = (int)(kk - b * a.T);
+    double v;
+    if (i < n)
+      v = a.B[b * a.strideB + (long long)k * n * m + i * m + j];
+    else
+      v = i - n == j ? 1.0 : 0.0;
+    a.Bt[e] = v;
+  } else {
+    const long long e = (long long)(blk - a.blocksA - a.blocksB) * FB_CLOSE_BLOCK + threadIdx.x;
+    if (e >= a.totalK) return;
+    const long long r = e / nz, kk = r / m, b = kk / a.T;
+    const int j = (int)(e - r * nz), s = (int)(r - kk * m), k = (int)(kk - b * a.T);
+    a.Kt[e] = j < n ? a.K[b * a.strideK + k * a.stepK + s * n + j] : 0.0;
+  }
+}
+
 struct TrueArgs {
   const double* A;        // the closed-loop window the plan's sources hold
   long long strideA;
@@ -357,6 +421,26 @@ int launch_ltv_close(int n, int m, int T, int batch, const double* A, long long 
   if (blocks > 0x7FFFFFFFLL) return MPCASM_ERR_LIMIT;
   const CloseArgs a{A, strideA, B, strideB, K, strideK, stepK, Acl, n, m, T, total};
   hipLaunchKernelGGL(ltv_close_kernel, dim3((unsigned)blocks), dim3(FB_CLOSE_BLOCK), 0, stream, a);
+  *err = hipGetLastError();
+  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+}
+
+int launch_ltv_augment(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
+                       long long strideB, const double* K, long long strideK, long long stepK, double* At, double* Bt,
+                       double* Kt, hipStream_t stream, hipError_t* err) {
+  *err = hipSuccess;
+  if (n < 1 || m < 1 || n + m > SW_NMAX || m > SW_MMAX) return MPCASM_ERR_LIMIT;
+  const long long nz = n + m, steps = (long long)batch * T;
+  const long long totalA = steps * nz * nz, totalB = steps * nz * m, totalK = Kt ? steps * m * nz : 0;
+  if (steps == 0) return MPCASM_OK;
+  const long long blocksA = (totalA + FB_CLOSE_BLOCK - 1) / FB_CLOSE_BLOCK;
+  const long long blocksB = (totalB + FB_CLOSE_BLOCK - 1) / FB_CLOSE_BLOCK;
+  const long long blocksK = (totalK + FB_CLOSE_BLOCK - 1) / FB_CLOSE_BLOCK;
+  if (blocksA + blocksB + blocksK > 0x7FFFFFFFLL) return MPCASM_ERR_LIMIT;
+  const AugmentArgs a{A, strideA, B, strideB, K, strideK, stepK, At, Bt, Kt, n, m, T, totalA, totalB, totalK,
+                      (unsigned)blocksA, (unsigned)blocksB};
+  hipLaunchKernelGGL(ltv_augment_kernel, dim3((unsigned)(blocksA + blocksB + blocksK)), dim3(FB_CLOSE_BLOCK), 0,
+                     stream, a);
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

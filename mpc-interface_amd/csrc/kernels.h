@@ -122,6 +122,10 @@ int launch_ltv_lqr(int n, int m, int T, int batch, const double* A, long long st
 int launch_ltv_close(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
                      long long strideB, const double* K, long long strideK, long long stepK, double* Acl,
                      hipStream_t stream, hipError_t* err);
+// ... and the closed loop augmented by one delay, z = [x ; u_prev], whose last m states are the true inputs
+int launch_ltv_augment(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
+                       long long strideB, const double* K, long long strideK, long long stepK, double* At, double* Bt,
+                       double* Kt, hipStream_t stream, hipError_t* err);
 int launch_ltv_true_inputs(const PlanDev& p, const SrcTable& src, const double* K, long long strideK,
                            const double* given, long long rows, const double* optim, const int32_t* index,
                            double* out, int count, hipStream_t stream, hipError_t* err);

@@ -168,6 +168,9 @@ SIGNATURES = {
     "mpcasm_ltv_close": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
                                                              _void_p, ctypes.c_int64, ctypes.c_int64, _void_p,
                                                              _void_p]),
+    "mpcasm_ltv_augment": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
+                                                               _void_p, ctypes.c_int64, ctypes.c_int64, _void_p,
+                                                               _void_p, _void_p, _void_p]),
     "mpcasm_ltv_true_inputs": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64),
                                               _void_p, ctypes.c_int64, _void_p, ctypes.c_int64, _void_p, _void_p,
                                               _void_p, ctypes.c_int, _void_p]),

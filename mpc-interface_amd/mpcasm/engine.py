@@ -784,6 +784,20 @@ def _seq_stride(seq):
     return int(np.prod(seq.shape[1:])) if seq.dim() == 4 else 0
 
 
+def _ltv_gain(torch, K, n, m, T, batch, device):
+    """``batch (None: everything shared), k_stride, k_step_stride`` of a gain ``(m, n)``, ``(B, m, n)`` or ``(B, T,
+    m, n)`` beside sequences of ``batch`` instances (:func:`_ltv_sequences`)."""
+    if not (torch.is_tensor(K) and K.dtype == torch.float64 and K.device == device and K.is_contiguous()
+            and K.dim() in (2, 3, 4) and tuple(K.shape[-2:]) == (m, n) and (K.dim() < 4 or K.shape[1] == T)
+            and (K.dim() == 2 or batch in (None, K.shape[0]))):
+        raise ValueError("K: a contiguous float64 tensor of shape (%d, %d), (B, %d, %d) or (B, %d, %d, %d) on %s, "
+                         "got %s" % (m, n, m, n, T, m, n, device,
+                                     tuple(K.shape) if torch.is_tensor(K) else type(K).__name__))
+    if K.dim() > 2:
+        batch = K.shape[0]
+    return (batch,) + {2: (0, 0), 3: (m * n, 0), 4: (T * m * n, m * n)}[K.dim()]
+
+
 def ltv_lqr(A_seq, B_seq, Q, R, terminal=None, want_closed=True, stream=None):
     """The gains that pre-stabilise per-step plants (``mpcasm_ltv_lqr``, csrc/feedback.hip): the backward Riccati
     sweep ``K_k = -(R + B_k^T P B_k)^-1 B_k^T P A_k``, ``P <- Q + A_k^T P (A_k + B_k K_k)`` from ``P = terminal``
@@ -823,15 +837,7 @@ def ltv_close(A_seq, B_seq, K, stream=None):
     ``(T, n, n)`` where the sequences and the gain are shared."""
     torch = _torch()
     n, m, T, batch, device = _ltv_sequences(torch, A_seq, B_seq)
-    if not (torch.is_tensor(K) and K.dtype == torch.float64 and K.device == device and K.is_contiguous()
-            and K.dim() in (2, 3, 4) and tuple(K.shape[-2:]) == (m, n) and (K.dim() < 4 or K.shape[1] == T)
-            and (K.dim() == 2 or batch in (None, K.shape[0]))):
-        raise ValueError("K: a contiguous float64 tensor of shape (%d, %d), (B, %d, %d) or (B, %d, %d, %d) on %s, "
-                         "got %s" % (m, n, m, n, T, m, n, device,
-                                     tuple(K.shape) if torch.is_tensor(K) else type(K).__name__))
-    if K.dim() > 2:
-        batch = K.shape[0]
-    k_stride, k_step = {2: (0, 0), 3: (m * n, 0), 4: (T * m * n, m * n)}[K.dim()]
+    batch, k_stride, k_step = _ltv_gain(torch, K, n, m, T, batch, device)
     Acl = torch.empty((() if batch is None else (batch,)) + (T, n, n), dtype=torch.float64, device=device)
     with torch.cuda.device(device):
         rc = capi.load().mpcasm_ltv_close(n, m, T, batch or 1, A_seq.data_ptr(), _seq_stride(A_seq), B_seq.data_ptr(),
@@ -839,6 +845,34 @@ def ltv_close(A_seq, B_seq, K, stream=None):
                                           _stream_handle(torch, stream))
     capi.check(rc, "mpcasm_ltv_close")
     return Acl
+
+
+def ltv_augment(A_seq, B_seq, K, want_gain=True, stream=None):
+    """The closed loop with the true input as a state (``mpcasm_ltv_augment``): ``z_k = [x_k ; u_{k-1}]`` with
+    ``u_k = K_k x_k + v_k``, so ``At_k = [[A_k + B_k K_k, 0], [K_k, 0]]`` and ``Bt_k = [[B_k], [I]]`` -- a formulation
+    on ``(At, Bt)`` whose input is ``v`` sees ``u`` as its last ``m`` states, and costs and limits on them are costs
+    and limits on the true input.  ``A_seq``, ``B_seq`` and ``K`` exactly as for :func:`ltv_close`; ``n + m <= 4``.
+    Returns ``(At_seq, Bt_seq, Kt_seq)``: ``(B, T, n + m, n + m)``, ``(B, T, n + m, m)`` and ``Kt = [K | 0]`` ``(B, T,
+    m, n + m)``, the gains :meth:`Assembler.true_inputs` takes on the augmented plan (``None`` unless ``want_gain``)
+    -- without the leading ``B`` where the sequences and the gain are shared.  The ``A + B K`` block is
+    :func:`ltv_close`'s result bit for bit."""
+    torch = _torch()
+    n, m, T, batch, device = _ltv_sequences(torch, A_seq, B_seq)
+    batch, k_stride, k_step = _ltv_gain(torch, K, n, m, T, batch, device)
+    if n + m > 4:
+        raise ValueError("n + m <= 4 states of the augmented plant (the sweep kernel's sizes), got n = %d, m = %d"
+                         % (n, m))
+    lead = () if batch is None else (batch,)
+    f = dict(dtype=torch.float64, device=device)
+    At, Bt = torch.empty(lead + (T, n + m, n + m), **f), torch.empty(lead + (T, n + m, m), **f)
+    Kt = torch.empty(lead + (T, m, n + m), **f) if want_gain else None
+    with torch.cuda.device(device):
+        rc = capi.load().mpcasm_ltv_augment(n, m, T, batch or 1, A_seq.data_ptr(), _seq_stride(A_seq),
+                                            B_seq.data_ptr(), _seq_stride(B_seq), K.data_ptr(), k_stride, k_step,
+                                            At.data_ptr(), Bt.data_ptr(), Kt.data_ptr() if want_gain else None,
+                                            _stream_handle(torch, stream))
+    capi.check(rc, "mpcasm_ltv_augment")
+    return At, Bt, Kt
 
 
 STREAMING_LAUNCH_BYTES = 560e6    # results per launch from which P is collected in LDS (resident.hip)

@@ -358,6 +358,78 @@ def lipm_feedback_weights(omega=3.3445):
     return C.T @ C + 1e-6 * np.eye(3), np.array([[1e-2]])
 
 
+def augment_matrices(A, B, K):
+    """``(At, Bt)`` of the closed loop ``u = K x + v`` with the true input as a state, ``z = [x ; u_prev]``:
+    ``At = [[A + B K, 0], [K, 0]]``, ``Bt = [[B], [I]]`` -- over any leading axes (``K`` broadcast against them), in
+    numpy (``mpcasm.engine.ltv_augment`` builds whole sequences of them on the device)."""
+    A, B, K = np.asarray(A), np.asarray(B), np.asarray(K)
+    n, m = B.shape[-2:]
+    lead = np.broadcast_shapes(A.shape[:-2], B.shape[:-2], K.shape[:-2])
+    At = np.zeros(lead + (n + m, n + m), dtype=np.result_type(A, B, K))
+    Bt = np.zeros(lead + (n + m, m), dtype=At.dtype)
+    At[..., :n, :n] = A + B @ K
+    At[..., n:, :n] = K
+    Bt[..., :n, :] = B
+    Bt[..., n:, :] = np.eye(m)
+    return At, Bt
+
+
+def _first_riccati_gain(A, B, Q, R, steps):
+    """``K_0`` of the backward Riccati sweep of ``steps`` steps over the constant pair ``(A, B)`` from ``P = Q``
+    (``mpcasm.engine.ltv_lqr``'s recursion, on the host)."""
+    P, K = Q, None
+    for _ in range(steps):
+        K = -np.linalg.solve(R + B.T @ P @ B, B.T @ P @ A)
+        P = Q + A.T @ P @ (A + B @ K)
+        P = (P + P.T) / 2
+    return K
+
+
+def lipm_ltv_true_input(api, N=100, tau=0.1, omega=3.3445, foot_corner=(0.1, 0.05), target_vel=(0.3, 0.0),
+                        input_limit=None, gain=None):
+    """:func:`lipm_ltv` with costs and limits on the TRUE input of a pre-stabilised plan: the pendulum closed by
+    ``cCoP_dot = K x + v`` and augmented by one delay (:func:`augment_matrices`), so the input is ``v`` and the
+    states are ``CoM, CoM_dot, CoM_ddot, cCoP_dot`` -- sample ``k`` of the state ``cCoP_dot`` is the input applied
+    at step ``k``.  The same three costs (``effort`` on the state ``cCoP_dot``: on the true input, not on ``v``) and
+    the same two boxes; with ``input_limit`` the pair ``-input_limit < cCoP_dot < input_limit`` at every step on
+    either axis: ``2 N`` unknowns, ``4 N + 4`` (``8 N + 4``) inequality rows.  Built on the nominal ``(A, B)`` and
+    a nominal ``gain (1, 3)`` -- default: the first gain of the Riccati sweep of ``N`` steps over the nominal pair
+    with :func:`lipm_feedback_weights` --; an assembler compiled with ``ltv=["LIP"]`` takes the per-step matrices
+    ``mpcasm.engine.ltv_augment`` builds (``mpcasm.ltv_loop.LtvLoop(feedback=, true_input=True)``)."""
+    t = api.tools
+    axes = ["_x", "_y"]
+    get_A, get_B, _ = t.get_system_matrices("dP->CCC")
+    A = np.asarray(get_A(tau=tau, omega=omega), dtype=float)
+    B = np.asarray(get_B(tau=tau, omega=omega), dtype=float).reshape(3, 1)
+    if gain is None:
+        gain = _first_riccati_gain(A, B, *lipm_feedback_weights(omega), steps=N)
+    gain = np.asarray(gain, dtype=float)
+    if gain.shape != (1, 3):
+        raise ValueError("gain: (1, 3), got %s" % (gain.shape,))
+    At, Bt = augment_matrices(A, B, gain)
+    closed = api.ControlSystem(["v"], ["CoM", "CoM_dot", "CoM_ddot", "cCoP_dot"], At, Bt, axes)
+    lip = api.ExtendedSystem.from_cotrol_system(closed, "x", N)
+    lip.define_output("b", {"CoM": 1, "CoM_ddot": -1 / omega**2})
+    lip.define_output("DCM", {"CoM": 1, "CoM_dot": 1 / omega})
+    foot = t.make_simetric_vertices(np.array(foot_corner))
+    form = api.Formulation()
+    form.incorporate_dynamics("LIP", lip)
+    form.incorporate_goal("effort", api.Cost("cCoP_dot", 1e-3, aim=[0, 0], axes=axes))
+    form.incorporate_goal("velocity", api.Cost("CoM_dot", 1e-2, aim=list(target_vel), axes=axes))
+    form.incorporate_goal("centre CoP", api.Cost("b", 1.0, aim=[0, 0], axes=axes))
+    form.incorporate_box("CoP", api.Box.task_space("b", foot, axes))
+    form.incorporate_box("terminal", api.Box.task_space("DCM", foot, axes, schedule=range(N - 1, N)))
+    if input_limit is not None:
+        for axis in axes:
+            form.incorporate_constraint(
+                "input limit" + axis,
+                [api.Constraint("cCoP_dot" + axis, float(input_limit)),
+                 api.Constraint("cCoP_dot" + axis, float(input_limit), arrow=[-1])])
+    form.identify_qp_domain(["v_x", "v_y"])
+    form.make_preview_matrices()
+    return form
+
+
 def ltv_lipm_steps(api, N=100, tau=0.1, omega=3.3445, theta=0.0):
     """``(A_k, B_k)`` of the ``dP->CCC`` pendulum with a slowly varying natural
     frequency ``omega_k = omega (1 + 0.05 sin(2 pi k / N + theta))``."""
