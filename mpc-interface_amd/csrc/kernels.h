@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mpcasm.h"
+#include "plan_check.h"
 #include "plan_dev.h"
 #include "plan_tables.h"
 
@@ -48,9 +49,8 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
                           const int32_t* h_itab);
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* work, int batch,
                       const int32_t* h_itab, SrcTable* eff, hipStream_t stream);
-// the zeros toeplitz_assemble_kernel keeps in LDS behind the group's table (doubles; even): what a stage's window
-// may read past the table's end (validate_plan holds the stages to it)
-int toeplitz_zero_pad(int N);
+// (toeplitz_zero_pad, the zeros toeplitz_assemble_kernel keeps in LDS behind the group's table: plan_check.h, beside
+// the checker that holds the stages to it)
 // host only: what launch_assemble_tiled launches for a plan (mpcasm_tiled_route).  `form`: MPCASM_TILED_*;
 // scan form: fused (the kernel makes its table and d itself) or behind the pre-passes, the instantiation
 // toeplitz_scan_kernel<kp, cb>, whether the records of G's rows ride in LDS, whether results leave as whole

@@ -10,8 +10,8 @@
 
 namespace mpcasm {
 
-// every int field of PlanDev, once: the struct, its upload (capi.hip) and the constants of a
-// specialised kernel (jit.hip) are generated from this list
+// every int field of PlanDev, once: the struct and the constants of a specialised kernel (jit.hip) are
+// generated from this list; the fields are filled from the tables by hand (plan_check.cpp plan_view)
 #define MPCASM_PLAN_INT_FIELDS(X)                                                                   \
   X(ng) X(no) X(nc) X(nparams) X(nsrc) X(nbase) X(nseg) X(rtot) X(nent) X(ngterm) X(nlimit)         \
   X(nlax) X(pmrows) X(pm_nent) X(ldv) X(off_seg) X(off_colseg) X(off_rowptr) X(off_entbase)         \

@@ -1737,8 +1737,6 @@ __global__ __launch_bounds__(BLOCK) void shared_qh_kernel(PlanDev p, const doubl
 
 extern int g_phase_mask;  // fused.hip (MPCASM_OPT_PHASE_MASK)
 
-int toeplitz_zero_pad(int N) { return (std::max(N, 16) + 16 + 1) & ~1; }  // (even: what follows stays 16-byte aligned)
-
 bool tiled_eligible(const PlanDev& p) { return p.t_ok != 0 && p.no >= T_BLOCK; }
 
 // the shared-model form may run on plans without generated groups and with rows of G in 16-byte pieces

@@ -422,6 +422,77 @@ def test_plan_tables_rejected_or_accepted_by_the_library(cpu_api):
     assert create(plan.itab[:-1].copy(), plan.dtab) == -2
 
 
+def record_fields(first):
+    """Index of every field of the record whose enum in csrc/plan_tables.h starts with ``first = 0``."""
+    import os
+    import re
+
+    text = open(os.path.join(os.path.dirname(__file__), "..", "mpc-interface_amd", "csrc", "plan_tables.h")).read()
+    body = re.search(r"enum\s*\{\s*(%s = 0,[^}]*)\}" % first, text).group(1)
+    names = [n.split("=")[0].strip() for n in body.split(",")]
+    return {n: i for i, n in enumerate(names) if n and not n.endswith("_WORDS")}
+
+
+def test_a_limit_whose_rows_overflow_is_refused(cpu_api, tmp_path):
+    """A limit's LM_OUT0 + LM_NROWS is a sum of two table words: with either of them 0x7fffffff it wrapped in
+    `int`, the bound before the walk over the row -> limit list held nothing, and the checker itself read far
+    outside the tables.  Both are malformed plans (-2); asked in a child process, so that a checker which crashes
+    again fails this test rather than the session."""
+    import subprocess
+    import sys
+
+    LM = record_fields("LM_OUT0")
+    plan = compile_plan(problems.body_case(cpu_api))
+    lim0 = plan.itab[_H["OFF_LIMIT"]]
+    assert plan.itab[_H["NLIMIT"]] >= 1
+    rows, out0 = plan.itab.copy(), plan.itab.copy()
+    rows[lim0 + LM["LM_NROWS"]] = 0x7FFFFFFF
+    out0[lim0 + LM["LM_OUT0"]] = 0x7FFFFFFF
+    rows.tofile(tmp_path / "rows")
+    out0.tofile(tmp_path / "out0")
+    plan.dtab.tofile(tmp_path / "dtab")
+    child = (
+        "import ctypes, sys, numpy as np\n"
+        "lib = ctypes.CDLL(sys.argv[1])\n"
+        "lib.mpcasm_plan_create.restype = ctypes.c_int\n"
+        "lib.mpcasm_plan_create.argtypes = [ctypes.c_void_p, ctypes.c_size_t] * 2 + [ctypes.c_void_p]\n"
+        "dt = np.fromfile(sys.argv[2], dtype=np.float64)\n"
+        "handle = ctypes.c_void_p()\n"
+        "for path in sys.argv[3:]:\n"
+        "    it = np.fromfile(path, dtype=np.int32)\n"
+        "    print(lib.mpcasm_plan_create(it.ctypes.data, it.size, dt.ctypes.data, dt.size, ctypes.byref(handle)),\n"
+        "          flush=True)\n")
+    done = subprocess.run([sys.executable, "-c", child, capi.LIB_PATH, str(tmp_path / "dtab"), str(tmp_path / "rows"),
+                           str(tmp_path / "out0")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert done.returncode == 0, (done.returncode, done.stdout, done.stderr[-2000:])
+    assert done.stdout.split() == ["-2", "-2"]
+
+
+def test_segments_and_gterms_that_overflow_are_refused(cpu_api):
+    """SEG_DST0 + SEG_LEN and GT_AOFF + GT_NROWS, formed in `int`, wrapped to a negative number that passed
+    `> W` and `> RTOT`: a cost term at workspace row 0x7ffffffe was accepted, and a segment at column 0x7fffffff
+    too wherever the compiler took the overflow at its word (GT_DOFF: the same sum on the term's rows of d)."""
+    import mpcasm.plan as P
+
+    SEG, GT = record_fields("SEG_SRC"), record_fields("GT_AOFF")
+    lib = capi.load()
+    plan = compile_plan(problems.body_case(cpu_api))
+    it = plan.itab
+    handle = ctypes.c_void_p()
+    seg0, gt0 = it[_H["OFF_SEG"]], it[_H["OFF_GTERM"]]
+    assert it[_H["NSEG"]] >= 1 and it[seg0 + SEG["SEG_LEN"]] >= 1
+    plain = [g for g in range(it[_H["NGTERM"]])
+             if not it[gt0 + g * P.GT_WORDS + GT["GT_FLAGS"]] & P.GT_FLAG_DIAG]
+    assert plain and it[gt0 + plain[0] * P.GT_WORDS + GT["GT_NROWS"]] >= 2
+    for what, word, value in (("SEG_DST0", seg0 + SEG["SEG_DST0"], 0x7FFFFFFF),
+                              ("GT_AOFF", gt0 + plain[0] * P.GT_WORDS + GT["GT_AOFF"], 0x7FFFFFFF - 1),
+                              ("GT_DOFF", gt0 + plain[0] * P.GT_WORDS + GT["GT_DOFF"], 0x7FFFFFFF - 1)):
+        bad = it.copy()
+        bad[word] = value
+        assert lib.mpcasm_plan_create(bad.ctypes.data, bad.size, plan.dtab.ctypes.data, plan.dtab.size,
+                                      ctypes.byref(handle)) == -2, what
+
+
 def test_persistent_kernel_tables_are_validated(cpu_api):
     """The tables only the persistent kernel reads -- full and short trips, packed row
     records, piece descriptors of G, per-column diagonal terms, the element program of the
