@@ -45,7 +45,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 /* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
  * mpcasm_ltv_rollout and mpcasm_ltv_advance, for the one that added mpcasm_qp_polish_wide and
  * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info, for the one that added mpcasm_ltv_lqr,
- * mpcasm_ltv_close and mpcasm_ltv_true_inputs and for the one that added mpcasm_ltv_augment (the project's tests pin
+ * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment and for the one that added
+ * mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft and their two info entries (the project's tests pin
  * the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
@@ -533,6 +534,56 @@ int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, c
  * every call, overrides that: "global" keeps K^-1 in d_kinv always, "lds" puts it on chip wherever it fits.
  * MPCASM_ERR_LIMIT beyond the size limit of mpcasm_qp_solve_wide (the other outputs still written). */
 int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
+
+/* Soft limits, without slack unknowns: mpcasm_qp_solve and mpcasm_qp_solve_wide on
+ *   min 1/2 x'Px + q'x + sum_i phi_i((Gx - h)_i)
+ * where a hard row has phi_i = the indicator of t <= 0 and a soft row has phi_i(t) = 0 for t <= 0 and
+ * lin_i t + 1/2 quad_i t^2 for t > 0.  This equals the slack QP  min ... + sum lin_i s_i + 1/2 quad_i s_i^2,
+ * Gx - s <= h, s >= 0  in x and in the multipliers of the rows of G.  The argument lists are the hard entries'
+ * plus d_soft_lin, d_soft_quad [batch][nc] at soft_stride doubles: soft_stride == nc means per instance, 0 means
+ * one pair of rows for the whole batch, anything else is MPCASM_ERR_ARG; null vectors with nc > 0 are
+ * MPCASM_ERR_ARG.  lin_i = +inf makes row i hard.  Everything else is the hard entry's: operands, outputs, warm
+ * start, d_rho, d_kinv / kinv_valid (K, its factorisation and the inverse do not see the penalties: an inverse a
+ * hard solve left serves a soft one and back), refusals.
+ * The iteration is the hard one except the z update.  With v = alpha zt + (1 - alpha) z + y / rho:
+ *   hard row, lin_i = +inf:  z+ = min(v, h) -- the hard entry's expression itself: with every lin = +inf every
+ *                            output equals the hard entry's bit for bit;
+ *   soft row:                z+ = v when v <= h, else z+ = h + max(0, (rho (v - h) - lin) / (rho + quad)).
+ * y+ = y + rho (alpha zt + (1 - alpha) z - z+) is unchanged: it is a subgradient of phi at z+, so both residuals,
+ * their scales, "solved" and the adaptive rho keep their meaning.
+ * Primal infeasible: soft rows take no part -- their entry of the projected step dy is 0 in all three quantities
+ * |dy|, h'dy, |G'dy|.  A certificate on the hard rows alone proves infeasibility whatever the soft rows do; with
+ * every row soft the verdict cannot occur.  (While y climbs towards a large lin its step looks exactly like a
+ * certificate: the masking is not optional.)
+ * Dual infeasible: unchanged, over all rows.  It stays sound, because a direction along which no row rises is also
+ * free of penalty; it no longer finds every unbounded instance (one whose cost falls along a direction that soft
+ * rows rise along more slowly): an instance it misses ends as MPCASM_QP_MAX_ITER.
+ * Bad penalties: an instance where any lin_i is NaN or < 0, or any quad_i is NaN, < 0 or +inf, is
+ * MPCASM_QP_NON_CVX with NaN iterates, as for rho <= 0; decided on the device while the vectors are loaded, the
+ * other instances of the launch are untouched.
+ * mpcasm_qp_polish* must not follow on an instance with a violated soft row (its active-set model and its
+ * z = min(Gx, h) are the hard problem's).  LDS: the hard entries' plus 2 nc doubles. */
+int mpcasm_qp_solve_soft(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                         const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                         double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                         double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                         int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                         int kinv_valid, void* stream, const double* d_soft_lin, const double* d_soft_quad,
+                         int64_t soft_stride);
+/* Needs no device: mpcasm_qp_solve_lds_bytes for mpcasm_qp_solve_soft (MPCASM_ERR_LIMIT exactly where its launch
+ * returns it). */
+int mpcasm_qp_solve_soft_lds_bytes(int no, int nc, int64_t* out);
+int mpcasm_qp_solve_wide_soft(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                              const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                              double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                              double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                              int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                              int kinv_valid, void* stream, const double* d_soft_lin, const double* d_soft_quad,
+                              int64_t soft_stride);
+/* Needs no device: mpcasm_qp_solve_wide_info for mpcasm_qp_solve_wide_soft (5 nc + 23 no + 64 doubles, + no (no | 1)
+ * with K^-1 on chip, within the same 156 KB: near the edge K^-1 may be on chip for the hard entry and in d_kinv for
+ * this one, and the size limit is tighter -- nc <= 1625 at no = 512, where the hard entry takes 2048). */
+int mpcasm_qp_solve_wide_soft_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
 
 /* Per-instance outcome of mpcasm_qp_polish, written to d_polish on the device. */
 enum {

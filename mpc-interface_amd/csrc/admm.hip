@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.h"
 #include "qp_prims.h"
@@ -40,9 +41,10 @@ namespace mpcasm {
 namespace {
 
 struct AdmmLds {
-  int mi, gs, x, q, z, y, h, v, r, xt, pa, pb, total, ld, lp;
+  int mi, gs, x, q, z, y, h, v, r, xt, pa, pb, sl, sq, total, ld, lp;
 };
-__host__ __device__ inline AdmmLds admm_lds(int no, int nc) {
+// soft: the soft instantiation's layout -- the same, with the two penalty vectors behind it
+__host__ __device__ inline AdmmLds admm_lds(int no, int nc, bool soft = false) {
   AdmmLds L;
   L.ld = no | 1;   // (an odd leading dimension: a column of a row-major matrix is conflict-free)
   L.lp = no > nc ? no : nc;
@@ -58,7 +60,9 @@ __host__ __device__ inline AdmmLds admm_lds(int no, int nc) {
   L.xt = L.r + no;
   L.pa = L.xt + no;                   // [QP_WAVES][lp] partial sums of G'v, then of G xt
   L.pb = L.pa + QP_WAVES * L.lp;    // [QP_WAVES][no] partial sums of K^-1 r
-  L.total = L.pb + QP_WAVES * no;
+  L.sl = L.pb + QP_WAVES * no;      // lin, quad [nc] (soft only)
+  L.sq = L.sl + (soft ? nc : 0);
+  L.total = L.sq + (soft ? nc : 0);
   L.total += L.total & 1;
   return L;
 }
@@ -69,18 +73,22 @@ __host__ __device__ inline AdmmLds admm_lds(int no, int nc) {
 // 10 000 cycles per iteration on three matrix-vector products of 36 x 76.
 // SOLVE: `iters` is max_iter, rho is the instance's s.rho[inst] and the loop ends at the first check that
 // decides; the iterates of the plain iteration are the same as before.
-template <bool SOLVE>
+// S = SoftSolveArgs: the soft instantiation (mpcasm_qp_solve_soft) -- the penalties loaded and tested beside h, the
+// z update qp_soft_z, a soft row's dy left out of the primal certificate; nothing else differs.
+template <bool SOLVE, typename S = SolveArgs>
 __global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
     int no, int nc, const double* __restrict__ P, const double* __restrict__ q,
     const double* __restrict__ G, const double* __restrict__ h, double* __restrict__ X,
     double* __restrict__ Y, double* __restrict__ Z, double* __restrict__ res, double rho, double sigma,
-    double alpha, int iters, int warm, int batch, double* __restrict__ Kinv, int kinv_valid, SolveArgs s) {
+    double alpha, int iters, int warm, int batch, double* __restrict__ Kinv, int kinv_valid, S s) {
+  constexpr bool SOFT = std::is_same<S, SoftSolveArgs>::value;
+  static_assert(SOLVE || !SOFT, "soft rows are the solve mode's");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long inst = blockIdx.x;
   if (inst >= batch) return;
-  const AdmmLds L = admm_lds(no, nc);
+  const AdmmLds L = admm_lds(no, nc, SOFT);
   const int ld = L.ld, lp = L.lp;
   double* Mi = sm + L.mi;   // K, then its Cholesky factor (lower), then K^-1
   double* Gs = sm + L.gs;   // G [nc][ld]; in between: T = L^-1 [no][ld]
@@ -94,6 +102,8 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
   double* xt = sm + L.xt;
   double* pa = sm + L.pa;
   double* pbuf = sm + L.pb;
+  double* sl = sm + L.sl;   // (SOFT only)
+  double* sq = sm + L.sq;
   const double* Pb = P + (size_t)inst * no * no;
   const double* Gb = G + (size_t)inst * nc * no;
   auto load_g = [&]() {
@@ -108,6 +118,7 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
   // `given` -- hands K^-1 back in: no factorisation, the larger part of a call of 25 iterations)
   if constexpr (SOLVE) rho = s.rho[inst];
   const bool reuse = Kinv != nullptr && kinv_valid != 0;
+  bool pen_bad = false;
   load_g();
   for (int e = tid; e < no; e += QP_BLOCK) {
     qs[e] = q[(size_t)inst * no + e];
@@ -118,8 +129,19 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
     hs[e] = hv;
     ys[e] = warm ? Y[(size_t)inst * nc + e] : 0.0;
     zs[e] = warm ? Z[(size_t)inst * nc + e] : fmin(0.0, hv);   // (a cold start: z = min(G x, h) with x = 0)
+    if constexpr (SOFT) {
+      const double lv = s.soft.lin[inst * s.soft.stride + e], qv = s.soft.quad[inst * s.soft.stride + e];
+      sl[e] = lv;
+      sq[e] = qv;
+      pen_bad = pen_bad || !qp_soft_valid(lv, qv);
+    }
+  }
+  if constexpr (SOFT) {   // (one bad pair: the instance is not solved; pa is free until the iterations)
+    const bool any = __ballot(pen_bad) != 0;
+    if (lane == 0) pa[wave] = any ? 1.0 : 0.0;
   }
   __syncthreads();
+  if constexpr (SOFT) pen_bad = (pa[0] + pa[1]) + (pa[2] + pa[3]) != 0.0;
 
   // K from G in LDS and P in memory, factored and inverted into Mi (false: K is not positive definite);
   // the solve mode calls it again when rho moves
@@ -173,7 +195,7 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
   };
 
   bool ok = true;
-  if (SOLVE && !(rho > 0.0)) {   // (no step to take: the solve calls the instance not convex)
+  if (SOLVE && (!(rho > 0.0) || pen_bad)) {   // (no step to take: the solve calls the instance not convex)
     ok = false;
     if (Kinv != nullptr)
       for (int e = tid; e < no * no; e += QP_BLOCK) Kinv[(size_t)inst * no * no + e] = __builtin_nan("");
@@ -223,12 +245,15 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_kernel(
     for (int r = tid; r < nc; r += QP_BLOCK) {
       const double zt = (pa[r] + pa[lp + r]) + (pa[2 * lp + r] + pa[3 * lp + r]);
       const double zr = fma(alpha, zt, (1.0 - alpha) * zs[r]);
-      const double zn = fmin(fma(ys[r], inv_rho, zr), hs[r]);
+      double zn;
+      if constexpr (SOFT) zn = qp_soft_z(fma(ys[r], inv_rho, zr), hs[r], rho, sl[r], sq + r);
+      else zn = fmin(fma(ys[r], inv_rho, zr), hs[r]);
       const double yo = ys[r], yn = fma(rho, zr - zn, yo);
       ys[r] = yn;
       zs[r] = zn;
       vs[r] = fma(rho, zn, -yn);
-      if (due) pa[r] = fmax(yn - yo, 0.0);   // (dy projected on the normal cone of (-inf, h])
+      // (dy projected on the normal cone of (-inf, h]; a soft row has none: its y climbing to lin is no certificate)
+      if (due) pa[r] = SOFT && qp_soft_row(sl[r]) ? 0.0 : fmax(yn - yo, 0.0);
     }
     __syncthreads();
     if constexpr (SOLVE) {
@@ -361,6 +386,17 @@ int launch_qp_solve(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipE
   return launch_with_lds(admm_kernel<true>, (unsigned)b.batch, QP_BLOCK, admm_lds_bytes(b.no, b.nc), stream, err,
                          b.no, b.nc, b.P, b.q, b.G, b.h, b.x, b.y, b.z, s.res, 0.0, s.sigma, s.alpha, s.max_iter,
                          s.warm, b.batch, s.kinv, s.kinv_valid, static_cast<const SolveArgs&>(s));
+}
+
+size_t admm_soft_lds_bytes(int no, int nc) { return (size_t)admm_lds(no, nc, true).total * sizeof(double); }
+
+int launch_qp_solve_soft(const QpBatch& b, const QpSolve& s, const QpSoft& soft, hipStream_t stream, hipError_t* err) {
+  SoftSolveArgs sa;
+  static_cast<SolveArgs&>(sa) = s;
+  sa.soft = soft;
+  return launch_with_lds(admm_kernel<true, SoftSolveArgs>, (unsigned)b.batch, QP_BLOCK, admm_soft_lds_bytes(b.no, b.nc),
+                         stream, err, b.no, b.nc, b.P, b.q, b.G, b.h, b.x, b.y, b.z, s.res, 0.0, s.sigma, s.alpha,
+                         s.max_iter, s.warm, b.batch, s.kinv, s.kinv_valid, sa);
 }
 
 }  // namespace mpcasm

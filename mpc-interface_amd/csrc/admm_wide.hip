@@ -39,9 +39,10 @@ constexpr int WIDE_ROWS = 4;   // rows of G a wavefront keeps in flight in the p
 constexpr int WIDE_MAX_NO = 512;
 
 struct WideLds {
-  int z, y, h, xs, dx, rv, pa, pb, pc, pk, pe, red, mi, ld, total;
+  int z, y, h, xs, dx, rv, pa, pb, pc, pk, pe, red, sl, sq, mi, ld, total;
 };
-__host__ __device__ inline WideLds wide_lds(int no, int nc, bool onchip) {
+// soft: the soft instantiations' layout -- the two penalty vectors between the verdict terms and K^-1
+__host__ __device__ inline WideLds wide_lds(int no, int nc, bool onchip, bool soft = false) {
   WideLds L;
   L.ld = no | 1;   // (K^-1 in LDS: an odd leading dimension, the factorisation walks its columns)
   L.z = 0;
@@ -56,25 +57,31 @@ __host__ __device__ inline WideLds wide_lds(int no, int nc, bool onchip) {
   L.pk = L.pc + QP_WAVES * no;   // of K^-1 r; of P x (checks)
   L.pe = L.pk + QP_WAVES * no;   // of P dx (checks)
   L.red = L.pe + QP_WAVES * no;  // [QP_WAVES][16] a wavefront's row verdict terms
-  L.mi = L.red + QP_WAVES * 16;
+  L.sl = L.red + QP_WAVES * 16;  // lin, quad [nc] (soft only)
+  L.sq = L.sl + (soft ? nc : 0);
+  L.mi = L.sq + (soft ? nc : 0);
   L.total = L.mi + (onchip ? no * L.ld : 0);
   L.total += L.total & 1;
   return L;
 }
 
-// NCH: columns per lane (no <= 64 NCH); ONCHIP: K^-1 in LDS
-template <int NCH, bool ONCHIP>
+// NCH: columns per lane (no <= 64 NCH); ONCHIP: K^-1 in LDS; S = SoftSolveArgs: the soft instantiation
+// (mpcasm_qp_solve_wide_soft), which differs as admm.hip's does -- the load, the z update, the dy a check keeps
+template <int NCH, bool ONCHIP, typename S = SolveArgs>
 __global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
     int no, int nc, const double* __restrict__ P, const double* __restrict__ q, const double* __restrict__ G,
     const double* __restrict__ h, double* __restrict__ X, double* __restrict__ Y, double* __restrict__ Z,
     double* __restrict__ res, double sigma, double alpha, int iters, int warm, int batch, double* Kinv,
-    int kinv_valid, SolveArgs s) {
+    int kinv_valid, S s) {
+  constexpr bool SOFT = std::is_same<S, SoftSolveArgs>::value;
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long inst = blockIdx.x;
   if (inst >= batch) return;
-  const WideLds L = wide_lds(no, nc, ONCHIP);
+  const WideLds L = wide_lds(no, nc, ONCHIP, SOFT);
+  double* sl = sm + L.sl;   // (SOFT only)
+  double* sq = sm + L.sq;
   double* zs = sm + L.z;
   double* ys = sm + L.y;
   double* hs = sm + L.h;
@@ -95,6 +102,7 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
   const double bad = __builtin_nan("");
 
   double rho = s.rho[inst];
+  bool pen_bad = false;
   double xr[NCH], qr[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -107,6 +115,18 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
     hs[e] = hv;
     ys[e] = warm ? Y[(size_t)inst * nc + e] : 0.0;
     zs[e] = warm ? Z[(size_t)inst * nc + e] : fmin(0.0, hv);
+    if constexpr (SOFT) {
+      const double lv = s.soft.lin[inst * s.soft.stride + e], qv = s.soft.quad[inst * s.soft.stride + e];
+      sl[e] = lv;
+      sq[e] = qv;
+      pen_bad = pen_bad || !qp_soft_valid(lv, qv);
+    }
+  }
+  if constexpr (SOFT) {   // (one bad pair: the instance is not solved; red is free until the first pass)
+    const bool any = __ballot(pen_bad) != 0;
+    if (lane == 0) red[wave * 16] = any ? 1.0 : 0.0;
+    __syncthreads();
+    pen_bad = (red[0] + red[16]) + (red[32] + red[48]) != 0.0;
   }
 
   // ---- K = P + sigma I + rho G'G, then K^-1 in place (false: K is not positive definite) ---------------
@@ -268,9 +288,10 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
         if (UPD) {
           const double zr = fma(alpha, zt[u], (1.0 - alpha) * zn);
           const double yo = yn;
-          zn = fmin(fma(yo, inv_rho, zr), hs[i]);
+          if constexpr (SOFT) zn = qp_soft_z(fma(yo, inv_rho, zr), hs[i], rho, sl[i], sq + i);
+          else zn = fmin(fma(yo, inv_rho, zr), hs[i]);
           yn = fma(rho, zr - zn, yo);
-          dy = fmax(yn - yo, 0.0);
+          dy = SOFT && qp_soft_row(sl[i]) ? 0.0 : fmax(yn - yo, 0.0);   // (a soft row certifies nothing)
           if (lane == 0) zs[i] = zn, ys[i] = yn;
         }
         const double v = fma(rho, zn, -yn);
@@ -333,7 +354,7 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
   using F = std::false_type;
 
   bool ok = true;
-  if (!(rho > 0.0)) {   // (no step to take: the instance is not convex)
+  if (!(rho > 0.0) || pen_bad) {   // (no step to take: the instance is not convex)
     ok = false;
     if (Kg != nullptr)
       for (int e = tid; e < no * no; e += QP_BLOCK) Kg[e] = bad;
@@ -524,8 +545,8 @@ __global__ __launch_bounds__(QP_BLOCK) void admm_wide_kernel(
 
 // where K^-1 lives for (no, nc): in LDS when it fits beside the vectors, unless MPCASM_QP_WIDE_KINV says
 // otherwise ("lds": there whenever it fits; "global": always in d_kinv)
-bool wide_kinv_on_chip(int no, int nc) {
-  const bool fits = (size_t)wide_lds(no, nc, true).total * sizeof(double) <= (size_t)RESIDENT_LDS_LIMIT;
+bool wide_kinv_on_chip(int no, int nc, bool soft) {
+  const bool fits = (size_t)wide_lds(no, nc, true, soft).total * sizeof(double) <= (size_t)RESIDENT_LDS_LIMIT;
   const char* env = getenv("MPCASM_QP_WIDE_KINV");
   if (env != nullptr && strcmp(env, "global") == 0) return false;
   if (env != nullptr && strcmp(env, "lds") == 0) return fits;
@@ -539,14 +560,32 @@ int launch_wide(const QpBatch& b, const QpSolve& s, size_t lds, hipStream_t stre
                          s.kinv, s.kinv_valid, static_cast<const SolveArgs&>(s));
 }
 
-}  // namespace
+template <int NCH, bool ONCHIP>
+int launch_wide_soft(const QpBatch& b, const QpSolve& s, const QpSoft& soft, size_t lds, hipStream_t stream,
+                     hipError_t* err) {
+  SoftSolveArgs sa;
+  static_cast<SolveArgs&>(sa) = s;
+  sa.soft = soft;
+  return launch_with_lds(admm_wide_kernel<NCH, ONCHIP, SoftSolveArgs>, (unsigned)b.batch, QP_BLOCK, lds, stream, err,
+                         b.no, b.nc, b.P, b.q, b.G, b.h, b.x, b.y, b.z, s.res, s.sigma, s.alpha, s.max_iter, s.warm,
+                         b.batch, s.kinv, s.kinv_valid, sa);
+}
 
-int qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
-  const bool on = no <= WIDE_MAX_NO && wide_kinv_on_chip(no, nc);
-  const size_t lds = (size_t)wide_lds(no, nc, on).total * sizeof(double);
+int wide_info(int no, int nc, bool soft, int64_t* lds_bytes, int32_t* kinv_on_chip) {
+  const bool on = no <= WIDE_MAX_NO && wide_kinv_on_chip(no, nc, soft);
+  const size_t lds = (size_t)wide_lds(no, nc, on, soft).total * sizeof(double);
   if (lds_bytes) *lds_bytes = (int64_t)lds;
   if (kinv_on_chip) *kinv_on_chip = on ? 1 : 0;
   return no > WIDE_MAX_NO || lds > (size_t)RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
+}
+
+}  // namespace
+
+int qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
+  return wide_info(no, nc, false, lds_bytes, kinv_on_chip);
+}
+int qp_solve_wide_soft_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
+  return wide_info(no, nc, true, lds_bytes, kinv_on_chip);
 }
 
 int launch_qp_solve_wide(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipError_t* err) {
@@ -561,6 +600,22 @@ int launch_qp_solve_wide(const QpBatch& b, const QpSolve& s, hipStream_t stream,
       {launch_wide<1, true>, launch_wide<2, true>, launch_wide<4, true>, launch_wide<8, true>},
       {launch_wide<1, false>, launch_wide<2, false>, launch_wide<4, false>, launch_wide<8, false>}};
   return table[on ? 0 : 1][b.no <= 64 ? 0 : b.no <= 128 ? 1 : b.no <= 256 ? 2 : 3](b, s, (size_t)lds, stream, err);
+}
+
+int launch_qp_solve_wide_soft(const QpBatch& b, const QpSolve& s, const QpSoft& soft, hipStream_t stream,
+                              hipError_t* err) {
+  int64_t lds = 0;
+  int32_t on = 0;
+  const int rc = qp_solve_wide_soft_info(b.no, b.nc, &lds, &on);
+  if (rc != MPCASM_OK) return rc;
+  if (!on && s.kinv == nullptr) return MPCASM_ERR_ARG;   // (d_kinv is the factorisation's workspace)
+  using Launch = int (*)(const QpBatch&, const QpSolve&, const QpSoft&, size_t, hipStream_t, hipError_t*);
+  static const Launch table[2][4] = {
+      {launch_wide_soft<1, true>, launch_wide_soft<2, true>, launch_wide_soft<4, true>, launch_wide_soft<8, true>},
+      {launch_wide_soft<1, false>, launch_wide_soft<2, false>, launch_wide_soft<4, false>,
+       launch_wide_soft<8, false>}};
+  return table[on ? 0 : 1][b.no <= 64 ? 0 : b.no <= 128 ? 1 : b.no <= 256 ? 2 : 3](b, s, soft, (size_t)lds, stream,
+                                                                                    err);
 }
 
 }  // namespace mpcasm

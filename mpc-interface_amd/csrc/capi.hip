@@ -872,18 +872,25 @@ int mpcasm_admm(int no, int nc, const double* d_P, const double* d_q, const doub
 
 // mpcasm_qp_solve and mpcasm_qp_solve_wide: the same arguments, checked in the same order; the wide entry also
 // asks its launch where K^-1 lives, before it looks at the batch
-static int qp_solve_entry(bool wide, const QpBatch& b, const QpSolve& s, void* stream) {
+// soft: the penalties of the _soft entries (NULL: the hard ones), their stride nc or 0
+static int qp_solve_entry(bool wide, const QpBatch& b, const QpSolve& s, void* stream, const QpSoft* soft = nullptr) {
   if (!qp_solve_settings_ok(s) || !qp_sizes_ok(b.no, b.nc) || b.batch < 0) return MPCASM_ERR_ARG;
+  if (soft && soft->stride != 0 && soft->stride != b.nc) return MPCASM_ERR_ARG;
   int32_t on_chip = 1;
   if (wide) {
-    const int limit = qp_solve_wide_info(b.no, b.nc, nullptr, &on_chip);
+    const int limit = soft ? qp_solve_wide_soft_info(b.no, b.nc, nullptr, &on_chip)
+                           : qp_solve_wide_info(b.no, b.nc, nullptr, &on_chip);
     if (limit != MPCASM_OK) return limit;
   }
   if (b.batch == 0) return MPCASM_OK;
   if (!qp_pointers_ok(b) || !s.rho || !s.status || !s.iters) return MPCASM_ERR_ARG;
+  if (soft && b.nc > 0 && (!soft->lin || !soft->quad)) return MPCASM_ERR_ARG;
   if ((s.kinv_valid != 0 || on_chip == 0) && s.kinv == nullptr) return MPCASM_ERR_ARG;
   hipError_t err;
   const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (soft)
+    return launched(wide ? launch_qp_solve_wide_soft(b, s, *soft, st, &err) : launch_qp_solve_soft(b, s, *soft, st, &err),
+                    err);
   return launched(wide ? launch_qp_solve_wide(b, s, st, &err) : launch_qp_solve(b, s, st, &err), err);
 }
 int mpcasm_qp_solve(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
@@ -921,6 +928,47 @@ int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, c
 int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
   if (!qp_sizes_ok(no, nc) || !lds_bytes || !kinv_on_chip) return MPCASM_ERR_ARG;
   return qp_solve_wide_info(no, nc, lds_bytes, kinv_on_chip);
+}
+
+int mpcasm_qp_solve_soft(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                         const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                         double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                         double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                         int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                         int kinv_valid, void* stream, const double* d_soft_lin, const double* d_soft_quad,
+                         int64_t soft_stride) {
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
+                   adaptive_rho_interval},
+                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
+  const QpSoft soft{d_soft_lin, d_soft_quad, soft_stride};
+  return qp_solve_entry(false, b, s, stream, &soft);
+}
+
+int mpcasm_qp_solve_soft_lds_bytes(int no, int nc, int64_t* out) {
+  if (!qp_sizes_ok(no, nc) || !out) return MPCASM_ERR_ARG;
+  *out = (int64_t)admm_soft_lds_bytes(no, nc);
+  return *out > RESIDENT_LDS_LIMIT ? MPCASM_ERR_LIMIT : MPCASM_OK;
+}
+
+int mpcasm_qp_solve_wide_soft(int no, int nc, const double* d_P, const double* d_q, const double* d_G,
+                              const double* d_h, double* d_x, double* d_y, double* d_z, int warm, double* d_rho,
+                              double sigma, double alpha, double eps_abs, double eps_rel, double eps_prim_inf,
+                              double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
+                              int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
+                              int kinv_valid, void* stream, const double* d_soft_lin, const double* d_soft_quad,
+                              int64_t soft_stride) {
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
+                   adaptive_rho_interval},
+                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
+  const QpSoft soft{d_soft_lin, d_soft_quad, soft_stride};
+  return qp_solve_entry(true, b, s, stream, &soft);
+}
+
+int mpcasm_qp_solve_wide_soft_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
+  if (!qp_sizes_ok(no, nc) || !lds_bytes || !kinv_on_chip) return MPCASM_ERR_ARG;
+  return qp_solve_wide_soft_info(no, nc, lds_bytes, kinv_on_chip);
 }
 
 // what the two polish entries decide alike: MPCASM_OK with *go set where there is something to launch

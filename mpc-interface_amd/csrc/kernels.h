@@ -193,6 +193,16 @@ struct QpSolve : SolveArgs {
   int kinv_valid;
   double* res;
 };
+// soft limits (mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft): row i costs lin_i t + 1/2 quad_i t^2 for
+// t = (Gx - h)_i > 0; lin_i = +inf is a hard row.  [batch][nc] at `stride` doubles (0: one pair for the batch)
+struct QpSoft {
+  const double *lin, *quad;
+  int64_t stride;
+};
+// what a soft instantiation's kernel takes in SolveArgs' place
+struct SoftSolveArgs : SolveArgs {
+  QpSoft soft;
+};
 struct QpPolish {
   const int32_t* status;
   double delta;
@@ -222,6 +232,12 @@ int launch_qp_solve(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipE
 // admm_wide.hip: the solve to tolerance with G read in place and K^-1 in LDS or in d_kinv
 int qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
 int launch_qp_solve_wide(const QpBatch& b, const QpSolve& s, hipStream_t stream, hipError_t* err);
+// the soft instantiations of the two solves: the penalty vectors on chip beside h
+size_t admm_soft_lds_bytes(int no, int nc);
+int launch_qp_solve_soft(const QpBatch& b, const QpSolve& s, const QpSoft& soft, hipStream_t stream, hipError_t* err);
+int qp_solve_wide_soft_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip);
+int launch_qp_solve_wide_soft(const QpBatch& b, const QpSolve& s, const QpSoft& soft, hipStream_t stream,
+                              hipError_t* err);
 // polish.hip: OSQP's polishing of solved instances (active-set KKT solve with refinement)
 size_t polish_lds_bytes(int no, int nc);
 int launch_qp_polish(const QpBatch& b, const QpPolish& p, hipStream_t stream, hipError_t* err);

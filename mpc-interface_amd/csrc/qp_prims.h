@@ -212,6 +212,21 @@ __device__ __forceinline__ bool qp_dual_infeasible(const SolveArgs& s, double nd
                                                    double mgdx) {
   return ndx > 1e-30 && qdx < -s.eps_dual_inf * ndx && npdx < s.eps_dual_inf * ndx && mgdx < s.eps_dual_inf * ndx;
 }
+// ---- soft rows (the SOFT instantiations of the two solves): row i costs lin t + 1/2 quad t^2 for t = (Gx - h)_i > 0
+// a pair the solve takes: lin in [0, +inf] (+inf: a hard row), quad in [0, +inf); a NaN fails both
+__device__ __forceinline__ bool qp_soft_valid(double lin, double quad) {
+  return lin >= 0.0 && quad >= 0.0 && quad < INFINITY;
+}
+__device__ __forceinline__ bool qp_soft_row(double lin) { return lin < INFINITY; }
+// the z update, v = alpha zt + (1 - alpha) z + y / rho: the minimiser of phi(z - h) + rho / 2 (z - v)^2.  A hard row
+// takes the hard solve's expression itself; a soft row past h stays at h while rho (v - h) <= lin (y, the slope
+// there, is below lin) and moves out at slope lin + quad (z - h) beyond
+// (quad: where the row's quad lies -- read only by a soft row past h)
+__device__ __forceinline__ double qp_soft_z(double v, double h, double rho, double lin, const double* quad) {
+  if (!qp_soft_row(lin) || !(v > h)) return fmin(v, h);
+  return h + fmax(0.0, (rho * (v - h) - lin) / (rho + *quad));
+}
+
 // the verdict of a check -- "solved", "primal infeasible", "dual infeasible", in that order; 0: go on -- from the
 // residuals r_p, r_d and their scales
 __device__ __forceinline__ int qp_verdict(const SolveArgs& s, double rp, double sp, double rd, double sd, bool pinf,

@@ -127,6 +127,16 @@ SIGNATURES = {
                              [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_qp_solve_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                                  ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_qp_solve_soft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] +
+                             [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
+                             [ctypes.c_int, _void_p, ctypes.c_int, _void_p, _void_p, _void_p, ctypes.c_int64]),
+    "mpcasm_qp_solve_soft_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_qp_solve_wide_soft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 +
+                                  [ctypes.c_int, _void_p] + [ctypes.c_double] * 6 + [ctypes.c_int] * 3 +
+                                  [_void_p] * 3 + [ctypes.c_int, _void_p, ctypes.c_int, _void_p, _void_p, _void_p,
+                                                   ctypes.c_int64]),
+    "mpcasm_qp_solve_wide_soft_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
+                                                      ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_qp_polish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 + [ctypes.c_double, ctypes.c_int,
                                                                                        _void_p, _void_p, ctypes.c_int,
                                                                                        _void_p]),

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .plan import compile_plan, is_causal, rollout_rows, rollout_sizes
+from .plan import compile_plan, is_causal, rollout_rows, rollout_sizes, soft_rows
 
 
 def _torch():
@@ -197,7 +197,8 @@ class PolishedQpSolution(collections.namedtuple("QpSolution", "x y z status iter
 
 def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
              eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False, warm=False):
+             alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False, warm=False,
+             soft=None):
     """A batch of dense QPs ``min 1/2 x'Px + q'x s.t. Gx <= h`` solved to tolerance on the device
     (``mpcasm_qp_solve``): :func:`admm`'s iteration with OSQP's termination tests and adaptive rho, every
     instance stopping on its own, nothing read back to the host (a tick can be captured in a graph).
@@ -215,10 +216,20 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
     ``polish``: :func:`polish_qp` with OSQP's defaults after the solve, on the solved instances; ``x, y, z`` and
     ``res`` of an instance whose polished point is accepted are that point's, and the solution grows a trailing field
     ``polish``, the ``(B,)`` int32 verdicts ``POLISH_*`` (a :class:`PolishedQpSolution`; without polish ``sol.polish``
-    is None and the solution has the seven fields it always had)."""
+    is None and the solution has the seven fields it always had).
+    ``soft``: ``(lin, quad)``, soft limits through ``mpcasm_qp_solve_soft`` -- row ``i`` may be violated by
+    ``t = (Gx - h)_i > 0`` at the price ``lin_i t + 1/2 quad_i t^2``; each a scalar or a tensor or array of shape
+    ``(nc,)`` (one pair for the batch) or ``(B, nc)``; ``lin_i = inf`` keeps row ``i`` hard.  A soft row takes no part
+    in the primal-infeasibility verdict; an instance with a negative or NaN penalty, or an infinite ``quad``, is
+    ``QP_NON_CVX``.  None: today's entry with today's arguments.  Not with ``polish`` (``ValueError``): the polish
+    models the hard problem.  Scalars and arrays are copied to the device here, on torch's current stream, in
+    tensors that are freed on return: a caller that passes ``stream=`` or captures a graph must pass contiguous
+    float64 DEVICE tensors (:meth:`Assembler.soft_rows`), which are handed on as they are."""
+    if polish and soft is not None:
+        raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
     sol = _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
                     max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out,
-                    warm_out=warm)
+                    warm_out=warm, soft=soft)
     if not polish:
         return sol
     verdict = polish_qp(P, q, G, h, sol, status=sol.status, stream=stream)[3]
@@ -316,9 +327,11 @@ def qp_polish_wide_info(no, nc, batch):
 
 
 def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
-              adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False, warm_out=False):
+              adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False, warm_out=False,
+              soft=None):
     """:func:`solve_qp` and :func:`solve_qp_wide` through the C entry ``entry``; ``workspace``: allocate
-    ``kinv`` when it is None (the wide path's K^-1 off chip); ``warm_out``: ``out``'s iterates hold the start."""
+    ``kinv`` when it is None (the wide path's K^-1 off chip); ``warm_out``: ``out``'s iterates hold the start;
+    ``soft``: the penalties, through ``entry`` + ``_soft``."""
     if warm_out and out is None:
         raise ValueError("warm=True is for out=: pass x, y, z for a warm start into new tensors")
     torch = require_device()
@@ -346,8 +359,13 @@ def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, e
         res = torch.empty((batch, 2), dtype=torch.float64, device=P.device)
     if workspace and kinv is None:
         lds, on = ctypes.c_int64(), ctypes.c_int32()
-        if capi.load().mpcasm_qp_solve_wide_info(no, nc, ctypes.byref(lds), ctypes.byref(on)) == 0 and not on.value:
+        info = capi.load().mpcasm_qp_solve_wide_info if soft is None else capi.load().mpcasm_qp_solve_wide_soft_info
+        if info(no, nc, ctypes.byref(lds), ctypes.byref(on)) == 0 and not on.value:
             kinv = torch.empty((batch, no, no), dtype=torch.float64, device=P.device)
+    extra = ()
+    if soft is not None:
+        lin, quad, stride = _soft_operands(torch, soft, batch, nc, P.device)
+        entry, extra = entry + "_soft", (lin.data_ptr(), quad.data_ptr(), stride)
     with torch.cuda.device(P.device):
         rc = getattr(capi.load(), entry)(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
                                          x.data_ptr(), y.data_ptr(), z.data_ptr(), 1 if warm else 0,
@@ -356,9 +374,56 @@ def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, e
                                          int(check_every), int(adaptive_rho_interval), status.data_ptr(),
                                          iters.data_ptr(), res.data_ptr(), batch,
                                          kinv.data_ptr() if kinv is not None else None, 1 if kinv_valid else 0,
-                                         _stream_handle(torch, stream))
+                                         _stream_handle(torch, stream), *extra)
     capi.check(rc, entry)
     return QpSolution(x, y, z, status, iters, res, rho)
+
+
+def _soft_operands(torch, soft, batch, nc, device):
+    """``soft=(lin, quad)`` as the C entries take it: two contiguous float64 tensors on ``device`` and their stride,
+    0 for one pair of rows ``(nc,)`` (scalars are spread over the rows), ``nc`` for ``(B, nc)``.  A tensor that is
+    already there is passed as it is (a loop that replays a graph keeps it at a fixed address)."""
+    try:
+        lin, quad = soft
+    except (TypeError, ValueError):
+        raise ValueError("soft: a pair (lin, quad)") from None
+    out = []
+    for v in (lin, quad):
+        if not isinstance(v, torch.Tensor):
+            v = torch.as_tensor(np.asarray(v, dtype=np.float64))
+        if v.dim() == 0:
+            v = v.expand(nc)
+        out.append(v.to(device=device, dtype=torch.float64).contiguous())
+    lin, quad = out
+    if lin.shape != quad.shape or tuple(lin.shape) not in ((nc,), (batch, nc)):
+        raise ValueError("soft: lin and quad scalars, (nc,) or (B, nc), both alike")
+    return lin, quad, (0 if lin.dim() == 1 else nc)
+
+
+def soft_pair(soft, nc, device):
+    """``soft=(lin, quad)`` of a loop, once: two ``(nc,)`` float64 tensors on ``device`` that every tick passes at
+    stride 0 (scalars spread over the rows).  ``ValueError`` for anything but scalars or ``(nc,)`` vectors."""
+    torch = require_device()
+    lin, quad, stride = _soft_operands(torch, soft, 1, nc, device)
+    if stride != 0:
+        raise ValueError("soft: a loop takes scalars or (nc,) vectors, one pair of rows for all instances")
+    return lin, quad
+
+
+def qp_solve_soft_lds_bytes(no, nc):
+    """:func:`qp_solve_lds_bytes` for ``solve_qp(soft=...)`` (``mpcasm_qp_solve_soft_lds_bytes``)."""
+    out = ctypes.c_int64()
+    rc = capi.load().mpcasm_qp_solve_soft_lds_bytes(int(no), int(nc), ctypes.byref(out))
+    capi.check(rc, "mpcasm_qp_solve_soft_lds_bytes")
+    return int(out.value)
+
+
+def qp_solve_wide_soft_info(no, nc):
+    """:func:`qp_solve_wide_info` for ``solve_qp_wide(soft=...)`` (``mpcasm_qp_solve_wide_soft_info``)."""
+    lds, on = ctypes.c_int64(), ctypes.c_int32()
+    rc = capi.load().mpcasm_qp_solve_wide_soft_info(int(no), int(nc), ctypes.byref(lds), ctypes.byref(on))
+    capi.check(rc, "mpcasm_qp_solve_wide_soft_info")
+    return int(lds.value), bool(on.value)
 
 
 def qp_solve_lds_bytes(no, nc):
@@ -372,17 +437,21 @@ def qp_solve_lds_bytes(no, nc):
 
 def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
                   eps_dual_inf=1e-4, max_iter=4000, check_every=25, adaptive_rho_interval=100, sigma=OSQP_SIGMA,
-                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False, warm=False):
+                  alpha=OSQP_ALPHA, kinv=None, kinv_valid=False, stream=None, out=None, polish=False, warm=False,
+                  soft=None):
     """:func:`solve_qp` for QPs whose matrices do not fit on chip (``mpcasm_qp_solve_wide``): the same
     arguments, rules and :class:`QpSolution`, up to 512 unknowns and 2 048 limits (:func:`qp_solve_wide_info`).
     ``G`` is read in place once per iteration; ``K^-1`` lives in LDS where it fits, else in ``kinv`` -- a
     ``(B, no, no)`` workspace allocated here when the caller passes none (the environment variable
     ``MPCASM_QP_WIDE_KINV`` = ``lds`` / ``global`` overrides where it lives).
     ``polish``: :func:`polish_qp_wide` with OSQP's defaults after the solve, on the solved instances, as
-    :func:`solve_qp` does with :func:`polish_qp`: a :class:`PolishedQpSolution`."""
+    :func:`solve_qp` does with :func:`polish_qp`: a :class:`PolishedQpSolution`.
+    ``soft``: as for :func:`solve_qp`, through ``mpcasm_qp_solve_wide_soft``."""
+    if polish and soft is not None:
+        raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
     sol = _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
                     eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
-                    stream, out, workspace=True, warm_out=warm)
+                    stream, out, workspace=True, warm_out=warm, soft=soft)
     if not polish:
         return sol
     verdict = polish_qp_wide(P, q, G, h, sol, status=sol.status, stream=stream)[3]
@@ -1188,6 +1257,12 @@ class Assembler:
         ``("cost", "track vel_x", "aim")`` or ``("limit", 3, "center")``."""
         start, rows, cols = self.plan.param_slots[(kind, name, field)]
         return slice(start, start + rows * cols), (rows, cols)
+
+    def soft_rows(self, rules):
+        """:func:`plan.soft_rows` of this assembler's plan on its device: ``(lin, quad)``, two ``(nc,)`` float64
+        tensors for ``solve_qp(soft=...)``."""
+        lin, quad = soft_rows(self.plan, rules)
+        return (self._torch.as_tensor(lin, device=self.device), self._torch.as_tensor(quad, device=self.device))
 
     def set_param(self, kind, name, field, values):
         """``values``: shape ``(rows, cols)`` (all instances) or ``(B, rows, cols)``."""

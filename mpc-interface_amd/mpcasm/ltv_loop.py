@@ -18,8 +18,8 @@ launch: the window's address changes every tick, which a captured graph would no
 import numpy as np
 
 from .engine import (APPLY_ALL, APPLY_SOLVED, OSQP_RHO, WARM_SOLVED, Assembler, WarmStore, _ltv_sequences, ltv_augment,
-                     ltv_close, ltv_lqr, polish_qp_wide, qp_polish_wide_info, qp_solve_wide_info, solve_qp_wide,
-                     warm_start_qp, warm_store_qp)
+                     ltv_close, ltv_lqr, polish_qp_wide, qp_polish_wide_info, qp_solve_wide_info,
+                     qp_solve_wide_soft_info, soft_pair, solve_qp_wide, warm_start_qp, warm_store_qp)
 
 
 class LtvLoop:
@@ -64,6 +64,11 @@ class LtvLoop:
     finds ``out["u"][:, :, 0]`` there, bit for bit, a held one what it had.  What stays out: ``n + m > 4``; limits
     on the input's RATE (they mix two steps' states); and the augmented pendulum runs the sweep kernel's generic
     instantiation, not the one compiled for 3 states.
+    ``soft`` (keyword only, default None: nothing changes): soft limits (``engine.solve_qp_wide(soft=...)``).  A pair
+    of scalars ``(lin, quad)`` makes every row soft -- a violation ``t > 0`` costs ``lin t + 1/2 quad t^2``; a
+    callable gets the loop's :class:`~mpcasm.engine.Assembler` and returns ``(lin, quad)``, scalars or ``(nc,)``
+    vectors (``asm.soft_rows({limit index: (lin, quad)})``; ``inf`` keeps a row hard).  The vectors are built once
+    and passed at stride 0 on every tick.  ``warm`` composes unchanged; with ``polish`` it is a ``ValueError``.
     ``solver_kwargs`` go to :func:`~mpcasm.engine.solve_qp_wide` (``eps_abs``, ``max_iter``, ...)."""
 
     def __init__(self, form, name, batch, A_seq, B_seq, on_unsolved="hold", polish=False, **solver_kwargs):
@@ -71,6 +76,11 @@ class LtvLoop:
         warm = solver_kwargs.pop("warm", False)
         feedback = solver_kwargs.pop("feedback", None)
         self.true_input = bool(solver_kwargs.pop("true_input", False))
+        soft = solver_kwargs.pop("soft", None)
+        if soft is not None and polish:
+            raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
+        if soft is not None and not callable(soft) and not (isinstance(soft, (tuple, list)) and len(soft) == 2):
+            raise ValueError("soft: a pair (lin, quad) or a callable that takes an Assembler and returns one")
         if self.true_input:               # (decided on the host, from the formulation: before anything is compiled)
             self._check_true_input(form, name, A_seq, B_seq, feedback)
         if on_unsolved not in ("hold", "apply"):
@@ -100,8 +110,12 @@ class LtvLoop:
                         z=torch.zeros((B, asm.nc), **f), status=torch.zeros(B, **i32), iters=torch.zeros(B, **i32),
                         res=torch.zeros((B, 2), **f), rho=torch.full((B,), OSQP_RHO, **f))
         self._solver_kwargs = dict(solver_kwargs)
+        # the penalties: one pair of rows for every instance and tick, at a fixed address
+        if soft is not None:
+            self._solver_kwargs["soft"] = soft_pair(soft(asm) if callable(soft) else soft, asm.nc, asm.device)
+        info = qp_solve_wide_info if soft is None else qp_solve_wide_soft_info
         # where K^-1 does not fit on chip it is the solver's workspace: allocated once, unless the caller brings one
-        if "kinv" not in solver_kwargs and not qp_solve_wide_info(asm.no, asm.nc)[1]:
+        if "kinv" not in solver_kwargs and not info(asm.no, asm.nc)[1]:
             self._solver_kwargs["kinv"] = torch.empty((B, asm.no, asm.no), **f)
         # the polish's workspace and verdicts, allocated once
         self.polish = bool(polish)

@@ -2280,3 +2280,32 @@ def compile_plan(form, costs=None, limits=None, lti=(), csc=None, workspace="aut
     plan.fingerprint = structure_fingerprint(costs, limits)
     plan.lti = [dict(name=g["name"], n=g["n"], m=g["m"], N=g["N"], ids=list(g["ids"])) for g in groups]
     return plan
+
+
+def soft_rows(plan, rules):
+    """The penalty vectors of a plan's soft limits, for ``engine.solve_qp(soft=...)``: ``rules`` maps a limit's
+    index -- the ``idx`` of ``plan.param_slots[("limit", idx, ...)]``, its rows ``plan.limit_rows[idx]`` -- to
+    ``(lin, quad)``, each a scalar or an array with one entry per row of that limit.  A violation ``t > 0`` of such
+    a row costs ``lin t + 1/2 quad t^2``.  Returns ``(lin, quad)``, two ``(plan.nc,)`` float64 arrays, ``+inf`` /
+    ``0`` (a hard row) on every row no rule names.  ``ValueError``: an index that is no limit's, a wrong length, a
+    negative or NaN value, a ``quad`` of ``+inf``.  Pure host."""
+    lin, quad = np.full(plan.nc, np.inf), np.zeros(plan.nc)
+    for idx, pair in rules.items():
+        if isinstance(idx, bool) or not isinstance(idx, (int, np.integer)) or not 0 <= idx < len(plan.limit_rows):
+            raise ValueError("soft_rows: %r is not the index of a limit (0 .. %d)" % (idx, len(plan.limit_rows) - 1))
+        try:
+            lv, qv = pair
+        except (TypeError, ValueError):
+            raise ValueError("soft_rows: limit %d takes a pair (lin, quad)" % idx) from None
+        row0, nrows = plan.limit_rows[idx]
+        for name, v, out in (("lin", lv, lin), ("quad", qv, quad)):
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != nrows):
+                raise ValueError("soft_rows: %s of limit %d: a scalar or %d values, got shape %s"
+                                 % (name, idx, nrows, v.shape))
+            if np.isnan(v).any() or (v < 0.0).any():
+                raise ValueError("soft_rows: %s of limit %d is negative or NaN" % (name, idx))
+            if name == "quad" and np.isinf(v).any():
+                raise ValueError("soft_rows: quad of limit %d is infinite (make the row hard: lin = inf)" % idx)
+            out[row0:row0 + nrows] = v
+    return lin, quad

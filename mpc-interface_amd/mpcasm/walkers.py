@@ -150,10 +150,17 @@ class WalkerFleet:
     margins or any other parameter; columns that are none of :data:`COMMAND_COLUMNS` start at the initial values
     (zero without).  Off by default: every walker keeps ``conf``'s gait and the parameters of a place are fixed
     the first time it comes round.
+    ``soft``: soft limits (``engine.solve_qp(soft=...)``): a pair of scalars ``(lin, quad)`` makes every row of every
+    QP soft -- a violation ``t > 0`` costs ``lin t + 1/2 quad t^2`` -- so that a disturbed walker still gets a plan
+    instead of PRIMAL_INFEASIBLE; a callable gets a bucket's :class:`~mpcasm.engine.Assembler` and returns
+    ``(lin, quad)``, scalars or ``(nc,)`` vectors (``asm.soft_rows({limit index: (lin, quad)})``; ``inf`` keeps a
+    row hard).  The vectors are built once per bucket and passed at stride 0 on every tick, captured graphs
+    included.  ``warm`` composes unchanged (the shifted start is only a start); with ``polish`` it is a
+    ``ValueError`` (the polish models the hard problem).  None (default): hard limits, today's solve.
     """
 
     def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False,
-                 on_unsolved="hold", polish=False, warm=False, commands=False, command_rules=None):
+                 on_unsolved="hold", polish=False, warm=False, commands=False, command_rules=None, soft=None):
         from .engine import APPLY_ALL, APPLY_SOLVED, Assembler, require_device
 
         if on_unsolved not in ("hold", "apply"):
@@ -162,6 +169,12 @@ class WalkerFleet:
         # polish=True: every solved QP is polished (engine.polish_qp, OSQP's defaults) before its solution
         # becomes the walker's next `given`
         self._polish = bool(polish)
+        # soft=: the penalties of the solve, a pair or what makes one from a bucket's assembler
+        if soft is not None and self._polish:
+            raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
+        if soft is not None and not callable(soft) and not (isinstance(soft, (tuple, list)) and len(soft) == 2):
+            raise ValueError("soft: a pair (lin, quad) or a callable that takes an Assembler and returns one")
+        self._soft = soft
         # warm=True: one warm store for the fleet (a record per walker, sized by the widest bucket), built with
         # the buckets' solver buffers; per place of the step cycle the shift maps are kept with its other inputs
         self._warm, self._warm_store = bool(warm), None
@@ -440,7 +453,8 @@ class WalkerFleet:
         solver buffers, then its walkers' next ``given`` from the solution, by the fleet's rule.  A warm fleet:
         the start from the store (tag: the place before), the solve from it, the store (tag: this place) after
         the polish when there is one."""
-        from .engine import OSQP_RHO, WARM_SOLVED, WarmStore, polish_qp, solve_qp, warm_start_qp, warm_store_qp
+        from .engine import (OSQP_RHO, WARM_SOLVED, WarmStore, polish_qp, soft_pair, solve_qp, warm_start_qp,
+                             warm_store_qp)
 
         bucket = self.buckets[item["p"]]
         asm, n = bucket["asm"], item["idx"].size
@@ -456,6 +470,9 @@ class WalkerFleet:
             bucket["gmap"] = asm.given_map(biped_given_rules(bucket["form"]))
             if self._polish:
                 qp["polish"] = torch.zeros(B, **i32)
+            if self._soft is not None:   # (one pair of rows for the bucket, at a fixed address)
+                bucket["soft"] = soft_pair(self._soft(asm) if callable(self._soft) else self._soft, asm.nc,
+                                           asm.device)
             if self._warm:
                 qp["warm"] = torch.zeros(B, **i32)
                 if self._warm_store is None:
@@ -474,7 +491,8 @@ class WalkerFleet:
             else:
                 rho.fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
             sol = solve_qp(entry["P"], entry["q"], entry["G"], entry["h"], rho=rho, stream=stream, warm=self._warm,
-                           out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")))
+                           out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")),
+                           soft=bucket.get("soft"))
             if self._polish:
                 polish_qp(entry["P"], entry["q"], entry["G"], entry["h"], sol, status=sol.status, stream=stream,
                           out=(qp["polish"][:n], sol.res))
