@@ -45,8 +45,9 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 /* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
  * mpcasm_ltv_rollout and mpcasm_ltv_advance, for the one that added mpcasm_qp_polish_wide and
  * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info, for the one that added mpcasm_ltv_lqr,
- * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment and for the one that added
- * mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft and their two info entries (the project's tests pin
+ * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment, for the one that added
+ * mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft and their two info entries and for the one that added
+ * mpcasm_qp_sens, mpcasm_qp_sens_wide and their two info entries (the project's tests pin
  * the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
@@ -661,6 +662,69 @@ int mpcasm_qp_polish_wide(int no, int nc, const double* d_P, const double* d_q, 
  * MPCASM_ERR_ARG for no < 1, nc < 0, batch < 0 or a null output. */
 int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
                                int32_t* workgroups);
+
+/* Per-instance outcome of mpcasm_qp_sens, written to d_verdict on the device. */
+enum {
+  MPCASM_SENS_DONE = 1,      /* u, w (and lres, gP, gG where asked for) were written                       */
+  MPCASM_SENS_SKIPPED = 0,   /* not a solved instance, or more active rows than unknowns: nothing written */
+  MPCASM_SENS_SINGULAR = -1  /* a pivot of the regularised KKT system is not positive: nothing written     */
+};
+
+/* The sensitivity of solved QPs -- how x* and y* move when q, h, P, G move -- for a batch of iterates of
+ * mpcasm_qp_solve, best polished ones: at a strictly complementary solution with active rows A the KKT
+ * conditions are  P x + q + G_A'y_A = 0,  G_A x = h_A,  so the forward and the adjoint derivative are both one
+ * solve with the polish's symmetric  K = [[P, G_A'], [G_A, 0]]  and a right-hand side [rx; ry] of the caller's.
+ * With [u; w_A] = K^-1 [rx; ry_A] and w = 0 off the active set:
+ *   adjoint (rx = dL/dx, ry = dL/dy)    dL/dq = -u,  dL/dh = w,  dL/dP = -1/2 (u x' + x u')  (P symmetric),
+ *                                       row i of dL/dG = -(y_i u' + w_i x') on active rows, 0 elsewhere
+ *   forward (rx = -(dq + dP x + dG_A'y_A), ry = dh - dG x)      dx = u,  dy = w
+ * Same layouts as mpcasm_qp_polish, every instance on its own, nothing read back, the call can be captured in a
+ * graph; P, G, h, x, y, z are only read.  Per instance b, in order:
+ *   skipped    d_status != NULL and d_status[b] != MPCASM_QP_SOLVED (the instance is not read: NON_CVX holds
+ *              NaN), or the guessed active set has na > no rows: d_verdict[b] = MPCASM_SENS_SKIPPED and no other
+ *              output is written
+ *   active set row i iff h_i - z_i < y_i, the polish's test
+ *   solve      r = [rx; ry on the active rows], dK = diag(delta I_no, -delta I_na);  t = (K + dK)^-1 r, then
+ *              refine_iters times  t += (K + dK)^-1 (r - K t), the residual from K as it is, with P and G as
+ *              given.  The polish's factorisations and defaults (delta = 1e-6, refine_iters = 3); a pivot that is
+ *              not positive: MPCASM_SENS_SINGULAR and no other output is written
+ *   results    d_u[b] = t[:no]; d_w[b] = t[no:] on the active rows and exactly 0 on every other row (all nc
+ *              entries are written); d_lres[b] = |r - K t|_inf after the last refinement -- at a weakly active row
+ *              or with dependent active rows K is singular, w depends on delta, and this residual is the sign to
+ *              read; d_verdict[b] = MPCASM_SENS_DONE
+ *   gradients  where d_gP / d_gG are not NULL they are written whole:  d_gP[b] = -1/2 (u x' + x u'),  row i of
+ *              d_gG[b] = -(y_i u' + w_i x') on active rows and exact zeros elsewhere; x, y the iterate's as passed
+ * d_rx, d_u [batch][no]; d_ry, d_w [batch][nc]; d_gP [batch][no][no]; d_gG [batch][nc][no]; d_verdict [batch] int32;
+ * d_lres [batch]; d_status (may be NULL: every instance is taken) as for mpcasm_qp_polish.  d_gP, d_gG, d_lres may
+ * be NULL.  No output may overlap an input.
+ * Size limit: mpcasm_qp_polish's, and its LDS (the same layout: rx, t and the iterate where the polish keeps q, its
+ * residuals and the polished point).  MPCASM_ERR_LIMIT beyond it, nothing launched.  MPCASM_ERR_ARG, before any
+ * device call: delta not finite or <= 0, refine_iters < 0, batch < 0, no < 1, nc < 0, a null d_P, d_x, d_rx, d_u,
+ * d_verdict (with nc > 0: d_G, d_h, d_y, d_z, d_ry, d_w).  batch == 0: MPCASM_OK. */
+int mpcasm_qp_sens(int no, int nc, const double* d_P, const double* d_G, const double* d_h, const double* d_x,
+                   const double* d_y, const double* d_z, const int32_t* d_status, const double* d_rx,
+                   const double* d_ry, double delta, int refine_iters, double* d_u, double* d_w, double* d_gP,
+                   double* d_gG, int32_t* d_verdict, double* d_lres, int batch, void* stream);
+/* Needs no device: the LDS bytes one instance of mpcasm_qp_sens takes, mpcasm_qp_polish_lds_bytes' figure and
+ * verdict. */
+int mpcasm_qp_sens_lds_bytes(int no, int nc, int64_t* out);
+
+/* The same sensitivity for QPs whose matrices do not fit on chip, the iterates of mpcasm_qp_solve_wide:
+ * mpcasm_qp_sens's operands, steps, verdicts and untouched outputs with mpcasm_qp_polish_wide's method, launch
+ * (min(batch, MPCASM_POLISH_WIDE_CAP) workgroups striding the batch), workspace (workgroups * (3 no^2, rounded up
+ * to even) doubles, d_work 16-byte aligned, nothing kept between calls), LDS and size limit.  u and w equal
+ * mpcasm_qp_sens's up to rounding, not bit for bit.  MPCASM_ERR_ARG, before any device call: mpcasm_qp_sens's
+ * cases, a null d_work, a d_work that is not 16-byte aligned, work_bytes smaller than mpcasm_qp_sens_wide_info
+ * reports for (no, nc, batch).  batch == 0: MPCASM_OK. */
+int mpcasm_qp_sens_wide(int no, int nc, const double* d_P, const double* d_G, const double* d_h, const double* d_x,
+                        const double* d_y, const double* d_z, const int32_t* d_status, const double* d_rx,
+                        const double* d_ry, double delta, int refine_iters, double* d_u, double* d_w, double* d_gP,
+                        double* d_gG, int32_t* d_verdict, double* d_lres, int batch, void* d_work, size_t work_bytes,
+                        void* stream);
+/* Needs no device: mpcasm_qp_polish_wide_info's three figures and verdict, for mpcasm_qp_sens_wide (the environment
+ * variable MPCASM_QP_POLISH_WIDE_GROUPS lowers the cap of both). */
+int mpcasm_qp_sens_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
+                             int32_t* workgroups);
 
 /* The loop's warm start  last tick's solution, moved one sample along, as this tick's start ----------------
  * A receding-horizon loop solves, every tick, nearly the QP of the tick before with the horizon moved on by one

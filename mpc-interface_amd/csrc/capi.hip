@@ -1023,6 +1023,58 @@ int mpcasm_qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, in
   return qp_polish_wide_info(no, nc, batch, lds_bytes, work_bytes, workgroups);
 }
 
+// what the two sensitivity entries decide alike: MPCASM_OK with *go set where there is something to launch
+static int qp_sens_checks(const QpSens& s, bool* go) {
+  *go = false;
+  const QpPolish settings{nullptr, s.delta, s.refine_iters, nullptr, nullptr};
+  if (!qp_sizes_ok(s.no, s.nc) || s.batch < 0 || !qp_polish_settings_ok(settings)) return MPCASM_ERR_ARG;
+  if (s.batch == 0) return MPCASM_OK;
+  if (!s.P || !s.x || !s.rx || !s.u || !s.verdict) return MPCASM_ERR_ARG;
+  if (s.nc > 0 && (!s.G || !s.h || !s.y || !s.z || !s.ry || !s.w)) return MPCASM_ERR_ARG;
+  *go = true;
+  return MPCASM_OK;
+}
+
+int mpcasm_qp_sens(int no, int nc, const double* d_P, const double* d_G, const double* d_h, const double* d_x,
+                   const double* d_y, const double* d_z, const int32_t* d_status, const double* d_rx,
+                   const double* d_ry, double delta, int refine_iters, double* d_u, double* d_w, double* d_gP,
+                   double* d_gG, int32_t* d_verdict, double* d_lres, int batch, void* stream) {
+  const QpSens s{no,   nc,    batch,        d_P, d_G, d_h,  d_x,  d_y,       d_z,   d_status,
+                 d_rx, d_ry,  delta,        refine_iters,   d_u,  d_w,       d_gP,  d_gG,
+                 d_verdict,   d_lres};
+  bool go;
+  const int rc = qp_sens_checks(s, &go);
+  if (!go) return rc;
+  hipError_t err;   // (past the LDS a workgroup may have: the launch's MPCASM_ERR_LIMIT)
+  return launched(launch_qp_sens(s, static_cast<hipStream_t>(stream), &err), err);
+}
+
+int mpcasm_qp_sens_lds_bytes(int no, int nc, int64_t* out) { return mpcasm_qp_polish_lds_bytes(no, nc, out); }
+
+int mpcasm_qp_sens_wide(int no, int nc, const double* d_P, const double* d_G, const double* d_h, const double* d_x,
+                        const double* d_y, const double* d_z, const int32_t* d_status, const double* d_rx,
+                        const double* d_ry, double delta, int refine_iters, double* d_u, double* d_w, double* d_gP,
+                        double* d_gG, int32_t* d_verdict, double* d_lres, int batch, void* d_work, size_t work_bytes,
+                        void* stream) {
+  const QpSens s{no,   nc,    batch,        d_P, d_G, d_h,  d_x,  d_y,       d_z,   d_status,
+                 d_rx, d_ry,  delta,        refine_iters,   d_u,  d_w,       d_gP,  d_gG,
+                 d_verdict,   d_lres};
+  bool go;
+  const int rc = qp_sens_checks(s, &go);
+  if (!go) return rc;
+  int64_t need = 0;
+  const int limit = qp_polish_wide_info(no, nc, batch, nullptr, &need, nullptr);
+  if (limit != MPCASM_OK) return limit;
+  if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0 || work_bytes < (size_t)need) return MPCASM_ERR_ARG;
+  hipError_t err;
+  return launched(launch_qp_sens_wide(s, static_cast<double*>(d_work), static_cast<hipStream_t>(stream), &err), err);
+}
+
+int mpcasm_qp_sens_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
+                             int32_t* workgroups) {
+  return mpcasm_qp_polish_wide_info(no, nc, batch, lds_bytes, work_bytes, workgroups);
+}
+
 int mpcasm_qp_warm_store(int no, int nc, const double* d_x, const double* d_y, const double* d_rho,
                          const int32_t* d_status, int tag, double* d_store_x, double* d_store_y, double* d_store_rho,
                          int32_t* d_store_meta, int64_t store_rows, int store_no, int store_nc, const int32_t* d_index,

@@ -210,6 +210,19 @@ struct QpPolish {
   int32_t* polish;
   double* res;
 };
+// the sensitivity of a batch of solved QPs (mpcasm_qp_sens, mpcasm_qp_sens_wide): operands, the iterate, the
+// right-hand side, the polish's settings and the outputs (gP, gG, lres: null for "not wanted")
+struct QpSens {
+  int no, nc, batch;
+  const double *P, *G, *h, *x, *y, *z;
+  const int32_t* status;
+  const double *rx, *ry;
+  double delta;
+  int refine_iters;
+  double *u, *w, *gP, *gG;
+  int32_t* verdict;
+  double* lres;
+};
 
 // the launch of a kernel with dynamic LDS: more than a workgroup may have -> MPCASM_ERR_LIMIT; more than 64 KiB ->
 // allow_whole_lds first; *err is the runtime's word where MPCASM_ERR_HIP comes back
@@ -246,6 +259,10 @@ int launch_qp_polish(const QpBatch& b, const QpPolish& p, hipStream_t stream, hi
 constexpr int POLISH_WIDE_CAP = MPCASM_POLISH_WIDE_CAP;
 int qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes, int32_t* workgroups);
 int launch_qp_polish_wide(const QpBatch& b, const QpPolish& p, double* work, hipStream_t stream, hipError_t* err);
+// sens_core.h in polish.hip and polish_wide.hip: one more solve with the polish's KKT system and the caller's
+// right-hand side, on the polish's LDS layout, workspace and launch geometry (their sizes are the polish's)
+int launch_qp_sens(const QpSens& s, hipStream_t stream, hipError_t* err);
+int launch_qp_sens_wide(const QpSens& s, double* work, hipStream_t stream, hipError_t* err);
 // warm.hip: a closed loop's warm store -- the scatter after a solve, the shifted start before the next
 int launch_qp_warm_store(int no, int nc, const double* x, const double* y, const double* rho, const int32_t* status,
                          int tag, double* sx, double* sy, double* srho, int32_t* smeta, int64_t store_rows,

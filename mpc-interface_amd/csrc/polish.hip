@@ -26,6 +26,7 @@
 
 #include "kernels.h"
 #include "polish_core.h"
+#include "sens_core.h"
 
 namespace mpcasm {
 
@@ -169,6 +170,18 @@ __global__ __launch_bounds__(QP_BLOCK) void polish_kernel(
   if (tid == 0) polish[inst] = verdict;
 }
 
+// mpcasm_qp_sens: sens_core.h's steps on the same back-end, the same LDS layout and the same geometry
+__global__ __launch_bounds__(QP_BLOCK) void sens_kernel(QpSens s) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const long inst = blockIdx.x;
+  if (inst >= s.batch) return;
+  LdsPolish be(sm, s.no, s.nc, s.delta, tid, lane, wave);
+  const int verdict = sens_instance(be, inst, s, tid, lane, wave);
+  if (tid == 0) s.verdict[inst] = verdict;
+}
+
 }  // namespace
 
 size_t polish_lds_bytes(int no, int nc) { return (size_t)polish_lds(no, nc).total * sizeof(double); }
@@ -177,6 +190,10 @@ int launch_qp_polish(const QpBatch& b, const QpPolish& p, hipStream_t stream, hi
   return launch_with_lds(polish_kernel, (unsigned)b.batch, QP_BLOCK, polish_lds_bytes(b.no, b.nc), stream, err,
                          b.no, b.nc, b.P, b.q, b.G, b.h, b.x, b.y, b.z, p.status, p.delta, p.refine_iters, p.polish,
                          p.res, b.batch);
+}
+
+int launch_qp_sens(const QpSens& s, hipStream_t stream, hipError_t* err) {
+  return launch_with_lds(sens_kernel, (unsigned)s.batch, QP_BLOCK, polish_lds_bytes(s.no, s.nc), stream, err, s);
 }
 
 }  // namespace mpcasm

@@ -26,6 +26,7 @@
 
 #include "kernels.h"
 #include "polish_core.h"
+#include "sens_core.h"
 
 namespace mpcasm {
 
@@ -201,6 +202,19 @@ __global__ __launch_bounds__(QP_BLOCK) void polish_wide_kernel(
   }
 }
 
+// mpcasm_qp_sens_wide: sens_core.h's steps on the same back-end, the same slices and the same geometry
+__global__ __launch_bounds__(QP_BLOCK) void sens_wide_kernel(QpSens s, double* work, long slice) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  SlicePolish be(sm, work + (size_t)blockIdx.x * slice, s.no, s.nc, s.delta, tid, lane, wave);
+  for (long inst = blockIdx.x; inst < s.batch; inst += gridDim.x) {
+    const int verdict = sens_instance(be, inst, s, tid, lane, wave);
+    if (tid == 0) s.verdict[inst] = verdict;
+    __syncthreads();   // (the next instance writes the LDS and the slice this one may still be reading)
+  }
+}
+
 }  // namespace
 
 int qp_polish_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes, int32_t* workgroups) {
@@ -224,6 +238,15 @@ int launch_qp_polish_wide(const QpBatch& b, const QpPolish& p, double* work, hip
   return launch_with_lds(polish_wide_kernel, (unsigned)grid, QP_BLOCK, (size_t)lds, stream, err, b.no, b.nc, b.P, b.q,
                          b.G, b.h, b.x, b.y, b.z, p.status, p.delta, p.refine_iters, p.polish, p.res, b.batch, work,
                          polish_wide_slice(b.no));
+}
+
+int launch_qp_sens_wide(const QpSens& s, double* work, hipStream_t stream, hipError_t* err) {
+  int64_t lds = 0;
+  int32_t grid = 0;
+  const int rc = qp_polish_wide_info(s.no, s.nc, s.batch, &lds, nullptr, &grid);
+  if (rc != MPCASM_OK) return rc;
+  return launch_with_lds(sens_wide_kernel, (unsigned)grid, QP_BLOCK, (size_t)lds, stream, err, s, work,
+                         polish_wide_slice(s.no));
 }
 
 }  // namespace mpcasm

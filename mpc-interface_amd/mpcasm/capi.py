@@ -43,6 +43,9 @@ QP_STATUS = {
 POLISH_DONE, POLISH_SKIPPED, POLISH_REJECTED = 1, 0, -1
 POLISH_WIDE_CAP = 512          # MPCASM_POLISH_WIDE_CAP: the most workgroups of one mpcasm_qp_polish_wide launch
 POLISH_STATUS = {1: "MPCASM_POLISH_DONE", 0: "MPCASM_POLISH_SKIPPED", -1: "MPCASM_POLISH_REJECTED"}
+# per-instance outcomes of mpcasm_qp_sens
+SENS_DONE, SENS_SKIPPED, SENS_SINGULAR = 1, 0, -1
+SENS_STATUS = {1: "MPCASM_SENS_DONE", 0: "MPCASM_SENS_SKIPPED", -1: "MPCASM_SENS_SINGULAR"}
 ROLL_GIVEN, ROLL_OPTIM, ROLL_STATE, ROLL_REC_WORDS = 0, 1, 2, 8   # records of mpcasm_ltv_rollout_compile
 ERR_ARG = -1
 # mpcasm_fill_route: out[0] and the flags of out[2]
@@ -147,6 +150,15 @@ SIGNATURES = {
     "mpcasm_qp_polish_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                                   ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_qp_sens": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 9 + [ctypes.c_double, ctypes.c_int] +
+                       [_void_p] * 6 + [ctypes.c_int, _void_p]),
+    "mpcasm_qp_sens_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_qp_sens_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 9 +
+                            [ctypes.c_double, ctypes.c_int] + [_void_p] * 6 +
+                            [ctypes.c_int, _void_p, ctypes.c_size_t, _void_p]),
+    "mpcasm_qp_sens_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                                ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_qp_warm_store": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 4 + [ctypes.c_int] +
                              [_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int,
                                               _void_p]),

@@ -1,0 +1,94 @@
+"""Differentiable QP solves: ``torch.autograd`` through :func:`mpcasm.engine.solve_qp`.
+
+The forward pass is the solve with polishing, on the device; the backward pass is ONE call of
+:func:`mpcasm.engine.qp_sensitivity` (``mpcasm_qp_sens``): at a strictly complementary solution with active rows ``A``
+the KKT conditions are ``P x + q + G_A'y_A = 0``, ``G_A x = h_A``, and with ``[u; w_A] = K^-1 [dL/dx; dL/dy_A]`` for the
+symmetric ``K = [[P, G_A'], [G_A, 0]]``
+
+    dL/dq = -u      dL/dh = w      dL/dP = -1/2 (u x' + x u')      row i of dL/dG = -(y_i u' + w_i x'), active rows only
+
+("The derivative of a solve").  ``dL/dP`` is the gradient with respect to a symmetric ``P``, which the
+solvers require: a caller that builds ``P`` from parameters gets their gradient by the chain rule through that
+construction.  Gradients with respect to ``given`` and ``params`` through the assembly are not here.
+"""
+from . import engine
+from .engine import require_device
+
+_FUNCTION = None
+
+
+class QpDiffSolution:
+    """What :func:`solve_qp_diff` returns: ``x (B, no)`` and ``y (B, nc)``, differentiable with respect to the
+    ``P, q, G, h`` that require grad; ``sol``, the :class:`mpcasm.engine.PolishedQpSolution` of the forward pass
+    (plain tensors; ``sol.x`` and ``sol.y`` share ``x``'s and ``y``'s memory); and, None until ``backward`` has run,
+    ``verdict`` ``(B,)`` int32 (``engine.SENS_*``) and ``lres`` ``(B,)`` of its sensitivity solve.  An instance whose
+    verdict is not ``SENS_DONE`` (not solved, more active rows than unknowns, a KKT matrix that does not factor) got
+    zero gradients."""
+    __slots__ = ("x", "y", "_outcome", "__weakref__")
+
+    def __init__(self, x, y, outcome):
+        self.x, self.y, self._outcome = x, y, outcome
+
+    sol = property(lambda self: self._outcome.sol)
+    verdict = property(lambda self: self._outcome.verdict)
+    lres = property(lambda self: self._outcome.lres)
+
+
+class _Outcome:
+    """What the two passes leave for the caller beside ``x`` and ``y``.  The autograd node holds THIS, never the
+    :class:`QpDiffSolution`: that one holds the node's own outputs, and a node that held it would close a cycle
+    through the autograd graph which Python's collector cannot see -- every call would keep its device tensors for
+    good.  Nothing here refers to ``x`` or ``y`` (``sol.x`` is the plain tensor they are views of)."""
+    __slots__ = ("sol", "verdict", "lres")
+
+    def __init__(self):
+        self.sol = self.verdict = self.lres = None
+
+
+def _function(torch):
+    global _FUNCTION
+    if _FUNCTION is not None:
+        return _FUNCTION
+
+    class SolveQpDiff(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, P, q, G, h, outcome, wide, solve_kw):
+            P, q, G, h = (t.detach().contiguous() for t in (P, q, G, h))
+            solve = engine.solve_qp_wide if wide else engine.solve_qp
+            sol = solve(P, q, G, h, polish=True, **solve_kw)
+            outcome.sol = sol
+            ctx.outcome, ctx.wide, ctx.stream = outcome, wide, solve_kw.get("stream")
+            ctx.save_for_backward(P, G, h, sol.x, sol.y, sol.z, sol.status)
+            return sol.x.view_as(sol.x), sol.y.view_as(sol.y)
+
+        @staticmethod
+        def backward(ctx, gx, gy):
+            P, G, h, x, y, z, status = ctx.saved_tensors
+            need_P, need_q, need_G, need_h = ctx.needs_input_grad[:4]
+            sens = engine.qp_sensitivity_wide if ctx.wide else engine.qp_sensitivity
+            s = sens(P, G, h, (x, y, z), gx.contiguous(), gy.contiguous(), status=status, want_P=need_P, want_G=need_G,
+                     stream=ctx.stream)
+            ctx.outcome.verdict, ctx.outcome.lres = s.verdict, s.lres
+            return (s.gP if need_P else None, -s.u if need_q else None, s.gG if need_G else None,
+                    s.w if need_h else None, None, None, None)
+
+    _FUNCTION = SolveQpDiff
+    return _FUNCTION
+
+
+def solve_qp_diff(P, q, G, h, wide=False, **solve_kw):
+    """``solve_qp(P, q, G, h, polish=True, **solve_kw)`` (``wide``: ``solve_qp_wide``) as a differentiable function
+    of ``P, q, G, h``: a :class:`QpDiffSolution`.  ``backward`` through its ``x`` and ``y`` makes one
+    :func:`mpcasm.engine.qp_sensitivity` (``wide``: ``qp_sensitivity_wide``) call on the solved instances and asks for
+    the dense ``P.grad`` / ``G.grad`` only where ``P`` / ``G`` require grad; the gradients are the active-set model's
+    at the polished point, zero for an instance that is not ``SENS_DONE``.  ``soft=`` is refused (``ValueError``):
+    the active-set model is the hard problem's, as for ``solve_qp(polish=, soft=)``."""
+    if solve_kw.get("soft") is not None:
+        raise ValueError("solve_qp_diff with soft=: the active-set model of the derivative is the hard problem's")
+    if "polish" in solve_kw:
+        raise ValueError("solve_qp_diff always polishes: the derivative is taken at the polished point")
+    solve_kw.pop("soft", None)
+    torch = require_device()
+    outcome = _Outcome()
+    x, y = _function(torch).apply(P, q, G, h, outcome, bool(wide), solve_kw)
+    return QpDiffSolution(x, y, outcome)

@@ -12,6 +12,7 @@ torch is used for memory, streams and ``data_ptr()`` only; nothing here
 computes on the host and nothing falls back to the CPU.
 """
 import collections
+import contextlib
 import ctypes
 
 import numpy as np
@@ -324,6 +325,164 @@ def qp_polish_wide_info(no, nc, batch):
                                                 ctypes.byref(groups))
     capi.check(rc, "mpcasm_qp_polish_wide_info")
     return int(lds.value), int(work.value), int(groups.value)
+
+
+# ---- the derivative of a solve: one more solve with the polish's KKT system --------------------------------------
+SENS_DONE, SENS_SKIPPED, SENS_SINGULAR = capi.SENS_DONE, capi.SENS_SKIPPED, capi.SENS_SINGULAR
+
+QpSensitivity = collections.namedtuple("QpSensitivity", "u w gP gG verdict lres")
+QpVjp = collections.namedtuple("QpVjp", "gq gh gP gG verdict")
+QpJvp = collections.namedtuple("QpJvp", "dx dy verdict")
+
+
+def qp_sensitivity(P, G, h, sol_or_xyz, rx, ry, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE,
+                   want_P=False, want_G=False, out=None, stream=None):
+    """The sensitivity solve of a batch of solved QPs (``mpcasm_qp_sens``): per instance, the active set guessed
+    from the iterate by the polish's test (row ``i`` iff ``h_i - z_i < y_i``), ``K = [[P, G_A'], [G_A, 0]]``, and
+    ``[u; w_A] = K^-1 [rx; ry_A]`` by the polish's regularised solve with ``refine_iters`` steps of refinement;
+    ``w`` is 0 off the active set.  ``K`` is symmetric, so this one solve is the adjoint (:func:`qp_vjp`) and the
+    forward derivative (:func:`qp_jvp`) alike.
+    ``sol_or_xyz``: a :class:`QpSolution` or ``(x, y, z)``, only read -- best a polished one: the derivative is the
+    active-set model's at that point.  ``rx (B, no)``, ``ry (B, nc)``: contiguous float64 device tensors.
+    ``status``: ``(B,)`` int32, only ``QP_SOLVED`` instances are taken (None: every instance).
+    Returns a :class:`QpSensitivity` ``(u, w, gP, gG, verdict, lres)``: ``u (B, no)``, ``w (B, nc)``; with
+    ``want_P`` / ``want_G`` the dense ``gP = -1/2 (u x' + x u')`` ``(B, no, no)`` and ``gG`` ``(B, nc, no)``, row ``i``
+    ``-(y_i u' + w_i x')`` on active rows and 0 elsewhere (else None); ``verdict (B,)`` int32 (``SENS_DONE`` /
+    ``SENS_SKIPPED`` / ``SENS_SINGULAR``); ``lres (B,)`` the residual ``|r - K t|_inf`` of the solve: large where the
+    active rows are dependent or a row is weakly active, and ``w`` then depends on ``delta``.  An instance that is
+    not ``SENS_DONE`` is not written; tensors allocated here start at zero, so it reads as a zero gradient.
+    ``out``: the caller's ``(u, w, gP, gG, verdict, lres)`` to write instead (fixed addresses for a replayed graph;
+    a None among them is allocated here, ``gP`` / ``gG`` only when wanted)."""
+    return _qp_sens("mpcasm_qp_sens", P, G, h, sol_or_xyz, rx, ry, status, delta, refine_iters, want_P, want_G, out,
+                    stream)
+
+
+def qp_sensitivity_wide(P, G, h, sol_or_xyz, rx, ry, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE,
+                        want_P=False, want_G=False, out=None, stream=None, work=None):
+    """:func:`qp_sensitivity` for QPs whose matrices do not fit on chip (``mpcasm_qp_sens_wide``), the iterates of
+    :func:`solve_qp_wide`: the same arguments and results with :func:`polish_qp_wide`'s method and ``work``, at least
+    ``qp_sens_wide_info(no, nc, B)[1]`` bytes (allocated here when None)."""
+    return _qp_sens("mpcasm_qp_sens_wide", P, G, h, sol_or_xyz, rx, ry, status, delta, refine_iters, want_P, want_G,
+                    out, stream, wide=True, work=work)
+
+
+def _qp_sens(entry, P, G, h, sol_or_xyz, rx, ry, status, delta, refine_iters, want_P, want_G, out, stream, wide=False,
+             work=None):
+    """:func:`qp_sensitivity` and :func:`qp_sensitivity_wide` through the C entry ``entry``."""
+    torch = require_device()
+    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
+        x, y, z = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z
+    else:
+        x, y, z = sol_or_xyz
+    for t in (P, G, h):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+            raise ValueError("P, G, h: contiguous float64 device tensors")
+    if P.dim() != 3 or P.shape[1] != P.shape[2] or G.dim() != 3 or G.shape[0] != P.shape[0] or \
+            G.shape[2] != P.shape[1] or h.shape != G.shape[:2]:
+        raise ValueError("shapes: P (B, no, no), G (B, nc, no), h (B, nc)")
+    batch, no, nc = P.shape[0], P.shape[1], G.shape[1]
+    f64, i32 = dict(dtype=torch.float64, device=P.device), dict(dtype=torch.int32, device=P.device)
+    u = w = gP = gG = verdict = lres = None
+    if out is not None:
+        u, w, gP, gG, verdict, lres = out
+    u = torch.zeros((batch, no), **f64) if u is None else u
+    w = torch.zeros((batch, nc), **f64) if w is None else w
+    if gP is None and want_P:
+        gP = torch.zeros((batch, no, no), **f64)
+    if gG is None and want_G:
+        gG = torch.zeros((batch, nc, no), **f64)
+    verdict = torch.zeros((batch,), **i32) if verdict is None else verdict
+    lres = torch.zeros((batch,), **f64) if lres is None else lres
+    checked = [(x, torch.float64, (batch, no)), (y, torch.float64, (batch, nc)), (z, torch.float64, (batch, nc)),
+               (rx, torch.float64, (batch, no)), (ry, torch.float64, (batch, nc)), (u, torch.float64, (batch, no)),
+               (w, torch.float64, (batch, nc)), (verdict, torch.int32, (batch,)), (lres, torch.float64, (batch,))]
+    checked += [(status, torch.int32, (batch,))] if status is not None else []
+    checked += [(gP, torch.float64, (batch, no, no))] if gP is not None else []
+    checked += [(gG, torch.float64, (batch, nc, no))] if gG is not None else []
+    for t, dtype, shape in checked:
+        if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
+                and tuple(t.shape) == shape):
+            raise ValueError("x, rx, u (B, no), y, z, ry, w (B, nc), gP (B, no, no), gG (B, nc, no), lres (B,) float64 "
+                             "and status, verdict (B,) int32: contiguous, on P's device")
+    extra = ()
+    if wide:
+        need = qp_sens_wide_info(no, nc, batch)[1]
+        if work is None:
+            work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=P.device)
+        if not (isinstance(work, torch.Tensor) and work.device == P.device and work.is_contiguous()
+                and work.dtype in (torch.uint8, torch.float64)):
+            raise ValueError("work: a contiguous uint8 or float64 tensor on P's device")
+        extra = (work.data_ptr(), work.numel() * work.element_size())
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(P.device):
+        rc = getattr(capi.load(), entry)(no, nc, P.data_ptr(), G.data_ptr(), h.data_ptr(), x.data_ptr(), y.data_ptr(),
+                                         z.data_ptr(), ptr(status), rx.data_ptr(), ry.data_ptr(), float(delta),
+                                         int(refine_iters), u.data_ptr(), w.data_ptr(), ptr(gP), ptr(gG),
+                                         verdict.data_ptr(), lres.data_ptr(), batch, *extra,
+                                         _stream_handle(torch, stream))
+    capi.check(rc, entry)
+    return QpSensitivity(u, w, gP, gG, verdict, lres)
+
+
+def qp_sens_lds_bytes(no, nc):
+    """LDS bytes one instance of :func:`qp_sensitivity` takes -- :func:`qp_polish_lds_bytes`' figure and limit
+    (``mpcasm_qp_sens_lds_bytes``).  Needs no device."""
+    out = ctypes.c_int64()
+    rc = capi.load().mpcasm_qp_sens_lds_bytes(int(no), int(nc), ctypes.byref(out))
+    capi.check(rc, "mpcasm_qp_sens_lds_bytes")
+    return int(out.value)
+
+
+def qp_sens_wide_info(no, nc, batch):
+    """``(lds_bytes, work_bytes, workgroups)`` of :func:`qp_sensitivity_wide` on ``batch`` instances --
+    :func:`qp_polish_wide_info`'s figures and limit (``mpcasm_qp_sens_wide_info``).  Needs no device."""
+    lds, work, groups = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    rc = capi.load().mpcasm_qp_sens_wide_info(int(no), int(nc), int(batch), ctypes.byref(lds), ctypes.byref(work),
+                                              ctypes.byref(groups))
+    capi.check(rc, "mpcasm_qp_sens_wide_info")
+    return int(lds.value), int(work.value), int(groups.value)
+
+
+def qp_vjp(P, G, h, sol_or_xyz, gx, gy, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE, want_P=False,
+           want_G=False, wide=False, stream=None, work=None):
+    """The adjoint of a solve: for a loss with ``dL/dx = gx (B, no)`` and ``dL/dy = gy (B, nc)`` at the solution
+    ``sol_or_xyz``, a :class:`QpVjp` ``(gq, gh, gP, gG, verdict)`` = ``(-u, w, -1/2 (u x' + x u'), -(y u' + w x') on
+    the active rows, SENS_*)`` of one :func:`qp_sensitivity` call (``wide``: :func:`qp_sensitivity_wide`); ``gP`` is
+    the gradient with respect to a symmetric ``P``.  An instance that is not ``SENS_DONE`` has zero gradients."""
+    call = qp_sensitivity_wide if wide else qp_sensitivity
+    kw = dict(work=work) if wide else {}
+    s = call(P, G, h, sol_or_xyz, gx, gy, status=status, delta=delta, refine_iters=refine_iters, want_P=want_P,
+             want_G=want_G, stream=stream, **kw)
+    return QpVjp(-s.u, s.w, s.gP, s.gG, s.verdict)
+
+
+def qp_jvp(P, G, h, sol_or_xyz, dq, dh, dP=None, dG=None, status=None, delta=OSQP_DELTA,
+           refine_iters=OSQP_POLISH_REFINE, wide=False, stream=None, work=None):
+    """The forward derivative of a solve: how ``x*, y*`` move along ``(dq (B, no), dh (B, nc), dP (B, no, no)
+    symmetric, dG (B, nc, no))`` (None: no change), a :class:`QpJvp` ``(dx, dy, verdict)``, so that
+    ``x*(q + dq, ...) ~ x* + dx`` while the active set stays.  The right-hand side ``rx = -(dq + dP x + dG_A'y_A)``,
+    ``ry = dh - dG x`` is formed with torch ops (the active mask is ``(h - z) < y``) on the stream of the solve --
+    ``stream`` where one is passed, else torch's current one -- and the solve is one :func:`qp_sensitivity` call (``wide``: :func:`qp_sensitivity_wide`)."""
+    torch = require_device()
+    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
+        x, y, z = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z
+    else:
+        x, y, z = sol_or_xyz
+    # (the torch ops run on the stream the solve is launched on: `stream` where one is passed)
+    with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+        rx, ry = -dq, dh.clone()
+        if dP is not None:
+            rx = rx - torch.bmm(dP, x.unsqueeze(2)).squeeze(2)
+        if dG is not None:
+            ya = torch.where((h - z) < y, y, torch.zeros_like(y))
+            rx = rx - torch.bmm(dG.transpose(1, 2), ya.unsqueeze(2)).squeeze(2)
+            ry = ry - torch.bmm(dG, x.unsqueeze(2)).squeeze(2)
+        rx, ry = rx.contiguous(), ry.contiguous()
+    call = qp_sensitivity_wide if wide else qp_sensitivity
+    kw = dict(work=work) if wide else {}
+    s = call(P, G, h, (x, y, z), rx, ry, status=status, delta=delta,
+             refine_iters=refine_iters, stream=stream, **kw)
+    return QpJvp(s.u, s.w, s.verdict)
 
 
 def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
