@@ -221,6 +221,8 @@ class LtvLoop:
         asm, qp = self.asm, self._qp
         asm.bind_ltv_window(self.name, self._win[0], self._win[1], self.t)
         P, q, G, h = asm.assemble(self.given)
+        if G is None:                      # (a plan without limits: the solver takes G and h of no rows)
+            G, h = P.new_empty((self.batch, 0, asm.no)), P.new_empty((self.batch, 0))
         if self.warm:                      # (the tag is the tick + 1: a record is one tick old or not warm)
             warm_start_qp(self._store, G, h, self._col_src, self._row_src, self.t, warm_mask=WARM_SOLVED,
                           rho_cold=OSQP_RHO, out=(qp["x"], qp["y"], qp["z"], qp["rho"], self._warm_flags))
