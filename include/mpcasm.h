@@ -47,7 +47,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
  * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info, for the one that added mpcasm_ltv_lqr,
  * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment, for the one that added
  * mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft and their two info entries and for the one that added
- * mpcasm_qp_sens, mpcasm_qp_sens_wide and their two info entries (the project's tests pin
+ * mpcasm_qp_sens, mpcasm_qp_sens_wide and their two info entries and for the one that added mpcasm_assemble_jvp,
+ * mpcasm_assemble_vjp and mpcasm_assemble_adjoint_info (the project's tests pin
  * the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
@@ -725,6 +726,43 @@ int mpcasm_qp_sens_wide(int no, int nc, const double* d_P, const double* d_G, co
  * variable MPCASM_QP_POLISH_WIDE_GROUPS lowers the cap of both). */
 int mpcasm_qp_sens_wide_info(int no, int nc, int batch, int64_t* lds_bytes, int64_t* work_bytes,
                              int32_t* workgroups);
+
+/* The derivative of the assembly with respect to `given`, matrix-free -------------------------------------------
+ * P and G of mpcasm_assemble do not depend on `given`; q and h are affine in it.  With cMg, cMo the rows of a
+ * definition after schedule and L over the columns of `given` and of the unknowns:
+ *   generate_qp_cost        body.py:266-302   q = sum over the cost terms  s w cMo_a' (cMg_b given - aim)
+ *   generate_qp_constraint  body.py:236-264   h = extreme + arrow . center - sum over the axes arrow_i (cMg_i given)
+ * so  dq = J_q d,  J_q = sum s w cMo_a' cMg_b  (s = 1/2 on the two terms of a crossed cost; a cost on a free
+ * variable itself contributes nothing), and -- the sign convention --  dh = -cMg d:  J_h = -sum_i diag(arrow_i)
+ * cMg_i.  These entries apply J = [J_q ; J_h] (mpcasm_assemble_jvp: the tangential predictor's dq, dh for a change
+ * d of `given`) and J' (mpcasm_assemble_vjp: dL/dgiven from dL/dq, dL/dh) without a preview matrix or a Jacobian
+ * in memory: one workgroup-resident pass per instance over the plan's own tables (csrc/adjoint.hip), deterministic
+ * -- no floating-point atomics; an instance's result does not depend on the batch or on its place in it.
+ * plan, h_src, h_src_stride, d_params [batch][n_params], d_work as for mpcasm_preview_direct / mpcasm_assemble (a
+ * plan compiled with lti=[...] takes the groups' (A, B) and needs d_work for the horizon tables it generates first).
+ *   mpcasm_assemble_jvp   d_dgiven [batch][ng] -> d_dq [batch][no], d_dh [batch][nc]; a NULL output is skipped
+ *   mpcasm_assemble_vjp   d_gq [batch][no], d_gh [batch][nc] -> d_ggiven [batch][ng] = J_q' gq + J_h' gh; a NULL
+ *                         cotangent is zero: d_ggiven is then the other half's alone
+ * MPCASM_ERR_ARG: both halves NULL, a null d_dgiven / d_ggiven, sources, d_params or d_work where the plan needs
+ * them, another device than the plan's.  MPCASM_ERR_LIMIT: a plan compiled with ltv=[...] (no S, U: its adjoint is
+ * the sweep's backward recursion), or one instance beyond the LDS of a CU.  ng == 0 or batch == 0: MPCASM_OK,
+ * nothing written.  The parameters are not differentiated.  The first of these calls on a plan derives the
+ * transposed index from the plan's tables and uploads it (a device allocation and a blocking copy, under a mutex in
+ * the handle; freed by mpcasm_plan_destroy): make it before capturing a graph.  Later calls only launch. */
+int mpcasm_assemble_jvp(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                        const double* d_params, const double* d_dgiven, double* d_dq, double* d_dh, void* d_work,
+                        int batch, void* stream);
+int mpcasm_assemble_vjp(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                        const double* d_params, const double* d_gq, const double* d_gh, double* d_ggiven,
+                        void* d_work, int batch, void* stream);
+/* Needs no device: what the two entries above launch for these tables -- validated as mpcasm_plan_create does --
+ * when the sources have the strides h_src_stride (may be NULL when the plan has no source).  out[0]: dynamic LDS
+ * bytes of a workgroup; out[1]: 1 when that is more than 64 KB (the whole-LDS attribute is set before the launch);
+ * out[2]: words of the transposed index derived from the tables and kept with the plan handle; out[3]: workgroups
+ * resident per CU (the launch's grid is min(batch, CUs * out[3])).  MPCASM_ERR_LIMIT exactly where the launches
+ * return it (out is zeroed): both take the decision from the same function. */
+int mpcasm_assemble_adjoint_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                                 const int64_t* h_src_stride, int32_t out[4]);
 
 /* The loop's warm start  last tick's solution, moved one sample along, as this tick's start ----------------
  * A receding-horizon loop solves, every tick, nearly the QP of the tick before with the horizon moved on by one

@@ -36,6 +36,13 @@ struct mpcasm_plan {
   // per CU (-1: the process-wide value of mpcasm_set_option)
   int opt_path = -1, opt_jit = -1, opt_per_cu = -1, opt_grid = -1;
   mutable int last_kernel = 0;  // mpcasm_plan_last_kernel: what the latest mpcasm_assemble launched
+  // the transposed index of mpcasm_assemble_jvp / _vjp (adjoint.hip): derived from h_itab and uploaded by the
+  // first call, under the mutex; adj_rc: what that attempt returned (1: not tried yet)
+  mutable std::mutex adj_mutex;
+  mutable int adj_rc = 1;
+  mutable int adj_hip = 0;
+  mutable AdjointIndex adj;
+  mutable int32_t* d_adj = nullptr;
 };
 
 namespace {
@@ -334,6 +341,7 @@ int mpcasm_plan_prepare(const mpcasm_plan* plan, int batch) {
 int mpcasm_plan_destroy(mpcasm_plan* plan) {
   if (!plan) return MPCASM_OK;
   jit_forget(plan->d_itab);
+  if (plan->d_adj) (void)hipFree(plan->d_adj);
   hipError_t e1 = hipFree(plan->d_itab);
   hipError_t e2 = hipFree(plan->d_dtab);
   delete plan;
@@ -491,6 +499,109 @@ int mpcasm_preview_direct(const mpcasm_plan* plan, const double* const* h_src,
   rc = launch_preview_direct(d, eff, d_given, d_optim, d_out, batch, plan->num_cus,
                              static_cast<hipStream_t>(stream), &err, plan->h_itab.data());
   return launched(rc, err);
+}
+
+namespace {
+// the plan's transposed index on its device: built and uploaded once, by whichever call comes first
+int plan_adjoint_index(const mpcasm_plan* plan, const AdjointIndex** out) {
+  std::lock_guard<std::mutex> lock(plan->adj_mutex);
+  if (plan->adj_rc == 1) {
+    plan->adj_rc = adjoint_build_index(plan->dev, plan->h_itab.data(), &plan->adj);
+    if (plan->adj_rc == MPCASM_OK) {
+      const size_t bytes = std::max<size_t>(plan->adj.words.size(), 1) * sizeof(int32_t);
+      hipError_t e = hipMalloc(&plan->d_adj, bytes);
+      if (e == hipSuccess && !plan->adj.words.empty())
+        e = hipMemcpy(plan->d_adj, plan->adj.words.data(), plan->adj.words.size() * sizeof(int32_t),
+                      hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        if (plan->d_adj) (void)hipFree(plan->d_adj);
+        plan->d_adj = nullptr;
+        plan->adj_rc = MPCASM_ERR_HIP;
+        plan->adj_hip = (int)e;
+      }
+      plan->adj.view.idx = plan->d_adj;
+    }
+  }
+  if (plan->adj_rc == MPCASM_ERR_HIP) g_last_hip = plan->adj_hip;
+  *out = &plan->adj;
+  return plan->adj_rc;
+}
+
+// JVP: in_x = d, out_x = dq, out_h = dh;  VJP: in_x = gq, in_h = gh, out_x = ggiven
+int adjoint_impl(const mpcasm_plan* plan, bool vjp, const double* const* h_src, const int64_t* h_src_stride,
+                 const double* d_params, const double* in_x, const double* in_h, double* out_x, double* out_h,
+                 void* d_work, int batch, void* stream) {
+  if (!plan || batch < 0) return MPCASM_ERR_ARG;
+  const PlanDev& d = plan->dev;
+  if (vjp ? (!in_x && !in_h) : (!out_x && !out_h)) return MPCASM_ERR_ARG;
+  if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (per-step dynamics: no S, U; the adjoint is the sweep's backward recursion)
+  if (batch == 0 || d.ng == 0) return MPCASM_OK;
+  if ((d.nsrc && (!h_src || !h_src_stride)) || (d.nparams && !d_params) || (vjp ? !out_x : !in_x))
+    return MPCASM_ERR_ARG;
+  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
+  {  // the plan's tables live on the device it was created on
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  }
+  SrcTable src, eff;
+  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  {  // (what the pre-pass refuses, before the index is built for nothing)
+    rc = lti_effective_sources(d, src, static_cast<double*>(d_work), plan->h_itab.data(), &eff);
+    if (rc != MPCASM_OK) return rc;
+  }
+  const AdjointIndex* index;
+  rc = plan_adjoint_index(plan, &index);
+  if (rc != MPCASM_OK) return rc;
+  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), batch, plan->h_itab.data(), &eff,
+                         static_cast<hipStream_t>(stream));
+  if (rc != MPCASM_OK) return rc;
+  hipError_t err;
+  rc = launch_assemble_adjoint(d, eff, *index, vjp, d_params, in_x, in_h, out_x, out_h, batch, plan->num_cus,
+                               static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
+}
+}  // namespace
+
+int mpcasm_assemble_jvp(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                        const double* d_params, const double* d_dgiven, double* d_dq, double* d_dh, void* d_work,
+                        int batch, void* stream) {
+  return adjoint_impl(plan, false, h_src, h_src_stride, d_params, d_dgiven, nullptr, d_dq, d_dh, d_work, batch,
+                      stream);
+}
+
+int mpcasm_assemble_vjp(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                        const double* d_params, const double* d_gq, const double* d_gh, double* d_ggiven,
+                        void* d_work, int batch, void* stream) {
+  return adjoint_impl(plan, true, h_src, h_src_stride, d_params, d_gq, d_gh, d_ggiven, nullptr, d_work, batch,
+                      stream);
+}
+
+int mpcasm_assemble_adjoint_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                                 const int64_t* h_src_stride, int32_t out[4]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  memset(out, 0, 4 * sizeof(int32_t));
+  PlanDev d;
+  const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
+  if (rc != MPCASM_OK) return rc;
+  if (d.nsrc && !h_src_stride) return MPCASM_ERR_ARG;
+  if (d.sw_ok) return MPCASM_ERR_LIMIT;
+  SrcTable src, eff;
+  memset(&src, 0, sizeof src);
+  for (int s = 0; s < d.nsrc; ++s) {
+    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
+    src.stride[s] = h_src_stride[s];
+  }
+  const int lti = lti_effective_sources(d, src, nullptr, h_itab, &eff);
+  if (lti != MPCASM_OK) return lti;
+  AdjointIndex index;
+  const int built = adjoint_build_index(d, h_itab, &index);
+  if (built != MPCASM_OK) return built;
+  out[0] = (int32_t)index.lds;
+  out[1] = index.lds > 64 * 1024;
+  out[2] = (int32_t)index.words.size();
+  out[3] = index.per_cu;
+  return MPCASM_OK;
 }
 
 int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,

@@ -101,6 +101,32 @@ int launch_next_given(const PlanDev& p, const SrcTable& eff, const int32_t* map,
                       hipError_t* err);
 int compile_given_map(const PlanDev& p, const int32_t* h_itab, const int32_t* rows, const double* values,
                       std::vector<int32_t>* out);
+// adjoint.hip: the derivative of the assembly with respect to `given`, applied matrix-free (mpcasm_assemble_jvp,
+// mpcasm_assemble_vjp).  The transposed index is derived from the plan's tables on the host; offsets are words
+// into `idx`, the o_* doubles into the kernel's dynamic LDS.  An entry of a rho row's contributions is two words:
+// source | flags, parameter slot.
+constexpr int32_t ADJ_SRC_MASK = (1 << 28) - 1, ADJ_HALF = 1 << 29, ADJ_LIMIT = 1 << 30;
+struct AdjointView {
+  const int32_t* idx;
+  int rowbase;            // [base rows] the base variable of every base row
+  int bsplit;             // [NBASE] where the unknowns begin among the base variable's columns (T_BCOLS)
+  int cb_ptr, cb_ent;     // [NG + NO + 1], [..] per column the base variables that cover it
+  int et_ptr, et_ent;     // [base rows + 1], [NENT][2] the CSC of E: workspace row, entry
+  int rj_ptr, rj_ent;     // [RTOT + 1], [..][2] what adds into a rho row, JVP
+  int rv_ptr, rv_ent;     // ... VJP
+  int lanes_j, lanes_v;   // threads per column of the last step
+  int o_x, o_gh, o_y, o_r, o_rho, o_bases;
+};
+struct AdjointIndex {
+  std::vector<int32_t> words;
+  AdjointView view;
+  size_t lds;             // dynamic LDS of a workgroup
+  int per_cu;             // resident workgroups per CU: grid = min(batch, CUs * per_cu)
+};
+int adjoint_build_index(const PlanDev& p, const int32_t* h_itab, AdjointIndex* out);
+int launch_assemble_adjoint(const PlanDev& p, const SrcTable& eff, const AdjointIndex& index, bool vjp,
+                            const double* params, const double* in_x, const double* in_h, double* out_x,
+                            double* out_h, int batch, int num_cus, hipStream_t stream, hipError_t* err);
 // rollout.hip: the preview rows and the next given of a plan compiled as ltv, by the forward recursion
 int compile_rollout_table(const PlanDev& p, const int32_t* recs, int nrec, const double* cvec, int ncvec,
                           std::vector<int32_t>* out);

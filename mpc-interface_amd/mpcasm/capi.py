@@ -112,6 +112,12 @@ SIGNATURES = {
     "mpcasm_preview_direct": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p),
                                              ctypes.POINTER(ctypes.c_int64), _void_p, _void_p,
                                              _void_p, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_assemble_jvp": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64)] +
+                            [_void_p] * 5 + [ctypes.c_int, _void_p]),
+    "mpcasm_assemble_vjp": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64)] +
+                            [_void_p] * 5 + [ctypes.c_int, _void_p]),
+    "mpcasm_assemble_adjoint_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
+                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_goal_distance": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
                                             _void_p, ctypes.c_int, ctypes.c_int, _void_p,
                                             ctypes.c_int, _void_p]),

@@ -9,7 +9,15 @@ symmetric ``K = [[P, G_A'], [G_A, 0]]``
 
 ("The derivative of a solve").  ``dL/dP`` is the gradient with respect to a symmetric ``P``, which the
 solvers require: a caller that builds ``P`` from parameters gets their gradient by the chain rule through that
-construction.  Gradients with respect to ``given`` and ``params`` through the assembly are not here.
+construction.
+
+Nobody holds ``P, q, G, h`` as leaves: they come out of the assembly.  ``P`` and ``G`` do not depend on ``given``, ``q``
+and ``h`` are affine in it, and :meth:`mpcasm.engine.Assembler.given_vjp` / :meth:`~mpcasm.engine.Assembler.given_jvp`
+apply that Jacobian and its transpose matrix-free on the device ("The derivative of the assembly").
+:func:`mpc_solve_diff` chains the two -- ``given.grad`` of a loss on the solution of the MPC's QP -- and
+:func:`tangent` is the tangential predictor ``x*(given + d) ~ x* + dx``.  Still open: gradients with respect to
+``params`` (weights, aims, arrows: they need the contraction with ``dL/dP``, ``dL/dG``), plans compiled with ``ltv=``
+(the sweep's backward recursion) and the fleet's wiring.
 """
 from . import engine
 from .engine import require_device
@@ -92,3 +100,95 @@ def solve_qp_diff(P, q, G, h, wide=False, **solve_kw):
     outcome = _Outcome()
     x, y = _function(torch).apply(P, q, G, h, outcome, bool(wide), solve_kw)
     return QpDiffSolution(x, y, outcome)
+
+
+class _MpcOutcome(_Outcome):
+    """:class:`_Outcome` of :func:`mpc_solve_diff`, with the assembled ``P, G, h`` the solve ran on (plain tensors of
+    the call's own: :func:`tangent` reads them)."""
+    __slots__ = ("P", "G", "h")
+
+    def __init__(self):
+        super().__init__()
+        self.P = self.G = self.h = None
+
+
+_MPC_FUNCTION = None
+
+
+def _mpc_function(torch):
+    global _MPC_FUNCTION
+    if _MPC_FUNCTION is not None:
+        return _MPC_FUNCTION
+
+    class MpcSolveDiff(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, given, asm, outcome, wide, solve_kw):
+            g = given.detach().contiguous()
+            f = dict(dtype=torch.float64, device=asm.device)
+            B, no, nc = asm.batch, asm.no, asm.nc
+            # (buffers of this call's own: the assembler's are overwritten by its next launch)
+            out = (torch.empty((B, no, no), **f), torch.empty((B, no), **f), torch.empty((B, nc, no), **f),
+                   torch.empty((B, nc), **f))
+            asm.assemble(g, out=out, stream=solve_kw.get("stream"))
+            P, q, G, h = out
+            solve = engine.solve_qp_wide if wide else engine.solve_qp
+            sol = solve(P, q, G, h, polish=True, **solve_kw)
+            outcome.sol, outcome.P, outcome.G, outcome.h = sol, P, G, h
+            ctx.asm, ctx.outcome, ctx.wide, ctx.stream = asm, outcome, wide, solve_kw.get("stream")
+            ctx.save_for_backward(P, G, h, sol.x, sol.y, sol.z, sol.status)
+            return sol.x.view_as(sol.x), sol.y.view_as(sol.y)
+
+        @staticmethod
+        def backward(ctx, gx, gy):
+            P, G, h, x, y, z, status = ctx.saved_tensors
+            sens = engine.qp_sensitivity_wide if ctx.wide else engine.qp_sensitivity
+            s = sens(P, G, h, (x, y, z), gx.contiguous(), gy.contiguous(), status=status, want_P=False, want_G=False,
+                     stream=ctx.stream)
+            ctx.outcome.verdict, ctx.outcome.lres = s.verdict, s.lres
+            # dL/dq = -u, dL/dh = w; an instance that is not SENS_DONE has u = w = 0: a zero row
+            return ctx.asm.given_vjp(-s.u, s.w, stream=ctx.stream), None, None, None, None
+
+    _MPC_FUNCTION = MpcSolveDiff
+    return _MPC_FUNCTION
+
+
+def mpc_solve_diff(asm, given, wide=False, **solve_kw):
+    """The MPC's QP as a differentiable function of ``given (B, ng)``, ``B = asm.batch``: ``asm.assemble(given)``, then
+    ``solve_qp(P, q, G, h, polish=True, **solve_kw)`` (``wide``: ``solve_qp_wide``).  A :class:`QpDiffSolution`, as
+    :func:`solve_qp_diff` returns it; ``backward`` through its ``x`` and ``y`` makes one
+    :func:`mpcasm.engine.qp_sensitivity` call (no dense ``dL/dP``, ``dL/dG``: ``P`` and ``G`` do not depend on
+    ``given``) and one :meth:`mpcasm.engine.Assembler.given_vjp` ``(-u, w)``.  An instance that is not ``SENS_DONE``
+    gets an exactly zero row of ``given.grad``.  The assembler's :attr:`~mpcasm.engine.Assembler.params` and sources
+    are read by both passes and not differentiated.  ``soft=`` and ``polish=`` are refused as in
+    :func:`solve_qp_diff`."""
+    if solve_kw.get("soft") is not None:
+        raise ValueError("mpc_solve_diff with soft=: the active-set model of the derivative is the hard problem's")
+    if "polish" in solve_kw:
+        raise ValueError("mpc_solve_diff always polishes: the derivative is taken at the polished point")
+    solve_kw.pop("soft", None)
+    torch = require_device()
+    if not (torch.is_tensor(given) and given.dtype == torch.float64 and given.device == asm.device
+            and tuple(given.shape) == (asm.batch, asm.ng)):
+        raise ValueError("given: a float64 tensor of shape (%d, %d) on %s" % (asm.batch, asm.ng, asm.device))
+    outcome = _MpcOutcome()
+    x, y = _mpc_function(torch).apply(given, asm, outcome, bool(wide), solve_kw)
+    return QpDiffSolution(x, y, outcome)
+
+
+def tangent(asm, sol, d, wide=False, P=None, G=None, h=None):
+    """The tangential predictor: ``(dx, dy)`` with ``x*(given + d) ~ x* + dx``, ``y* + dy`` while the active set
+    stays -- :meth:`mpcasm.engine.Assembler.given_jvp` ``(d)`` fed to :func:`mpcasm.engine.qp_jvp` (``wide``: its wide
+    form).  ``sol``: what :func:`mpc_solve_diff` returned (its ``P, G, h`` are used), or a polished
+    :class:`mpcasm.engine.PolishedQpSolution` / :class:`~mpcasm.engine.QpSolution` together with the ``P, G, h`` it
+    solved.  An instance that is not ``QP_SOLVED`` has ``dx = dy = 0``."""
+    if isinstance(sol, QpDiffSolution):
+        o = sol._outcome
+        P = getattr(o, "P", None) if P is None else P
+        G = getattr(o, "G", None) if G is None else G
+        h = getattr(o, "h", None) if h is None else h
+        sol = o.sol
+    if P is None or G is None or h is None:
+        raise ValueError("tangent: P, G, h of the solve (or the result of mpc_solve_diff)")
+    dq, dh = asm.given_jvp(d)
+    j = engine.qp_jvp(P, G, h, sol, dq, dh, status=getattr(sol, "status", None), wide=wide)
+    return j.dx, j.dy

@@ -904,6 +904,25 @@ def preview_route(plan, src_stride=None, nterms=0, ngoals=0):
     return tuple(int(x) for x in out)
 
 
+AdjointInfo = collections.namedtuple("AdjointInfo", "lds whole_lds index_words per_cu")
+
+
+def adjoint_info(plan, src_stride=None):
+    """What ``mpcasm_assemble_jvp`` / ``mpcasm_assemble_vjp`` launch for ``plan`` when its sources have the strides
+    ``src_stride`` (default: every source shared) -- ``mpcasm_assemble_adjoint_info``, the launches' own decision,
+    no device needed: an :class:`AdjointInfo` ``(LDS bytes of a workgroup, whole LDS, words of the transposed index,
+    resident workgroups per CU)``.  Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launches
+    refuse the plan (compiled with ``ltv=``, or one instance beyond a CU's LDS)."""
+    out = (ctypes.c_int32 * 4)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    n = len(plan.sources)
+    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
+    capi.check(capi.load().mpcasm_assemble_adjoint_info(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides, out),
+        "mpcasm_assemble_adjoint_info")
+    return AdjointInfo(*(int(x) for x in out))
+
+
 def sweep_route(plan):
     """What ``mpcasm_assemble`` launches for a plan with a dynamics compiled as ``ltv`` -- ``mpcasm_sweep_route``,
     the launch's own decision, no device needed: ``(CPT, specialised, PAIR, per_line, reg_lines, LR, LDS bytes,
@@ -1597,6 +1616,79 @@ class Assembler:
                 _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_preview_direct")
         return out
+
+    # ---- the derivative of the assembly with respect to `given` ---------------------------------
+    def _adjoint_args(self, what, count, tensors):
+        """The instances a call runs and its operands checked: ``tensors`` is ``(tensor or None, width, name)``."""
+        torch = self._torch
+        n = self.batch if count is None else int(count)
+        if not 0 <= n <= self.batch:
+            raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
+        checked = []
+        for t, width, name in tensors:
+            if t is not None:
+                t = _as_device(torch, t, self.device).reshape(-1, width).contiguous() if width else None
+                if t is not None and t.shape[0] < n:
+                    raise ValueError("%s: %s must have %d rows, got %d" % (what, name, n, t.shape[0]))
+            checked.append(t)
+        return n, checked
+
+    def given_jvp(self, d, out=None, count=None, stream=None):
+        """How ``q`` and ``h`` of :meth:`assemble` move along a change ``d (B, ng)`` of ``given``:
+        ``(dq (B, no), dh (B, nc))``, ``dq = J_q d``, ``dh = -cMg d`` (``mpcasm_assemble_jvp``; ``P`` and ``G`` do not
+        depend on ``given``), with this assembler's :attr:`params` and sources, matrix-free.  ``out``: the caller's
+        ``(dq, dh)``, a None among them skipped (not both).  Refused (``ERR_LIMIT``) for a plan compiled with
+        ``ltv=``."""
+        torch = self._torch
+        n, (d,) = self._adjoint_args("given_jvp", count, [(d, self.ng, "d")])
+        if out is None:
+            f = dict(dtype=torch.float64, device=self.device)
+            out = (torch.zeros((self.batch, self.no), **f), torch.zeros((self.batch, self.nc), **f))
+        dq, dh = out
+        if dq is None and dh is None:
+            raise ValueError("given_jvp: out holds neither dq nor dh")
+        if dq is not None:
+            _checked_out(torch, dq, (n, self.no), self.device, "given_jvp dq")
+        if dh is not None:
+            _checked_out(torch, dh, (n, self.nc), self.device, "given_jvp dh")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptrs, strides = self._src_args()
+        work = self._workspace()
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_assemble_jvp(
+                self._handle, ptrs, strides, self.params.data_ptr(), ptr(d), ptr(dq), ptr(dh), work.data_ptr(), n,
+                _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_assemble_jvp")
+        return dq, dh
+
+    def given_vjp(self, gq, gh, out=None, count=None, stream=None):
+        """``dL/dgiven (B, ng) = J_q' gq + J_h' gh`` for ``gq = dL/dq (B, no)`` and ``gh = dL/dh (B, nc)`` of
+        :meth:`assemble`'s ``q`` and ``h`` (``mpcasm_assemble_vjp``); a None cotangent is zero (not both).  Same
+        conventions as :meth:`given_jvp`; ``out``: the caller's ``ggiven``."""
+        torch = self._torch
+        if gq is None and gh is None:
+            raise ValueError("given_vjp: neither gq nor gh")
+        n, (gq, gh) = self._adjoint_args("given_vjp", count, [(gq, self.no, "gq"), (gh, self.nc, "gh")])
+        if out is None:
+            out = torch.zeros((self.batch, self.ng), dtype=torch.float64, device=self.device)
+        else:
+            _checked_out(torch, out, (n, self.ng), self.device, "given_vjp")
+        if gq is None and gh is None:      # (no rows of G and no gq: nothing depends on given)
+            out[:n].zero_()
+            return out
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptrs, strides = self._src_args()
+        work = self._workspace()
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_assemble_vjp(
+                self._handle, ptrs, strides, self.params.data_ptr(), ptr(gq), ptr(gh), out.data_ptr(),
+                work.data_ptr(), n, _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_assemble_vjp")
+        return out
+
+    def adjoint_info(self):
+        """What :meth:`given_jvp` / :meth:`given_vjp` launch with the sources bound now (:func:`adjoint_info`)."""
+        return adjoint_info(self.plan, self._src_stride)
 
     def preview_route(self, goals=False):
         """What :meth:`preview_rows` -- with ``goals`` (the Formulation whose goals :meth:`goal_terms` lists)
