@@ -48,7 +48,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
  * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment, for the one that added
  * mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft and their two info entries and for the one that added
  * mpcasm_qp_sens, mpcasm_qp_sens_wide and their two info entries and for the one that added mpcasm_assemble_jvp,
- * mpcasm_assemble_vjp and mpcasm_assemble_adjoint_info (the project's tests pin
+ * mpcasm_assemble_vjp and mpcasm_assemble_adjoint_info and for the one that added mpcasm_assemble_route (the
+ * project's tests pin
  * the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
@@ -100,8 +101,11 @@ enum { MPCASM_OPT_PATH = 1, MPCASM_OPT_PHASE_MASK = 2, MPCASM_OPT_RESIDENT_PER_C
  * 16-byte stores whenever P fits there beside the workspace; 0 (default): as 1 when the launch
  * writes less than ~0.55 GB, or when P in LDS would cost a workgroup per CU and an instance's
  * results are small (< 128 KB), else as 2.
- * These options are process-wide test / tuning hooks, not part of a launch's state: set them
- * before other threads start launching. */
+ * These options are process-wide test / tuning hooks.  Every launch reads them once, when it starts, into a
+ * record of its own that travels with it: a change made while other threads launch is seen whole by the launches
+ * that start after it and not at all by those under way (the values are atomic, there is no data race) -- but
+ * which launches those are is the caller's to order.  A caller with several plans on several threads uses
+ * mpcasm_plan_set_option. */
 int mpcasm_set_option(int option, int value);
 /* The same choice for ONE plan (MPCASM_OPT_PATH, MPCASM_OPT_JIT, MPCASM_OPT_RESIDENT_PER_CU,
  * MPCASM_OPT_RESIDENT_GRID; value
@@ -251,7 +255,7 @@ int mpcasm_assemble_indexed(const mpcasm_plan* plan, const double* const* h_src,
 /* Which kernels the latest successful mpcasm_assemble on this plan launched (a record for
  * benchmarks and tests; 0 before the first launch): the persistent kernel ahead of time / compiled
  * for the plan, the per-instance fused kernel, the staged K2 -> K3 -> K4 pipeline, the tiled
- * kernel for wide problems. */
+ * kernel for wide problems.  With two threads launching on one plan the record is the last writer's. */
 enum { MPCASM_KERNEL_NONE = 0, MPCASM_KERNEL_RESIDENT = 1, MPCASM_KERNEL_RESIDENT_JIT = 2,
        MPCASM_KERNEL_FUSED = 3, MPCASM_KERNEL_STAGED = 4, MPCASM_KERNEL_TILED = 5,
        MPCASM_KERNEL_TILED_SCAN = 6 /* the tiled kernel's scan form: P summed along diagonals */,
@@ -386,6 +390,26 @@ enum { MPCASM_TILED_TABLES_NONE = 0, MPCASM_TILED_TABLES_SMALL = 1 /* a wavefron
 enum { MPCASM_WANT_COST = 1, MPCASM_WANT_CONSTRAINTS = 2 };
 int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                        const int64_t* h_src_stride, int batch, int want, int path, int32_t out[16]);
+
+/* Diagnostic, needs no device: which kernel family mpcasm_assemble (indexed = 0) or mpcasm_assemble_indexed
+ * (indexed = 1) runs a launch of `batch` instances of these tables on (validated as mpcasm_plan_create does), under
+ * MPCASM_OPT_PATH `path` (0 .. 4; -1: the process-wide value), when the launch's inputs meet the alignment the
+ * persistent kernel's 16-byte loads assume (inputs_aligned = 1: `given`, the parameters and the sources it reads
+ * that way 16-byte aligned with even strides) or not (0).  The launch takes the decision from the same function.
+ * The order: the sweep kernel for a plan with a dynamics compiled as ltv; the persistent kernel when an instance
+ * fits a CU's LDS, the inputs are aligned and `path` is 0 (any `path` for a plan compiled with lti=[...] or with
+ * results in CSC form, which run nowhere else on chip); the tiled kernel for a wide problem unless `path` is 2;
+ * the per-instance fused kernel while two workgroups fit a CU and `path` is at most 1; else the staged pipeline.
+ * out[0]: MPCASM_KERNEL_* -- the persistent kernel always as MPCASM_KERNEL_RESIDENT (whether the launch takes the
+ * kernel compiled for the plan depends on the batch, MPCASM_OPT_JIT and the runtime: mpcasm_plan_last_kernel may
+ * say MPCASM_KERNEL_RESIDENT_JIT for the same route), the tiled path always as MPCASM_KERNEL_TILED (its form:
+ * mpcasm_tiled_route); out[1]: dynamic LDS bytes of a workgroup of the persistent or the fused kernel, else 0;
+ * out[2]: 1 when the persistent kernel hands P over directly at this batch, 0 through LDS (as out[0] / out[1] of
+ * mpcasm_resident_lds_bytes); out[3]: 0.  MPCASM_ERR_LIMIT exactly where the launch returns it (out is zeroed):
+ * rows of `given` by index off the persistent kernel, or a plan compiled with lti=[...] or with CSC results
+ * that fits no kernel.  MPCASM_ERR_ARG: batch < 1, `path` out of range, a flag that is not 0 or 1. */
+int mpcasm_assemble_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int batch,
+                          int path, int inputs_aligned, int indexed, int32_t out[4]);
 
 /* f3  sparse hand-off -----------------------------------------------------------
  * Replaces the dense -> CSC conversion in front of the solver call of the walking loop

@@ -585,40 +585,39 @@ size_t assemble_workspace_bytes(const PlanDev& p, int batch) {
   return (size_t)batch * p.rtot * p.ldv * sizeof(double);
 }
 
-int launch_assemble_staged(const PlanDev& p, const SrcTable& src, const double* params,
-                           const double* given, double* P, double* q, double* G, double* h,
-                           void* work, int batch, hipStream_t stream, hipError_t* err) {
-  double* V = static_cast<double*>(work);
+int launch_assemble_staged(const PlanDev& p, const AssembleCall& c) {
+  double* V = static_cast<double*>(c.work);
+  const int batch = c.batch;
   if (p.rtot > 0) {
     const unsigned nrb = ceil_div(p.rtot, WAVES * K2_ROWS_PER_WAVE);
-    hipLaunchKernelGGL(compose_rowsets_kernel, dim3(nrb * batch), dim3(BLOCK), 0, stream, p, src,
-                       given, V, (int)nrb);
+    hipLaunchKernelGGL(compose_rowsets_kernel, dim3(nrb * batch), dim3(BLOCK), 0, c.stream, p, c.src,
+                       c.given, V, (int)nrb);
   }
-  if (P && p.no >= GB) {
+  if (c.P && p.no >= GB) {
     // wide problems: P by the LDS-tiled GEMM, q by the block kernel on its own column
     const int nb = (int)ceil_div(p.no, GB);
     const int sym = p.rs_sym_any;
     const int npairs = sym ? nb * (nb + 1) / 2 : nb * nb;
-    hipLaunchKernelGGL(hessian_gemm_kernel, dim3((unsigned)npairs * batch), dim3(BLOCK), 0, stream,
-                       p, params, V, P, nb, npairs, sym);
+    hipLaunchKernelGGL(hessian_gemm_kernel, dim3((unsigned)npairs * batch), dim3(BLOCK), 0, c.stream,
+                       p, c.params, V, c.P, nb, npairs, sym);
     const unsigned ncb = ceil_div(p.no, 64);
-    hipLaunchKernelGGL(gradient_kernel, dim3(ncb * batch), dim3(BLOCK), 0, stream, p, params, V, q,
+    hipLaunchKernelGGL(gradient_kernel, dim3(ncb * batch), dim3(BLOCK), 0, c.stream, p, c.params, V, c.q,
                        (int)ncb);
-  } else if (P && p.no > 0) {
+  } else if (c.P && p.no > 0) {
     const unsigned nblk = ceil_div(p.no, 32) * ceil_div(p.no + 1, 32);
     const unsigned nrb = ceil_div(nblk, WAVES);
-    hipLaunchKernelGGL(hessian_kernel, dim3(nrb * batch), dim3(BLOCK), 0, stream, p, params, V, P,
-                       q, (int)nrb, 0);
+    hipLaunchKernelGGL(hessian_kernel, dim3(nrb * batch), dim3(BLOCK), 0, c.stream, p, c.params, V, c.P,
+                       c.q, (int)nrb, 0);
   }
-  if (G && p.nc > 0) {
+  if (c.G && p.nc > 0) {
     if (p.max_axes > K4_AXMAX) return MPCASM_ERR_LIMIT;
     const unsigned nrb = ceil_div(p.nc, K4_ROWS);
     const unsigned groups = ceil_div((unsigned)batch, 8u);
-    hipLaunchKernelGGL(constraints_kernel, dim3(nrb * groups * 8), dim3(BLOCK), 0, stream, p, params,
-                       V, G, h, (int)nrb, batch);
+    hipLaunchKernelGGL(constraints_kernel, dim3(nrb * groups * 8), dim3(BLOCK), 0, c.stream, p, c.params,
+                       V, c.G, c.h, (int)nrb, batch);
   }
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  *c.err = hipGetLastError();
+  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
 int launch_preview_matrices(const PlanDev& p, const SrcTable& src, double* PM, int batch,

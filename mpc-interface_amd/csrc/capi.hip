@@ -7,6 +7,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
+#include <climits>
 #include <cmath>
 #include <mutex>
 #include <new>
@@ -19,11 +21,14 @@
 using namespace mpcasm;
 
 namespace mpcasm {
-int g_p_direct = 0;  // MPCASM_OPT_P_DIRECT (read when a plan is created)
-extern int g_path;
-extern int g_phase_mask;
-extern int g_resident_per_cu, g_resident_grid;
+Options g_options;
 }
+
+// mpcasm_plan_set_option: a plan's own choice of path / per-plan compilation / workgroups per CU / workgroups per
+// launch (-1: the process-wide value of mpcasm_set_option)
+struct PlanOptions {
+  int path = -1, jit = -1, per_cu = -1, grid = -1;
+};
 
 struct mpcasm_plan {
   PlanDev dev;
@@ -32,10 +37,9 @@ struct mpcasm_plan {
   int device;
   int num_cus;
   std::vector<int32_t> h_itab;  // host copy: what a specialised kernel is generated from (jit.hip)
-  // mpcasm_plan_set_option: this plan's own choice of path / per-plan compilation / workgroups
-  // per CU (-1: the process-wide value of mpcasm_set_option)
-  int opt_path = -1, opt_jit = -1, opt_per_cu = -1, opt_grid = -1;
-  mutable int last_kernel = 0;  // mpcasm_plan_last_kernel: what the latest mpcasm_assemble launched
+  PlanOptions opt;
+  // mpcasm_plan_last_kernel: what the latest mpcasm_assemble launched (two threads on one plan: the last writer)
+  mutable std::atomic<int> last_kernel{0};
   // the transposed index of mpcasm_assemble_jvp / _vjp (adjoint.hip): derived from h_itab and uploaded by the
   // first call, under the mutex; adj_rc: what that attempt returned (1: not tried yet)
   mutable std::mutex adj_mutex;
@@ -57,6 +61,40 @@ int hip_fail(hipError_t e) {
 int launched(int rc, const hipError_t& err) {
   if (rc == MPCASM_ERR_HIP) g_last_hip = (int)err;
   return rc;
+}
+
+// every option, once: its id, the least and the greatest value mpcasm_set_option takes, the process-wide value and,
+// for the four a plan may set for itself, the plan's own (mpcasm_plan_set_option takes -1 beside the range)
+struct OptionRow {
+  int id, least, greatest;
+  std::atomic<int> Options::*wide;
+  int PlanOptions::*own;
+};
+constexpr OptionRow OPTION_TABLE[] = {
+    {MPCASM_OPT_PATH, 0, 4, &Options::path, &PlanOptions::path},
+    {MPCASM_OPT_PHASE_MASK, INT_MIN, INT_MAX, &Options::phase_mask, nullptr},
+    {MPCASM_OPT_P_DIRECT, 0, 2, &Options::p_direct, nullptr},
+    {MPCASM_OPT_JIT, 0, 2, &Options::jit, &PlanOptions::jit},
+    {MPCASM_OPT_RESIDENT_PER_CU, 0, 16, &Options::per_cu, &PlanOptions::per_cu},
+    {MPCASM_OPT_JIT_FETCH_RUNS, 0, FS_MAX, &Options::fetch_runs, nullptr},
+    {MPCASM_OPT_RESIDENT_GRID, 0, 1 << 20, &Options::grid, &PlanOptions::grid},
+};
+const OptionRow* option_row(int id) {
+  for (const OptionRow& row : OPTION_TABLE)
+    if (row.id == id) return &row;
+  return nullptr;
+}
+
+// the options a launch of `plan` runs under, or with plan == nullptr the process-wide ones: the only place where
+// "the plan's own value, else the process-wide one" is written
+LaunchOptions launch_options(const mpcasm_plan* plan) {
+  const auto pick = [plan](int PlanOptions::*own, const std::atomic<int>& wide) {
+    return plan && plan->opt.*own >= 0 ? plan->opt.*own : wide.load(std::memory_order_relaxed);
+  };
+  const Options& g = g_options;
+  return LaunchOptions{pick(&PlanOptions::path, g.path),     pick(&PlanOptions::jit, g.jit),
+                       pick(&PlanOptions::per_cu, g.per_cu), pick(&PlanOptions::grid, g.grid),
+                       g.phase_mask.load(std::memory_order_relaxed), g.fetch_runs.load(std::memory_order_relaxed)};
 }
 
 // ---- the checks the QP entries share (every one of them decided before any device call) -------------------
@@ -93,7 +131,7 @@ int host_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t
   if (rc != MPCASM_OK) return rc;
   memset(d, 0, sizeof *d);
   plan_view(h_itab, d);
-  d->rs_p_direct = d->rs_ok ? resident_choose_p_direct(*d, g_p_direct) : 0;
+  d->rs_p_direct = d->rs_ok ? resident_choose_p_direct(*d, g_options.p_direct.load(std::memory_order_relaxed)) : 0;
   // the CSC form of P is read out of its LDS copy: such a plan has no other way
   if (d->csc_pnnz != 0 && d->rs_ok) d->rs_p_direct = resident_choose_p_direct(*d, 2);
   return MPCASM_OK;
@@ -114,50 +152,17 @@ int mpcasm_device_count(void) {
 int mpcasm_last_hip(void) { return g_last_hip; }
 
 int mpcasm_set_option(int option, int value) {
-  if (option == MPCASM_OPT_PATH) {
-    if (value < 0 || value > 4) return MPCASM_ERR_ARG;
-    g_path = value;
-    return MPCASM_OK;
-  }
-  if (option == MPCASM_OPT_PHASE_MASK) {
-    g_phase_mask = value;
-    return MPCASM_OK;
-  }
-  if (option == MPCASM_OPT_P_DIRECT) {
-    if (value < 0 || value > 2) return MPCASM_ERR_ARG;
-    g_p_direct = value;
-    return MPCASM_OK;
-  }
-  if (option == MPCASM_OPT_JIT) {
-    if (value < 0 || value > 2) return MPCASM_ERR_ARG;
-    g_jit = value;
-    return MPCASM_OK;
-  }
-  if (option == MPCASM_OPT_RESIDENT_PER_CU) {
-    if (value < 0 || value > 16) return MPCASM_ERR_ARG;
-    g_resident_per_cu = value;
-    return MPCASM_OK;
-  }
-  if (option == MPCASM_OPT_JIT_FETCH_RUNS) {
-    if (value < 0 || value > FS_MAX) return MPCASM_ERR_ARG;
-    g_jit_fetch_runs = value;
-    return MPCASM_OK;
-  }
-  if (option == MPCASM_OPT_RESIDENT_GRID) {
-    if (value < 0 || value > (1 << 20)) return MPCASM_ERR_ARG;
-    g_resident_grid = value;
-    return MPCASM_OK;
-  }
-  return MPCASM_ERR_ARG;
+  const OptionRow* row = option_row(option);
+  if (!row || value < row->least || value > row->greatest) return MPCASM_ERR_ARG;
+  (g_options.*row->wide).store(value, std::memory_order_relaxed);
+  return MPCASM_OK;
 }
 
 int mpcasm_plan_set_option(mpcasm_plan* plan, int option, int value) {
   if (!plan) return MPCASM_ERR_ARG;
-  if (option == MPCASM_OPT_PATH && value >= -1 && value <= 4) plan->opt_path = value;
-  else if (option == MPCASM_OPT_JIT && value >= -1 && value <= 2) plan->opt_jit = value;
-  else if (option == MPCASM_OPT_RESIDENT_PER_CU && value >= -1 && value <= 16) plan->opt_per_cu = value;
-  else if (option == MPCASM_OPT_RESIDENT_GRID && value >= -1 && value <= (1 << 20)) plan->opt_grid = value;
-  else return MPCASM_ERR_ARG;
+  const OptionRow* row = option_row(option);
+  if (!row || !row->own || (value != -1 && (value < row->least || value > row->greatest))) return MPCASM_ERR_ARG;
+  plan->opt.*row->own = value;
   return MPCASM_OK;
 }
 
@@ -287,7 +292,7 @@ int mpcasm_jit_check(const int32_t* h_itab, size_t n_itab, const double* h_dtab,
       if (form == large && small != large && out != MPCASM_OK) break;
       d.rs_p_direct = form;
       // (through the disk cache, as a launch would: a second check of the same plan compiles nothing)
-      out = jit_code_for(jit_spec_header(d, h_itab, g_jit_fetch_runs), false, 0xBF, &code, &text) ? MPCASM_OK : MPCASM_ERR_HIP;
+      out = jit_code_for(jit_spec_header(d, h_itab, launch_options(nullptr).fetch_runs), false, 0xBF, &code, &text) ? MPCASM_OK : MPCASM_ERR_HIP;
       if (small == large) break;
     }
   }
@@ -326,15 +331,15 @@ int mpcasm_plan_prepare(const mpcasm_plan* plan, int batch) {
   if (!plan || batch < 0) return MPCASM_ERR_ARG;
   int current = -1;
   if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  const LaunchOptions opt = launch_options(plan);
+  AssembleRoute r;
+  // (nothing is compiled per plan for the other kernels; input alignment is taken as given)
+  if (assemble_route(plan->dev, batch, opt, true, false, &r) != MPCASM_OK || r.kernel != MPCASM_KERNEL_RESIDENT)
+    return MPCASM_OK;
   PlanDev p = plan->dev;
-  if (!p.rs_ok || p.sw_ok) return MPCASM_OK;  // (nothing is compiled per plan for the other kernels)
-  p.rs_p_direct = resident_p_direct_for(plan->dev, batch);
-  const size_t rs = resident_lds_bytes(p);
-  if (rs == 0 || rs > RESIDENT_LDS_LIMIT) return MPCASM_OK;
-  t_path = plan->opt_path >= 0 ? plan->opt_path : g_path;
-  t_jit = plan->opt_jit >= 0 ? plan->opt_jit : g_jit;
-  if (t_path != 0 && p.rs_nlti == 0 && p.csc_pnnz == 0 && p.csc_gnnz == 0) return MPCASM_OK;
-  (void)jit_kernel_for(p, plan->h_itab.data(), plan->device, batch, rs);  // (a failure: the ahead-of-time kernel)
+  p.rs_p_direct = r.p_direct;
+  // (a failure: the ahead-of-time kernel)
+  (void)jit_kernel_for(p, plan->h_itab.data(), plan->device, batch, r.lds, opt.jit, opt.phase_mask, opt.fetch_runs);
   return MPCASM_OK;
 }
 
@@ -374,7 +379,7 @@ int mpcasm_workspace_bytes(const mpcasm_plan* plan, int batch, size_t* out_bytes
   const size_t stamps = 2 * groups * 8 * 8 * sizeof(uint64_t);
   // a wide problem on the tiled kernel needs d and the generated horizon tables only -- unless the
   // options in force send it down the staged pipeline (a test hook): ask again after changing them
-  const int path = plan->opt_path >= 0 ? plan->opt_path : g_path;
+  const int path = launch_options(plan).path;
   if (sweep_eligible(plan->dev)) {  // (everything in LDS)
     *out_bytes = stamps;
     return MPCASM_OK;
@@ -419,15 +424,12 @@ static int assemble_impl(const mpcasm_plan* plan, const double* const* h_src,
     src.stride[MAX_SOURCES - 1] = -1;
   }
   hipError_t err;
-  // what this launch runs on: the plan's own options where it has them, else the process-wide ones
-  t_path = plan->opt_path >= 0 ? plan->opt_path : g_path;
-  t_jit = plan->opt_jit >= 0 ? plan->opt_jit : g_jit;
-  t_per_cu = plan->opt_per_cu >= 0 ? plan->opt_per_cu : g_resident_per_cu;
-  t_grid = plan->opt_grid >= 0 ? plan->opt_grid : g_resident_grid;
-  rc = launch_assemble(d, src, d_params, d_given, d_P, d_q, d_G, d_h, d_work, batch,
-                       plan->num_cus, static_cast<hipStream_t>(stream), &err, plan->h_itab.data(),
-                       plan->device, d_given_index != nullptr);
-  if (rc == MPCASM_OK) plan->last_kernel = t_last_kernel;
+  int kernel = MPCASM_KERNEL_NONE;
+  const AssembleCall call{src, d_params, d_given, d_P, d_q, d_G, d_h, d_work, batch,
+                          static_cast<hipStream_t>(stream), plan->num_cus, plan->device, plan->h_itab.data(),
+                          d_given_index != nullptr, launch_options(plan), &err, &kernel};
+  rc = launch_assemble(d, call);
+  if (rc == MPCASM_OK) plan->last_kernel.store(kernel, std::memory_order_relaxed);
   return launched(rc, err);
 }
 
@@ -448,7 +450,9 @@ int mpcasm_assemble_indexed(const mpcasm_plan* plan, const double* const* h_src,
                        d_work, batch, stream);
 }
 
-int mpcasm_plan_last_kernel(const mpcasm_plan* plan) { return plan ? plan->last_kernel : MPCASM_ERR_ARG; }
+int mpcasm_plan_last_kernel(const mpcasm_plan* plan) {
+  return plan ? plan->last_kernel.load(std::memory_order_relaxed) : MPCASM_ERR_ARG;
+}
 
 int mpcasm_preview_matrices(const mpcasm_plan* plan, const double* const* h_src,
                             const int64_t* h_src_stride, double* d_PM, int batch, void* stream) {
@@ -660,16 +664,14 @@ int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
     if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
     src.stride[s] = h_src_stride[s];
   }
-  if (path < 0) path = g_path;
-  // launch_assemble's order: the sweep kernel, the persistent kernel, then the tiled path
-  if (sweep_eligible(d)) return MPCASM_ERR_ARG;
-  d.rs_p_direct = d.rs_ok ? resident_p_direct_for(d, batch) : 0;
-  const size_t rs = resident_lds_bytes(d);
-  if (rs != 0 && rs <= RESIDENT_LDS_LIMIT && (path == 0 || d.rs_nlti != 0 || d.csc_pnnz != 0 || d.csc_gnnz != 0))
+  LaunchOptions opt = launch_options(nullptr);
+  if (path >= 0) opt.path = path;
+  AssembleRoute r;
+  if (assemble_route(d, batch, opt, true, false, &r) != MPCASM_OK || r.kernel != MPCASM_KERNEL_TILED)
     return MPCASM_ERR_ARG;
-  if (!tiled_eligible(d) || path == 2 || d.csc_pnnz != 0 || d.csc_gnnz != 0) return MPCASM_ERR_ARG;
+  d.rs_p_direct = r.p_direct;
   TiledChoice c;
-  const int choice = tiled_choose(d, src, h_itab, path, batch, (want & MPCASM_WANT_COST) != 0,
+  const int choice = tiled_choose(d, src, h_itab, opt.path, batch, (want & MPCASM_WANT_COST) != 0,
                                   (want & MPCASM_WANT_CONSTRAINTS) != 0, true, true, &c);
   if (choice != MPCASM_OK) return choice;
   out[0] = c.form;
@@ -683,6 +685,26 @@ int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
   out[8] = c.tables;
   out[9] = c.tg;
   out[10] = c.sym;
+  return MPCASM_OK;
+}
+
+int mpcasm_assemble_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int batch,
+                          int path, int inputs_aligned, int indexed, int32_t out[4]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out || batch < 1 || path < -1 || path > 4 ||
+      (inputs_aligned != 0 && inputs_aligned != 1) || (indexed != 0 && indexed != 1))
+    return MPCASM_ERR_ARG;
+  memset(out, 0, 4 * sizeof(int32_t));
+  PlanDev d;
+  int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
+  if (rc != MPCASM_OK) return rc;
+  LaunchOptions opt = launch_options(nullptr);
+  if (path >= 0) opt.path = path;
+  AssembleRoute r;
+  rc = assemble_route(d, batch, opt, inputs_aligned != 0, indexed != 0, &r);
+  if (rc != MPCASM_OK) return rc;
+  out[0] = r.kernel;
+  out[1] = (int32_t)r.lds;
+  out[2] = r.p_direct;
   return MPCASM_OK;
 }
 
@@ -1274,63 +1296,6 @@ hipError_t allow_whole_lds(const void* fn) {
     (void)hipGetLastError();
   }
   return e;
-}
-
-int g_path = 0;  // test hook (MPCASM_OPT_PATH): 0 best, 1 no resident kernel, 2 staged only
-int g_resident_per_cu = 0;  // tuning aid (MPCASM_OPT_RESIDENT_PER_CU): 0 = automatic
-int g_resident_grid = 0;    // MPCASM_OPT_RESIDENT_GRID: 0 = every resident workgroup slot
-// the values in force for the launch this thread is making (mpcasm_assemble sets them)
-thread_local int t_path = 0, t_jit = 0, t_per_cu = 0, t_grid = 0;
-thread_local int t_last_kernel = 0;
-
-// dispatch: fused single launch when the problem fits on chip, else staged
-int launch_assemble(const PlanDev& plan, const SrcTable& src, const double* params,
-                    const double* given, double* P, double* q, double* G, double* h, void* work,
-                    int batch, int num_cus, hipStream_t stream, hipError_t* err,
-                    const int32_t* h_itab, int device, bool indexed) {
-  // a dynamics compiled as ltv: the sweep kernel and nothing else (the other kernels' tables describe
-  // the formulation's own horizon matrices, the source slots carry (A_k, B_k))
-  if (sweep_eligible(plan)) {
-    if (indexed) return MPCASM_ERR_LIMIT;   // (rows of `given` by index: the persistent kernel only)
-    t_last_kernel = MPCASM_KERNEL_SWEEP;
-    return launch_assemble_sweep(plan, src, params, given, P, q, G, h, batch, stream, err, h_itab);
-  }
-  PlanDev p = plan;
-  p.rs_p_direct = p.rs_ok ? resident_p_direct_for(plan, batch) : 0;  // (the launch's size decides)
-  // the persistent kernel may take a whole CU's LDS (one workgroup of 8 wavefronts per
-  // CU still beats the staged pipeline by far); the per-instance fused kernel is only
-  // worth it while two workgroups fit
-  constexpr size_t FUSED_LDS_LIMIT = 80 * 1024;
-  const size_t rs = resident_lds_bytes(p);
-  if (rs != 0 && rs <= RESIDENT_LDS_LIMIT && (t_path == 0 || p.rs_nlti != 0 || p.csc_pnnz != 0 || p.csc_gnnz != 0) &&
-      resident_inputs_aligned(p, src, params, given)) {
-    // large batches: the same kernel compiled for this very plan (jit.hip), when available
-    if (h_itab != nullptr)
-      if (const void* k = jit_kernel_for(p, h_itab, device, batch, rs)) {
-        t_last_kernel = MPCASM_KERNEL_RESIDENT_JIT;
-        return jit_launch(k, p, src, params, given, P, q, G, h, batch, num_cus, t_per_cu,
-                          t_grid, work, stream, err);
-      }
-    t_last_kernel = MPCASM_KERNEL_RESIDENT;
-    return launch_assemble_resident(p, src, params, given, P, q, G, h, work, batch, rs, num_cus,
-                                    stream, err);
-  }
-  if (indexed) return MPCASM_ERR_LIMIT;   // (rows of `given` by index: the persistent kernel only)
-  // wide problems: one workgroup per block of P, rows composed straight into the LDS tiles
-  if (tiled_eligible(p) && t_path != 2 && p.csc_pnnz == 0 && p.csc_gnnz == 0) {
-    t_last_kernel = MPCASM_KERNEL_TILED;
-    return launch_assemble_tiled(p, src, params, given, P, q, G, h, work, batch, stream, err, h_itab);
-  }
-  // elsewhere, horizon matrices generated from (A, B) and the CSC form of the results exist in the
-  // persistent kernel only
-  if (p.rs_nlti != 0 || p.csc_pnnz != 0 || p.csc_gnnz != 0) return MPCASM_ERR_LIMIT;
-  const size_t lds = fused_lds_bytes(p, 4);
-  if (lds != 0 && lds <= FUSED_LDS_LIMIT && t_path <= 1) {
-    t_last_kernel = MPCASM_KERNEL_FUSED;
-    return launch_assemble_fused(p, src, params, given, P, q, G, h, batch, lds, stream, err);
-  }
-  t_last_kernel = MPCASM_KERNEL_STAGED;
-  return launch_assemble_staged(p, src, params, given, P, q, G, h, work, batch, stream, err);
 }
 
 }  // namespace mpcasm

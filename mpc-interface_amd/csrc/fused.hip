@@ -26,8 +26,6 @@
 
 namespace mpcasm {
 
-int g_phase_mask = 0xBF;  // diagnostic (timing-only ablation): see mpcasm_set_option
-
 namespace {
 
 constexpr int TPW = 9;       // MFMA output tiles a wavefront may own
@@ -321,19 +319,17 @@ size_t fused_lds_bytes(const PlanDev& p, int nw) {
   return (size_t)fused_layout(p, nw).total_doubles * sizeof(double);
 }
 
-int launch_assemble_fused(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h,
-                          int batch, size_t lds_bytes, hipStream_t stream, hipError_t* err) {
+int launch_assemble_fused(const PlanDev& p, const AssembleCall& c, size_t lds_bytes) {
   constexpr int NW = 4;
   auto kernel = fused_assemble_kernel<NW>;
   if (lds_bytes > 64 * 1024) {
-    *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
-    if (*err != hipSuccess) return MPCASM_ERR_HIP;
+    *c.err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
+    if (*c.err != hipSuccess) return MPCASM_ERR_HIP;
   }
-  hipLaunchKernelGGL(kernel, dim3(batch), dim3(NW * 64), lds_bytes, stream, p, src, params, given,
-                     P, q, G, h, batch, g_phase_mask);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  hipLaunchKernelGGL(kernel, dim3(c.batch), dim3(NW * 64), lds_bytes, c.stream, p, c.src, c.params, c.given,
+                     c.P, c.q, c.G, c.h, c.batch, c.opt.phase_mask);
+  *c.err = hipGetLastError();
+  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
 }  // namespace mpcasm

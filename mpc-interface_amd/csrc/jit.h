@@ -6,13 +6,9 @@
 #include <string>
 #include <vector>
 
-#include "plan_dev.h"
+#include "kernels.h"
 
 namespace mpcasm {
-
-extern int g_jit;         // MPCASM_OPT_JIT
-extern int g_jit_fetch_runs;  // MPCASM_OPT_JIT_FETCH_RUNS
-extern int g_phase_mask;  // fused.hip
 
 // "plan_spec.h" of a plan: its sizes and trip lists as constants
 // (seg_limit: most runs a chunk of a fetch table may have to be fetched by arithmetic, at most FS_MAX)
@@ -24,8 +20,9 @@ std::vector<int32_t> jit_fetch_plan(const PlanDev& d, const int32_t* h_itab, int
 int jit_compile(const std::string& header, std::vector<char>* code, std::string* log,
                 bool stamps = false, int phases = 0xBF);
 // the compiled kernel of (plan structure, device), or nullptr: use the ahead-of-time kernel
+// (jit, phase_mask, fetch_runs: the launch's MPCASM_OPT_JIT, _PHASE_MASK and _JIT_FETCH_RUNS)
 const void* jit_kernel_for(const PlanDev& d, const int32_t* h_itab, int device, int batch,
-                           size_t lds_bytes);
+                           size_t lds_bytes, int jit, int phase_mask, int fetch_runs);
 // the code object of a generated header: from the disk cache ($MPCASM_CACHE_DIR, $XDG_CACHE_HOME/mpcasm
 // or ~/.cache/mpcasm; MPCASM_NO_DISK_CACHE=1: never), else compiled and stored there
 // (distrust_disk: the cached file was read and did not load -- delete it and compile)
@@ -36,8 +33,6 @@ bool jit_available();
 void jit_stats(long out[3]);
 // (called when a plan is destroyed: compiled kernels are remembered by the plan's device tables)
 void jit_forget(const void* itab);
-int jit_launch(const void* kernel, const PlanDev& p, const SrcTable& src, const double* params,
-               const double* given, double* P, double* q, double* G, double* h, int batch,
-               int num_cus, int per_cu_limit, int grid_limit, void* work, hipStream_t stream, hipError_t* err);
+int jit_launch(const void* kernel, const PlanDev& p, const AssembleCall& call);
 
 }  // namespace mpcasm

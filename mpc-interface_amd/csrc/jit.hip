@@ -36,9 +36,6 @@
 
 namespace mpcasm {
 
-int g_jit = 0;  // MPCASM_OPT_JIT: 0 automatic (batches >= JIT_MIN_BATCH), 1 always, 2 never
-int g_jit_fetch_runs = FS_MAX;  // MPCASM_OPT_JIT_FETCH_RUNS (test aid): most runs a chunk may have to be fetched by arithmetic
-
 namespace {
 
 #include "jit_embed.inc"  // k_src_resident, k_src_device_prims, k_src_plan_dev, k_src_plan_tables
@@ -406,16 +403,16 @@ namespace {
 // the specialised kernel of this plan on this device, compiled on first use; nullptr when the
 // plan runs on the ahead-of-time kernel (JIT off, batch too small, hiprtc missing, a failure)
 const void* jit_kernel_for(const PlanDev& d, const int32_t* h_itab, int device, int batch,
-                           size_t lds_bytes) {
-  if (t_jit == 2) return nullptr;
-  const bool stamps = (g_phase_mask & 64) != 0;  // the diagnostic build with in-kernel cycle stamps
+                           size_t lds_bytes, int jit, int phase_mask, int fetch_runs) {
+  if (jit == 2) return nullptr;
+  const bool stamps = (phase_mask & 64) != 0;  // the diagnostic build with in-kernel cycle stamps
   // (the phase mask is a constant of the build: the shipped value in every normal process, one
   // more build per value a profiling tool sets)
-  const int phases = stamps ? -1 : g_phase_mask;
-  const FastKey fast{d.itab, stamps ? device + 4096 : device, d.rs_p_direct, phases, g_jit_fetch_runs};
+  const int phases = stamps ? -1 : phase_mask;
+  const FastKey fast{d.itab, stamps ? device + 4096 : device, d.rs_p_direct, phases, fetch_runs};
   // a small launch does not start a compilation, but takes the kernel when it is there already
   // (mpcasm_plan_prepare, or an earlier large launch)
-  const bool may_build = t_jit == 1 || batch >= JIT_MIN_BATCH;
+  const bool may_build = jit == 1 || batch >= JIT_MIN_BATCH;
   JitKernel* slot = nullptr;
   bool mine = false;
   std::string header;
@@ -516,25 +513,22 @@ void jit_forget(const void* itab) {
     it = it->first.itab == itab ? g_fast.erase(it) : std::next(it);
 }
 
-int jit_launch(const void* kernel, const PlanDev& p, const SrcTable& src, const double* params,
-               const double* given, double* P, double* q, double* G, double* h, int batch,
-               int num_cus, int per_cu_limit, int grid_limit, void* work, hipStream_t stream,
-               hipError_t* err) {
+int jit_launch(const void* kernel, const PlanDev& p, const AssembleCall& call) {
   const JitKernel* k = static_cast<const JitKernel*>(kernel);
+  AssembleCall c = call;  // (hipModuleLaunchKernel takes the arguments' addresses as void*)
   int per_cu = k->per_cu;
-  if (per_cu_limit > 0 && per_cu_limit < per_cu) per_cu = per_cu_limit;
-  long grid = (long)num_cus * per_cu;
-  if (grid_limit > 0 && grid_limit < grid) grid = grid_limit;
-  if (grid > batch) grid = batch;
+  if (c.opt.per_cu > 0 && c.opt.per_cu < per_cu) per_cu = c.opt.per_cu;
+  long grid = (long)c.num_cus * per_cu;
+  if (c.opt.grid > 0 && c.opt.grid < grid) grid = c.opt.grid;
+  if (grid > c.batch) grid = c.batch;
   const int32_t* itab = p.itab;
   const double* dtab = p.dtab;
-  SrcTable s = src;
-  int phases = g_phase_mask;
-  unsigned long long* stamps = (g_phase_mask & 64) ? static_cast<unsigned long long*>(work) : nullptr;
-  void* args[] = {&itab, &dtab, &s, &params, &given, &P, &q, &G, &h, &batch, &phases, &stamps};
-  *err = hipModuleLaunchKernel(k->fn, (unsigned)grid, 1, 1, RS_NT, 1, 1, (unsigned)k->lds, stream,
-                               args, nullptr);
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  SrcTable s = c.src;
+  unsigned long long* stamps = (c.opt.phase_mask & 64) ? static_cast<unsigned long long*>(c.work) : nullptr;
+  void* args[] = {&itab, &dtab, &s, &c.params, &c.given, &c.P, &c.q, &c.G, &c.h, &c.batch, &c.opt.phase_mask, &stamps};
+  *c.err = hipModuleLaunchKernel(k->fn, (unsigned)grid, 1, 1, RS_NT, 1, 1, (unsigned)k->lds, c.stream,
+                                 args, nullptr);
+  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
 }  // namespace mpcasm

@@ -1,9 +1,10 @@
-// kernels.h -- internal launch interface between capi.hip and the kernel files.
+// kernels.h -- internal launch interface between capi.hip, dispatch.hip and the kernel files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <vector>
 
 #include "../../include/mpcasm.h"
@@ -35,18 +36,63 @@ struct FillChoice {
 };
 int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillChoice* out);
 
+// ---- mpcasm_assemble: options, route and call record --------------------------------------------------------
+// The process-wide options of mpcasm_set_option (defined in capi.hip, beside the table of their ranges): read and
+// written relaxed, so a launch on one thread may race a mpcasm_set_option on another and sees the old value or
+// the new.  No launch code reads this record: it reads the LaunchOptions of its call.
+struct Options {
+  std::atomic<int> path{0};              // MPCASM_OPT_PATH: 0 best, 1 no persistent kernel, 2 staged only, 3, 4: mpcasm.h
+  std::atomic<int> phase_mask{0xBF};     // MPCASM_OPT_PHASE_MASK: diagnostic (timing-only ablation)
+  std::atomic<int> per_cu{0};            // MPCASM_OPT_RESIDENT_PER_CU: tuning aid, 0 = automatic
+  std::atomic<int> jit{0};               // MPCASM_OPT_JIT: 0 automatic (batches >= JIT_MIN_BATCH), 1 always, 2 never
+  std::atomic<int> p_direct{0};          // MPCASM_OPT_P_DIRECT (read when a plan is created)
+  std::atomic<int> grid{0};              // MPCASM_OPT_RESIDENT_GRID: 0 = every resident workgroup slot
+  std::atomic<int> fetch_runs{FS_MAX};   // MPCASM_OPT_JIT_FETCH_RUNS (test aid): most runs of a chunk fetched by arithmetic
+};
+extern Options g_options;
+// the options in force for ONE launch or its prediction: the plan's own where mpcasm_plan_set_option gave it some,
+// else the process-wide ones (capi.hip launch_options, the only place that says so)
+struct LaunchOptions {
+  int path, jit, per_cu, grid, phase_mask, fetch_runs;
+};
+// dispatch.hip: which kernel family a launch of `batch` instances runs on -- the ONE statement of the order (sweep,
+// persistent, tiled, fused, staged).  Host only, no device call.  `kernel`: MPCASM_KERNEL_* (the persistent kernel
+// as MPCASM_KERNEL_RESIDENT, ahead of time or compiled for the plan); `p_direct`: the persistent kernel's hand-over
+// of P for this batch (resident_p_direct_for; 0 on the sweep kernel); `lds`: dynamic LDS bytes of the persistent
+// or the fused kernel, else 0.  MPCASM_ERR_LIMIT: rows of `given` by index off the persistent kernel, or a plan
+// with generated horizon matrices or CSC results that no kernel takes.
+struct AssembleRoute {
+  int kernel, p_direct;
+  size_t lds;
+};
+int assemble_route(const PlanDev& plan, int batch, const LaunchOptions& opt, bool inputs_aligned, bool indexed,
+                   AssembleRoute* out);
+// what travels unchanged from mpcasm_assemble to the kernel launches.  h_itab / device: the plan's tables on the
+// host and its device, for the per-plan compiled kernel (jit.hip); *err: the runtime's word where MPCASM_ERR_HIP
+// comes back; *kernel: the MPCASM_KERNEL_* actually launched (what mpcasm_plan_last_kernel reports)
+struct AssembleCall {
+  const SrcTable& src;
+  const double *params, *given;
+  double *P, *q, *G, *h;
+  void* work;
+  int batch;
+  hipStream_t stream;
+  int num_cus, device;
+  const int32_t* h_itab;
+  bool indexed;
+  LaunchOptions opt;
+  hipError_t* err;
+  int* kernel;
+};
+int launch_assemble(const PlanDev& plan, const AssembleCall& call);
+
 // assemble.hip
 size_t assemble_workspace_bytes(const PlanDev& p, int batch);
-int launch_assemble_staged(const PlanDev& p, const SrcTable& src, const double* params,
-                           const double* given, double* P, double* q, double* G, double* h,
-                           void* work, int batch, hipStream_t stream, hipError_t* err);
+int launch_assemble_staged(const PlanDev& p, const AssembleCall& call);
 // tiled.hip
 bool tiled_eligible(const PlanDev& p);
 size_t tiled_workspace_bytes(const PlanDev& p, int batch);
-int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h,
-                          void* work, int batch, hipStream_t stream, hipError_t* err,
-                          const int32_t* h_itab);
+int launch_assemble_tiled(const PlanDev& p, const AssembleCall& call);
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* work, int batch,
                       const int32_t* h_itab, SrcTable* eff, hipStream_t stream);
 // (toeplitz_zero_pad, the zeros toeplitz_assemble_kernel keeps in LDS behind the group's table: plan_check.h, beside
@@ -80,9 +126,7 @@ struct SweepChoice {
 };
 int sweep_choose(const PlanDev& p, const int32_t* h_itab, SweepChoice* out);
 int sweep_lines_ahead(int cpt);   // LR: the lines of a step whose words and weights are fetched at once
-int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h, int batch,
-                          hipStream_t stream, hipError_t* err, const int32_t* h_itab);
+int launch_assemble_sweep(const PlanDev& p, const AssembleCall& call);
 // preview.hip
 int launch_preview_direct(const PlanDev& p, const SrcTable& eff, const double* given,
                           const double* optim, double* out, int batch, int num_cus,
@@ -160,9 +204,7 @@ int launch_goal_distance(const double* preview, long long preview_stride, const 
                          double* out, int batch, hipStream_t stream, hipError_t* err);
 // fused.hip
 size_t fused_lds_bytes(const PlanDev& p, int nw);
-int launch_assemble_fused(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h,
-                          int batch, size_t lds_bytes, hipStream_t stream, hipError_t* err);
+int launch_assemble_fused(const PlanDev& p, const AssembleCall& call, size_t lds_bytes);
 // resident.hip
 size_t resident_lds_bytes(const PlanDev& p);
 int resident_choose_p_direct(const PlanDev& p, int option);
@@ -170,20 +212,7 @@ int resident_p_direct_for(const PlanDev& p, int batch);
 // whether this launch's buffers meet the alignment the plan's input loads assume
 bool resident_inputs_aligned(const PlanDev& p, const SrcTable& src, const double* params,
                              const double* given);
-int launch_assemble_resident(const PlanDev& p, const SrcTable& src, const double* params,
-                             const double* given, double* P, double* q, double* G, double* h,
-                             void* work, int batch, size_t lds_bytes, int num_cus,
-                             hipStream_t stream, hipError_t* err);
-// h_itab / device: the plan's tables on the host and its device, for the per-plan compiled
-// kernel (jit.hip); nullptr = ahead-of-time kernels only
-// options in force for the launch the calling thread is making (capi.hip: the plan's own where
-// mpcasm_plan_set_option gave it some, else the process-wide ones of mpcasm_set_option)
-extern thread_local int t_path, t_jit, t_per_cu, t_grid;
-extern thread_local int t_last_kernel;  // MPCASM_KERNEL_*: what launch_assemble launched
-int launch_assemble(const PlanDev& p, const SrcTable& src, const double* params,
-                    const double* given, double* P, double* q, double* G, double* h, void* work,
-                    int batch, int num_cus, hipStream_t stream, hipError_t* err,
-                    const int32_t* h_itab = nullptr, int device = 0, bool indexed = false);
+int launch_assemble_resident(const PlanDev& p, const AssembleCall& call, size_t lds_bytes);
 int launch_preview_matrices(const PlanDev& p, const SrcTable& src, double* PM, int batch,
                             hipStream_t stream, hipError_t* err);
 int launch_box_transform(double* params, long long nparams, int batch, const int32_t* facets,

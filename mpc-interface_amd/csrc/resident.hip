@@ -71,11 +71,6 @@ typedef unsigned long uintptr_t;
 
 namespace mpcasm {
 
-#ifndef __HIPCC_RTC__
-extern int g_phase_mask;  // diagnostic (timing-only ablation), fused.hip
-extern int g_resident_per_cu;  // tuning aid, capi.hip
-#endif
-
 namespace {
 
 constexpr int NT = RS_NT;         // threads of a workgroup
@@ -1592,12 +1587,12 @@ __global__ __launch_bounds__(NT, 4) void resident_assemble_kernel(
 #ifndef __HIPCC_RTC__
 
 template <int JC>
-int launch_jc(const PlanDev& p, const SrcTable& src, const double* params, const double* given,
-              double* P, double* q, double* G, double* h, void* work, int batch, size_t lds_bytes,
-              int num_cus, hipStream_t stream, hipError_t* err) {
+int launch_jc(const PlanDev& p, const AssembleCall& c, size_t lds_bytes) {
+  hipError_t* const err = c.err;
+  const int phase_mask = c.opt.phase_mask;
   // the stamped instantiation exists for the diagnostic option only
   // (the stamped instantiation exists once, with everything compiled in)
-  auto kernel = (g_phase_mask & 64) ? resident_assemble_kernel<JC, true, true>
+  auto kernel = (phase_mask & 64) ? resident_assemble_kernel<JC, true, true>
                 : p.rs_nlti != 0    ? resident_assemble_kernel<JC, false, true>
                                     : resident_assemble_kernel<JC, false, false>;
   // residency of this instantiation at this LDS size: queried once per (instantiation, device,
@@ -1613,7 +1608,7 @@ int launch_jc(const PlanDev& p, const SrcTable& src, const double* params, const
   constexpr int KEPT = 8;
   static thread_local Residency kept[3][KEPT];
   static thread_local int nkept[3] = {0, 0, 0};
-  const int slot = (g_phase_mask & 64) ? 2 : (p.rs_nlti != 0 ? 1 : 0);
+  const int slot = (phase_mask & 64) ? 2 : (p.rs_nlti != 0 ? 1 : 0);
   int device = 0;
   (void)hipGetDevice(&device);  // (the attribute and the occupancy belong to one device)
   int found = -1;
@@ -1635,13 +1630,13 @@ int launch_jc(const PlanDev& p, const SrcTable& src, const double* params, const
   // than there are instances
   int per_cu = found;
   if (per_cu < 1) return MPCASM_ERR_LIMIT;
-  if (t_per_cu > 0 && t_per_cu < per_cu) per_cu = t_per_cu;
-  long grid = (long)num_cus * per_cu;
-  if (t_grid > 0 && t_grid < grid) grid = t_grid;
-  if (grid > batch) grid = batch;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NT), lds_bytes, stream, p, src, params,
-                     given, P, q, G, h, batch, g_phase_mask,
-                     (g_phase_mask & 64) ? static_cast<unsigned long long*>(work) : nullptr);
+  if (c.opt.per_cu > 0 && c.opt.per_cu < per_cu) per_cu = c.opt.per_cu;
+  long grid = (long)c.num_cus * per_cu;
+  if (c.opt.grid > 0 && c.opt.grid < grid) grid = c.opt.grid;
+  if (grid > c.batch) grid = c.batch;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NT), lds_bytes, c.stream, p, c.src, c.params,
+                     c.given, c.P, c.q, c.G, c.h, c.batch, phase_mask,
+                     (phase_mask & 64) ? static_cast<unsigned long long*>(c.work) : nullptr);
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
@@ -1707,17 +1702,12 @@ bool resident_inputs_aligned(const PlanDev& p, const SrcTable& src, const double
   return ok(given, p.ng) && ok(params, p.nparams);
 }
 
-int launch_assemble_resident(const PlanDev& p, const SrcTable& src, const double* params,
-                             const double* given, double* P, double* q, double* G, double* h,
-                             void* work, int batch, size_t lds_bytes, int num_cus,
-                             hipStream_t stream, hipError_t* err) {
-#define MPCASM_RS_ARGS p, src, params, given, P, q, G, h, work, batch, lds_bytes, num_cus, stream, err
-  if (p.rs_jc <= 3) return launch_jc<3>(MPCASM_RS_ARGS);
-  if (p.rs_jc <= 4) return launch_jc<4>(MPCASM_RS_ARGS);
-  if (p.rs_jc <= 5) return launch_jc<5>(MPCASM_RS_ARGS);
-  if (p.rs_jc <= 8) return launch_jc<8>(MPCASM_RS_ARGS);
-  return launch_jc<RS_JC_MAX>(MPCASM_RS_ARGS);
-#undef MPCASM_RS_ARGS
+int launch_assemble_resident(const PlanDev& p, const AssembleCall& call, size_t lds_bytes) {
+  if (p.rs_jc <= 3) return launch_jc<3>(p, call, lds_bytes);
+  if (p.rs_jc <= 4) return launch_jc<4>(p, call, lds_bytes);
+  if (p.rs_jc <= 5) return launch_jc<5>(p, call, lds_bytes);
+  if (p.rs_jc <= 8) return launch_jc<8>(p, call, lds_bytes);
+  return launch_jc<RS_JC_MAX>(p, call, lds_bytes);
 }
 #endif  // !__HIPCC_RTC__
 

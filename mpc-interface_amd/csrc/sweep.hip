@@ -762,14 +762,14 @@ int sweep_choose(const PlanDev& p, const int32_t* h_itab, SweepChoice* out) {
   return MPCASM_OK;
 }
 
-int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h, int batch,
-                          hipStream_t stream, hipError_t* err, const int32_t* h_itab) {
+int launch_assemble_sweep(const PlanDev& p, const AssembleCall& call) {
   SweepChoice c;
-  const int rc = sweep_choose(p, h_itab, &c);
+  const int rc = sweep_choose(p, call.h_itab, &c);
   if (rc != MPCASM_OK) return rc;
   const int per_line = c.per_line, reg_lines = c.reg_lines;
   const size_t lds = c.lds;
+  const SrcTable& src = call.src;
+  hipError_t* const err = call.err;
   const double* A = src.ptr[p.sw_src_a];
   const double* Bm = src.ptr[p.sw_src_b];
   const long long sa = src.stride[p.sw_src_a], sb = src.stride[p.sw_src_b];
@@ -780,8 +780,9 @@ int launch_assemble_sweep(const PlanDev& p, const SrcTable& src, const double* p
       *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));                                   \
       if (*err != hipSuccess) return MPCASM_ERR_HIP;                                                   \
     }                                                                                                  \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(SW_BLOCK), lds, stream, p, A, sa, Bm, sb,   \
-                       params, given, P, q, G, h, batch, per_line, reg_lines);                         \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)call.batch), dim3(SW_BLOCK), lds, call.stream, p, A, sa, \
+                       Bm, sb, call.params, call.given, call.P, call.q, call.G, call.h, call.batch,    \
+                       per_line, reg_lines);                                                           \
     *err = hipGetLastError();                                                                          \
     return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;                                            \
   }

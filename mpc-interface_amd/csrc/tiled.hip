@@ -1735,8 +1735,6 @@ __global__ __launch_bounds__(BLOCK) void shared_qh_kernel(PlanDev p, const doubl
 
 }  // namespace
 
-extern int g_phase_mask;  // fused.hip (MPCASM_OPT_PHASE_MASK)
-
 bool tiled_eligible(const PlanDev& p) { return p.t_ok != 0 && p.no >= T_BLOCK; }
 
 // the shared-model form may run on plans without generated groups and with rows of G in 16-byte pieces
@@ -1883,13 +1881,16 @@ int shared_tg(int weights) {
 }
 
 // The shared-model form, for a launch tiled_choose found to be one
-int launch_shared_form(const PlanDev& p, const SrcTable& eff, const double* params, double* w,
-                       long long stride, double* P, double* q, double* G, double* h, int batch, int nb,
-                       int npairs, int sym, int tg, const int32_t* h_itab, hipStream_t stream, hipError_t* err) {
+int launch_shared_form(const PlanDev& p, const AssembleCall& c, const SrcTable& eff, double* w, long long stride,
+                       int nb, int npairs, int sym, int tg) {
+  double *const P = c.P, *const q = c.q, *const G = c.G, *const h = c.h;
+  const double* const params = c.params;
+  const int batch = c.batch;
+  const hipStream_t stream = c.stream;
   SharedSlots sl;
   size_t qh_lds = 0;
   {
-    const int rc = shared_form_choose(p, eff, h_itab, batch, G != nullptr, w != nullptr, &sl, &qh_lds);
+    const int rc = shared_form_choose(p, eff, c.h_itab, batch, G != nullptr, w != nullptr, &sl, &qh_lds);
     if (rc != MPCASM_OK) return rc;
   }
   const int nrho = p.t_nstage * TK;
@@ -1945,19 +1946,18 @@ int launch_shared_form(const PlanDev& p, const SrcTable& eff, const double* para
     hipLaunchKernelGGL(shared_qh_kernel, dim3((unsigned)ceil_div(batch, SH_QB)), dim3(BLOCK), qh_lds, stream, p,
                        V, params, w, stride, P != nullptr ? q : nullptr,
                        (G != nullptr && p.nc > 0) ? h : nullptr, batch, nrho);
-  *err = hipGetLastError();
-  t_last_kernel = MPCASM_KERNEL_TILED_SHARED;
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  *c.err = hipGetLastError();
+  *c.kernel = MPCASM_KERNEL_TILED_SHARED;
+  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
 template <int KP, int CB>
-int launch_scan_as(const PlanDev& p, const SrcTable& eff, const double* A, long long strideA,
-                   const double* Bm, long long strideB, const double* params, const double* w,
-                   long long stride, double* P, double* q, double* G, double* h, int batch, int dlen,
-                   int whole_lines, int rows_in_lds, size_t lds, const double* given, int fused,
-                   hipStream_t stream, hipError_t* err) {
+int launch_scan_as(const PlanDev& p, const AssembleCall& call, const SrcTable& eff, const double* A,
+                   long long strideA, const double* Bm, long long strideB, const double* w, long long stride,
+                   const TiledChoice& c, const double* given) {
+  hipError_t* const err = call.err;
   auto kernel = toeplitz_scan_kernel<KP, CB>;
-  if (lds > 64 * 1024) {
+  if (c.lds > 64 * 1024) {
     *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
     if (*err != hipSuccess) return MPCASM_ERR_HIP;
   }
@@ -1968,11 +1968,11 @@ int launch_scan_as(const PlanDev& p, const SrcTable& eff, const double* A, long 
     const int v = e ? atoi(e) : SCAN_GROUP;   // (r04: 8 rows per ticket 8.6 ms per 8192 C4 instances, 4: 9.3, 1: 9.7)
     return v < 1 ? 1 : (v > SCAN_GROUP ? SCAN_GROUP : v);
   }();
-  hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(BLOCK), lds, stream, p, eff, A, strideA, Bm, strideB,
-                     params, w, stride, P, q, G, h, batch, dlen, whole_lines, group, rows_in_lds, g_phase_mask,
-                     given, fused);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)call.batch), dim3(BLOCK), c.lds, call.stream, p, eff, A, strideA, Bm,
+                     strideB, call.params, w, stride, call.P, call.q, call.G, call.h, call.batch, c.dlen,
+                     c.whole_lines, group, c.rows_in_lds, call.opt.phase_mask, given, c.fused);
   *err = hipGetLastError();
-  if (*err == hipSuccess) t_last_kernel = MPCASM_KERNEL_TILED_SCAN;
+  if (*err == hipSuccess) *call.kernel = MPCASM_KERNEL_TILED_SCAN;
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
@@ -2012,17 +2012,15 @@ int scan_choose(const PlanDev& p, const int32_t* h_itab, bool fused, bool have_g
 
 // the scan form as tiled_choose picked it.  `src`: the launch's own sources (the group's (A, B) in the slots of
 // its first two), `eff`: with the generated tables in the places of the group's U_j and S (fused: unused, as `w`)
-int launch_scan(const PlanDev& p, const SrcTable& src, const SrcTable& eff, const double* params,
-                const double* w, long long stride, double* P, double* q, double* G, double* h, int batch,
-                const int32_t* h_itab, const TiledChoice& c, const double* given, hipStream_t stream,
-                hipError_t* err) {
-  const int32_t* rec = h_itab + p.off_t_lti;
-  const int32_t* ids = h_itab + p.off_t_lti_ids + rec[TL_IDS];
+int launch_scan(const PlanDev& p, const AssembleCall& call, const SrcTable& eff, const double* w, long long stride,
+                const TiledChoice& c, const double* given) {
+  const SrcTable& src = call.src;
+  const int32_t* rec = call.h_itab + p.off_t_lti;
+  const int32_t* ids = call.h_itab + p.off_t_lti_ids + rec[TL_IDS];
 #define MPCASM_SCAN_CASE(KP, CB)                                                                          \
   if (c.kp == KP && c.cb == CB)                                                                          \
-    return launch_scan_as<KP, CB>(p, eff, src.ptr[ids[0]], src.stride[ids[0]], src.ptr[ids[1]],           \
-                                  src.stride[ids[1]], params, w, stride, P, q, G, h, batch, c.dlen,       \
-                                  c.whole_lines, c.rows_in_lds, c.lds, given, c.fused, stream, err);
+    return launch_scan_as<KP, CB>(p, call, eff, src.ptr[ids[0]], src.stride[ids[0]], src.ptr[ids[1]],     \
+                                  src.stride[ids[1]], w, stride, c, given);
   MPCASM_SCAN_CASE(4, 4)
   MPCASM_SCAN_CASE(8, 4)
   MPCASM_SCAN_CASE(4, 8)
@@ -2123,29 +2121,29 @@ int tiled_choose(const PlanDev& p, const SrcTable& src, const int32_t* h_itab, i
   return MPCASM_OK;
 }
 
-int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* params,
-                          const double* given, double* P, double* q, double* G, double* h,
-                          void* work, int batch, hipStream_t stream, hipError_t* err,
-                          const int32_t* h_itab) {
-  double* w = static_cast<double*>(work);
+int launch_assemble_tiled(const PlanDev& p, const AssembleCall& call) {
+  const SrcTable& src = call.src;
+  const int32_t* const h_itab = call.h_itab;
+  const int batch = call.batch;
+  hipError_t* const err = call.err;
+  double* w = static_cast<double*>(call.work);
   const long long stride = p.t_work;
   TiledChoice c;
   {
-    const int rc = tiled_choose(p, src, h_itab, t_path, batch, P != nullptr, G != nullptr, given != nullptr,
-                                w != nullptr, &c);
+    const int rc = tiled_choose(p, src, h_itab, call.opt.path, batch, call.P != nullptr, call.G != nullptr,
+                                call.given != nullptr, w != nullptr, &c);
     if (rc != MPCASM_OK) return rc;
   }
-  if (c.form == MPCASM_TILED_SCAN && c.fused)
-    return launch_scan(p, src, src, params, nullptr, 0, P, q, G, h, batch, h_itab, c, given, stream, err);
+  if (c.form == MPCASM_TILED_SCAN && c.fused) return launch_scan(p, call, src, nullptr, 0, c, call.given);
   SrcTable eff;
   {
-    const int rc = launch_lti_tables(p, src, w, batch, h_itab, &eff, stream);
+    const int rc = launch_lti_tables(p, src, w, batch, h_itab, &eff, call.stream);
     if (rc != MPCASM_OK) return rc;
   }
   if (p.rtot > 0) {
     const unsigned nrb = ceil_div(p.rtot, BLOCK);
     hipLaunchKernelGGL(compose_d_kernel, dim3(nrb * batch), dim3(BLOCK), (size_t)p.ng * sizeof(double),
-                       stream, p, eff, given, w, stride, (int)nrb);
+                       call.stream, p, eff, call.given, w, stride, (int)nrb);
   }
   const int nb = (int)ceil_div(p.no, T_BLOCK);
   const int sym = p.rs_sym_any;
@@ -2153,26 +2151,24 @@ int launch_assemble_tiled(const PlanDev& p, const SrcTable& src, const double* p
   const unsigned groups = ceil_div((unsigned)batch, 8u);
   switch (c.form) {
     case MPCASM_TILED_SCAN:
-      return launch_scan(p, src, eff, params, w, stride, P, q, G, h, batch, h_itab, c, nullptr, stream, err);
+      return launch_scan(p, call, eff, w, stride, c, nullptr);
     case MPCASM_TILED_TOEPLITZ: {
       const ToeplitzLds x = toeplitz_lds(p, h_itab + p.off_t_lti);
       *err = allow_whole_lds(reinterpret_cast<const void*>(toeplitz_assemble_kernel));
       if (*err != hipSuccess) return MPCASM_ERR_HIP;
-      hipLaunchKernelGGL(toeplitz_assemble_kernel, dim3((unsigned)batch), dim3(BLOCK), c.lds,
-                         stream, p, eff, params, w, stride, P, q, G, h, nb, npairs, sym, batch, x.tbn, x.nzero,
-                         g_phase_mask);
+      hipLaunchKernelGGL(toeplitz_assemble_kernel, dim3((unsigned)batch), dim3(BLOCK), c.lds, call.stream, p, eff,
+                         call.params, w, stride, call.P, call.q, call.G, call.h, nb, npairs, sym, batch, x.tbn,
+                         x.nzero, call.opt.phase_mask);
       *err = hipGetLastError();
       return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
     }
     case MPCASM_TILED_SHARED:
-      return launch_shared_form(p, eff, params, w, stride, P, q, G, h, batch, nb, npairs, sym, c.tg, h_itab,
-                                stream, err);
+      return launch_shared_form(p, call, eff, w, stride, nb, npairs, sym, c.tg);
     default:
       break;
   }
-  t_last_kernel = MPCASM_KERNEL_TILED;
-  hipLaunchKernelGGL(tiled_assemble_kernel, dim3(groups * 8 * (unsigned)npairs), dim3(BLOCK), 0,
-                     stream, p, eff, params, w, stride, P, q, G, h, nb, npairs, sym, batch);
+  hipLaunchKernelGGL(tiled_assemble_kernel, dim3(groups * 8 * (unsigned)npairs), dim3(BLOCK), 0, call.stream, p,
+                     eff, call.params, w, stride, call.P, call.q, call.G, call.h, nb, npairs, sym, batch);
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

@@ -89,6 +89,8 @@ SIGNATURES = {
     "mpcasm_tiled_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
                                           ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_assemble_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t] + [ctypes.c_int] * 4 +
+                              [ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),
@@ -218,6 +220,8 @@ KERNEL_NAMES = {0: "none", 1: "resident_assemble_kernel (persistent, ahead of ti
                 6: "toeplitz_scan_kernel (tiled, scan form: P summed along diagonals)",
                 7: "ltv_sweep_kernel (per-step dynamics, no horizon matrix)",
                 8: "shared_p_kernel / shared_g_kernel (tiled, shared-model form: weighted sums of per-term matrices)"}
+(KERNEL_NONE, KERNEL_RESIDENT, KERNEL_RESIDENT_JIT, KERNEL_FUSED, KERNEL_STAGED, KERNEL_TILED, KERNEL_TILED_SCAN,
+ KERNEL_SWEEP, KERNEL_TILED_SHARED) = range(9)                               # MPCASM_KERNEL_*
 PREVIEW_NONE, PREVIEW_DIRECT, PREVIEW_STAGED, PREVIEW_BLOCKED = range(4)   # out[0] of mpcasm_preview_route
 PREVIEW_ROUTES = {0: "none", 1: "direct", 2: "staged", 3: "blocked"}
 TILED_SCAN, TILED_TOEPLITZ, TILED_SHARED, TILED_GENERAL = range(1, 5)         # out[0] of mpcasm_tiled_route

@@ -961,6 +961,25 @@ def tiled_route(plan, batch, src_stride=None, want=capi.WANT_COST | capi.WANT_CO
     return TiledRoute(*(int(x) for x in out[:11]))
 
 
+AssembleRoute = collections.namedtuple("AssembleRoute", "kernel lds p_direct")
+
+
+def assemble_route(plan, batch, path=0, aligned=True, indexed=False):
+    """Which kernel family ``mpcasm_assemble`` (``indexed``: ``mpcasm_assemble_indexed``) runs ``batch`` instances
+    of ``plan`` on under ``MPCASM_OPT_PATH`` ``path`` (``-1``: the process-wide value), with the launch's inputs
+    aligned for the persistent kernel's 16-byte loads or not -- ``mpcasm_assemble_route``, the launch's own
+    decision, no device needed.  An :class:`AssembleRoute`: ``kernel`` one of ``capi.KERNEL_*`` (the persistent
+    kernel always as ``capi.KERNEL_RESIDENT``, the tiled path as ``capi.KERNEL_TILED``), the dynamic LDS bytes of
+    the persistent or fused kernel, and whether the persistent kernel hands ``P`` over directly at this batch.
+    Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses."""
+    out = (ctypes.c_int32 * 4)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    capi.check(capi.load().mpcasm_assemble_route(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, int(batch), int(path),
+        int(aligned), int(indexed), out), "mpcasm_assemble_route")
+    return AssembleRoute(*(int(x) for x in out[:3]))
+
+
 def rollout_table(plan, records=None, cvec=None, sizes=None):
     """The words of the row table ``mpcasm_ltv_rollout`` and ``mpcasm_ltv_advance`` read for ``plan`` (compiled
     with ``ltv=``), an int32 array -- ``mpcasm_ltv_rollout_compile``, host only, no device needed.  ``records``,
