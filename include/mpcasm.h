@@ -48,8 +48,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
  * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment, for the one that added
  * mpcasm_qp_solve_soft, mpcasm_qp_solve_wide_soft and their two info entries and for the one that added
  * mpcasm_qp_sens, mpcasm_qp_sens_wide and their two info entries and for the one that added mpcasm_assemble_jvp,
- * mpcasm_assemble_vjp and mpcasm_assemble_adjoint_info and for the one that added mpcasm_assemble_route (the
- * project's tests pin
+ * mpcasm_assemble_vjp and mpcasm_assemble_adjoint_info and for the one that added mpcasm_assemble_route and for the one that
+ * added mpcasm_assemble_params_vjp and mpcasm_assemble_params_vjp_info (the project's tests pin
  * the value): a client cannot tell from this number whether
  * those entries are there -- look the symbols up (dlsym) instead. */
 int mpcasm_abi_version(void);
@@ -787,6 +787,43 @@ int mpcasm_assemble_vjp(const mpcasm_plan* plan, const double* const* h_src, con
  * return it (out is zeroed): both take the decision from the same function. */
 int mpcasm_assemble_adjoint_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                                  const int64_t* h_src_stride, int32_t out[4]);
+
+/* The derivative of the assembly with respect to the parameters, matrix-free -----------------------------------
+ * dL/dparams [batch][n_params] for the cotangent of (P, q, G, h) that mpcasm_qp_sens stands for,
+ *   gP = -1/2 (u x' + x u')     gq = -u     gG_R = -(y_R u' + w_R x')     gh = w
+ * from d_x, d_u [batch][no] and d_y, d_w [batch][nc] (y with zeros off the active set; mpcasm_qp_sens writes w so),
+ * without the dense gP, gG, a preview matrix or a row of the workspace in memory.  With V = [V_g | V_o] the
+ * workspace rows (csrc/plan_tables.h), s = 1/2 under GT_FLAG_HALF, t = params[b] and the three row vectors
+ * r_x = V_o x, r_u = V_o u, r_g = V_g given, the result is the sum of
+ *   gterm (a, b, n, wp, dd, ap), not diagonal:  P += w V_o[a]' V_o[b] (GT_FLAG_P),  q += s w V_o[a]' (V_g[dd] given - aim)
+ *     g[wp] += [GT_FLAG_P] (-1/2) sum_k (r_u[a+k] r_x[b+k] + r_x[a+k] r_u[b+k])  -  s sum_k r_u[a+k] (r_g[dd+k] - t[ap])
+ *     g[ap] += s t[wp] sum_k r_u[a+k]
+ *   GT_FLAG_DIAG gterm, column c = GT_AOFF + k, coefficient coef_k:  P[c][c] += w coef^2,  q[c] += -w coef aim
+ *     g[wp] += sum_k coef_k (-coef_k u_c x_c + t[ap] u_c)          g[ap] += t[wp] sum_k coef_k u_c
+ *   limit, line R = LM_OUT0 + l, axis i, row = LX_ROWOFF + (LX_ROWS == 1 ? 0 : l):
+ *   G_R = sum_i arrow_Ri V_o[row],  h_R = extreme_R + sum_i arrow_Ri center_Ri - sum_i arrow_Ri r_g[row]
+ *     g[arrow_Ri]  += -(y_R r_u[row] + w_R r_x[row]) + w_R (t[center_Ri] - r_g[row])
+ *     g[center_Ri] += w_R t[arrow_Ri]                               g[extreme_R] += w_R
+ * (a field of one row is broadcast over the lines: its gradient sums over them).  Every slot is written; one that
+ * no record names is exactly 0.0.  One workgroup-resident pass per instance (csrc/adjoint.hip): every slot is
+ * gathered by the lanes that own it through a parameter index derived from the plan's tables by the first call (a
+ * device allocation and a blocking copy, under the handle's mutex, freed by mpcasm_plan_destroy: make that call
+ * before capturing a graph) -- no floating-point atomics, two calls give identical bits, an instance's row does not
+ * depend on the batch or on its place in it.
+ * plan, h_src, h_src_stride, d_params, d_work as for mpcasm_assemble_vjp.  d_given [batch][ng], NULL when ng == 0.
+ * d_verdict [batch] may be NULL; otherwise an instance whose verdict is not MPCASM_SENS_DONE gets an exactly zero
+ * row and none of its vectors is read.  MPCASM_ERR_ARG: a null operand the plan needs, another device than the
+ * plan's.  MPCASM_ERR_LIMIT: a plan compiled with ltv=[...], or one instance beyond the LDS of a CU.  batch == 0 or
+ * n_params == 0: MPCASM_OK, nothing written. */
+int mpcasm_assemble_params_vjp(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                               const double* d_params, const double* d_given, const double* d_x, const double* d_u,
+                               const double* d_y, const double* d_w, const int32_t* d_verdict, double* d_gparams,
+                               void* d_work, int batch, void* stream);
+/* Needs no device: what mpcasm_assemble_params_vjp launches for these tables; the four words mean what
+ * mpcasm_assemble_adjoint_info's do (out[2]: words of the parameter index).  MPCASM_ERR_LIMIT exactly where the
+ * launch returns it (out is zeroed): both take the decision from the same function. */
+int mpcasm_assemble_params_vjp_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                                    const int64_t* h_src_stride, int32_t out[4]);
 
 /* The loop's warm start  last tick's solution, moved one sample along, as this tick's start ----------------
  * A receding-horizon loop solves, every tick, nearly the QP of the tick before with the horizon moved on by one

@@ -16,6 +16,9 @@
 // result, in an order fixed by the plan alone, through a transposed index (the CSC of E, per rho
 // row its contributions, per column the base variables that cover it) that the host derives from the
 // plan's tables once (adjoint_build_index) and that is kept with the plan handle.
+//
+// Further down, the derivative with respect to the parameters (mpcasm_assemble_params_vjp): the same first two
+// steps three times, then a gather per parameter slot through a parameter index (params_adjoint_build_index).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,6 +47,47 @@ struct AdjointArgs {
   int batch;
 };
 
+// Steps 1 and 2, shared by the two kernels of this unit: the workspace rows applied to a vector over the unknowns
+// (OPT) or over `given`,  y = Bm_in x  (every base row over those columns only), then  r = E y.  `x` and the stream
+// bases are in LDS and visible; `r` is visible to the workgroup on return, `y` is scratch.
+template <bool OPT>
+__device__ __forceinline__ void workspace_rows(const PlanDev& p, const AdjointView& v, const double* const* s_base,
+                                               const double* x, double* y, double* r, int tid) {
+  const int ng = p.ng, rtot = p.rtot, nbrow = p.t_nbrow;
+  const int32_t* brow0 = p.itab + p.off_t_brow0;
+  const int2* cig = reinterpret_cast<const int2*>(p.itab + p.off_t_cig);
+  const int2* cio = reinterpret_cast<const int2*>(p.itab + p.off_t_cio);
+  const int32_t* bcolptr = p.itab + p.off_t_bcolptr;
+  const int32_t* bcols = p.itab + p.off_t_bcols;
+  const int32_t* rowptr = p.itab + p.off_rowptr;
+  const int32_t* entbase = p.itab + p.off_entbase;
+  const int32_t* entk = p.itab + p.off_entk;
+  const double* coef = p.dtab + p.doff_entcoef;
+  const int32_t* rowbase = v.idx + v.rowbase;
+  const int32_t* bsplit = v.idx + v.bsplit;
+  const int in0 = OPT ? ng : 0;
+  for (int t = tid; t < nbrow; t += BLOCK) {
+    const int b = rowbase[t];
+    const int k = t - brow0[b];
+    const int i0 = OPT ? bsplit[b] : bcolptr[b], i1 = OPT ? bcolptr[b + 1] : bsplit[b];
+    const int2* row = OPT ? cio + (size_t)b * p.t_nop - ng : cig + (size_t)b * ng;
+    double acc = 0.0;
+    for (int i = i0; i < i1; ++i) {
+      const int c = bcols[i];
+      const int2 ci = row[c];
+      acc = fma(s_base[(unsigned)ci.y >> 24][(long)ci.x + (long)k * sext24(ci.y)], x[c - in0], acc);
+    }
+    y[t] = acc;
+  }
+  __syncthreads();
+  for (int w = tid; w < rtot; w += BLOCK) {
+    double acc = 0.0;
+    for (int e = rowptr[w]; e < rowptr[w + 1]; ++e) acc = fma(coef[e], y[brow0[entbase[e]] + entk[e]], acc);
+    r[w] = acc;
+  }
+  __syncthreads();
+}
+
 // Dynamic LDS (doubles, every part rounded up to even):
 //   x   [max(ng, no)]  the direction d / the cotangent gq            dead after step 1
 //   gh  [nc]           the cotangent of h (VJP; unused by the JVP, whose dh leaves from registers)
@@ -66,14 +110,7 @@ __global__ __launch_bounds__(BLOCK) void assemble_adjoint_kernel(PlanDev p, SrcT
   const int32_t* brow0 = p.itab + p.off_t_brow0;
   const int2* cig = reinterpret_cast<const int2*>(p.itab + p.off_t_cig);
   const int2* cio = reinterpret_cast<const int2*>(p.itab + p.off_t_cio);
-  const int32_t* bcolptr = p.itab + p.off_t_bcolptr;
-  const int32_t* bcols = p.itab + p.off_t_bcols;
-  const int32_t* rowptr = p.itab + p.off_rowptr;
-  const int32_t* entbase = p.itab + p.off_entbase;
-  const int32_t* entk = p.itab + p.off_entk;
   const double* coef = p.dtab + p.doff_entcoef;
-  const int32_t* rowbase = v.idx + v.rowbase;
-  const int32_t* bsplit = v.idx + v.bsplit;
   const int32_t* et_ptr = v.idx + v.et_ptr;
   const int2* et_ent = reinterpret_cast<const int2*>(v.idx + v.et_ent);
   const int32_t* rc_ptr = v.idx + (VJP ? v.rv_ptr : v.rj_ptr);
@@ -81,7 +118,7 @@ __global__ __launch_bounds__(BLOCK) void assemble_adjoint_kernel(PlanDev p, SrcT
   const int32_t* cb_ptr = v.idx + v.cb_ptr;
   const int32_t* cb_ent = v.idx + v.cb_ent;
   // the columns the direction comes in on and the columns the result goes out on
-  const int nin = VJP ? no : ng, in0 = VJP ? ng : 0;
+  const int nin = VJP ? no : ng;
   const int nout = VJP ? ng : no, out0 = VJP ? 0 : ng;
   const bool has_x = VJP ? a.in_x != nullptr : true;          // (VJP: gq given)
   const bool has_h = VJP ? a.in_h != nullptr : a.out_h != nullptr;
@@ -103,28 +140,7 @@ __global__ __launch_bounds__(BLOCK) void assemble_adjoint_kernel(PlanDev p, SrcT
     __syncthreads();
     // 1. y = Bm_in x: every base row over the columns of the direction only
     // 2. r = E y
-    if (has_x) {
-      for (int t = tid; t < nbrow; t += BLOCK) {
-        const int b = rowbase[t];
-        const int k = t - brow0[b];
-        const int i0 = VJP ? bsplit[b] : bcolptr[b], i1 = VJP ? bcolptr[b + 1] : bsplit[b];
-        const int2* row = VJP ? cio + (size_t)b * p.t_nop - ng : cig + (size_t)b * ng;
-        double acc = 0.0;
-        for (int i = i0; i < i1; ++i) {
-          const int c = bcols[i];
-          const int2 ci = row[c];
-          acc = fma(s_base[(unsigned)ci.y >> 24][(long)ci.x + (long)k * sext24(ci.y)], x[c - in0], acc);
-        }
-        y[t] = acc;
-      }
-      __syncthreads();
-      for (int w = tid; w < rtot; w += BLOCK) {
-        double acc = 0.0;
-        for (int e = rowptr[w]; e < rowptr[w + 1]; ++e) acc = fma(coef[e], y[brow0[entbase[e]] + entk[e]], acc);
-        r[w] = acc;
-      }
-      __syncthreads();
-    }
+    if (has_x) workspace_rows<VJP>(p, v, s_base, x, y, r, tid);
     // 3. (JVP) dh_R = - sum over axes arrow_Ri r[row_i(R)]
     if (!VJP && has_h) {
       const int32_t* rowlimit = p.itab + p.off_rowlimit;
@@ -191,6 +207,134 @@ __global__ __launch_bounds__(BLOCK) void assemble_adjoint_kernel(PlanDev p, SrcT
         for (int off = lanes >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, lanes);
         if (l == 0 && c < nout) o[c] = acc;
       }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the derivative with respect to the parameters (mpcasm_assemble_params_vjp) --------------------------------
+// P, q, G, h are sums of outer products of workspace rows times a parameter, and the cotangent that a solve's
+// sensitivity stands for is of rank two:  gP = -1/2 (u x' + x u'),  gq = -u,  gG_R = -(y_R u' + w_R x'),  gh = w.
+// So the gradient of every parameter is a short sum of products of entries of three row vectors
+//   r_x = V_o x,   r_u = V_o u,   r_g = V_g given                        (steps 1 and 2 above, three times)
+// and neither the dense cotangents nor a row of V are ever formed.  Step 3 gathers: the group of lanes that owns a
+// parameter slot walks the slot's records (ParamsView), each lane a strided share of a record's rows, then a
+// butterfly over the group -- an order fixed by the plan alone.
+struct ParamsAdjointArgs {
+  const double* params;     // [batch][nparams]
+  const double* given;      // [batch][ng] or nullptr (ng == 0)
+  const double *x, *u;      // [batch][no]
+  const double *y, *w;      // [batch][nc]: y zero off the active set
+  const int32_t* verdict;   // [batch] or nullptr: an instance that is not MPCASM_SENS_DONE gets a zero row
+  double* gparams;          // [batch][nparams]
+  int batch;
+};
+
+// Dynamic LDS (doubles, every part rounded up to even):
+//   x, u [no] each | given [ng] | y, w [nc] each | base rows (scratch of steps 1, 2) | r_x, r_u, r_g [RTOT] each |
+//   stream bases [NSTREAM]
+__global__ __launch_bounds__(BLOCK) void assemble_params_adjoint_kernel(PlanDev p, SrcTable src, AdjointView v,
+                                                                        ParamsView pv, ParamsAdjointArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int tid = threadIdx.x;
+  const int ng = p.ng, no = p.no, nc = p.nc, rtot = p.rtot, np = p.nparams;
+  double* x = lds + pv.o_x;
+  double* u = lds + pv.o_u;
+  double* g = lds + pv.o_g;
+  double* yy = lds + pv.o_y;
+  double* ww = lds + pv.o_w;
+  double* yb = lds + pv.o_yb;
+  double* rx = lds + pv.o_rx;
+  double* ru = lds + pv.o_ru;
+  double* rg = lds + pv.o_rg;
+  const double** s_base = reinterpret_cast<const double**>(lds + pv.o_bases);
+  const int32_t* sl_ptr = pv.idx + pv.sl_ptr;
+  const int4* sl_rec = reinterpret_cast<const int4*>(pv.idx + pv.sl_rec);
+  const int lanes = pv.lanes, groups = BLOCK / lanes;
+  const int grp = tid / lanes, l = tid - grp * lanes;
+
+  for (long inst = blockIdx.x; inst < a.batch; inst += gridDim.x) {
+    double* o = a.gparams + inst * np;
+    if (a.verdict && a.verdict[inst] != MPCASM_SENS_DONE) {   // (none of its vectors is read: they may hold NaN)
+      for (int s = tid; s < np; s += BLOCK) o[s] = 0.0;
+      continue;
+    }
+    const double* pb = a.params + inst * np;
+    for (int c = tid; c < no; c += BLOCK) x[c] = a.x[inst * no + c], u[c] = a.u[inst * no + c];
+    for (int c = tid; c < ng; c += BLOCK) g[c] = a.given[inst * ng + c];
+    for (int R = tid; R < nc; R += BLOCK) yy[R] = a.y[inst * nc + R], ww[R] = a.w[inst * nc + R];
+    if (tid < NSTREAM) {
+      const double* b = p.dtab;
+      if (tid < T_SID_CONST && tid < p.nsrc) b = src.ptr[tid] + inst * src.stride[tid];
+      s_base[tid] = b;
+    }
+    __syncthreads();
+    // 1., 2. the three row vectors
+    workspace_rows<true>(p, v, s_base, x, yb, rx, tid);
+    workspace_rows<true>(p, v, s_base, u, yb, ru, tid);
+    if (ng) {
+      workspace_rows<false>(p, v, s_base, g, yb, rg, tid);
+    } else {
+      for (int w = tid; w < rtot; w += BLOCK) rg[w] = 0.0;
+      __syncthreads();
+    }
+    // 3. the gather: a record is two int4, (kind | flags, rows, f0, f1), (f2, f3, f4, f5)
+    for (int s0 = 0; s0 < np; s0 += groups) {
+      const int slot = s0 + grp;
+      double acc = 0.0;
+      if (slot < np) {
+        for (int e = sl_ptr[slot]; e < sl_ptr[slot + 1]; ++e) {
+          const int4 h0 = sl_rec[2 * e], h1 = sl_rec[2 * e + 1];
+          const int n = h0.y;
+          const double s = (h0.x & PA_HALF) ? 0.5 : 1.0;
+          switch (h0.x & PA_KIND_MASK) {
+            case PA_GT_WEIGHT: {   // rows a = f0, b = f1 (under PA_P), d rows f2, the aim's slot f3
+              const int ra = h0.z, rb = h0.w, rd = h1.x;
+              const double aim = pb[h1.y];
+              const bool hess = (h0.x & PA_P) != 0;
+              for (int k = l; k < n; k += lanes) {
+                double t = 0.0;
+                if (hess) t = -0.5 * fma(ru[ra + k], rx[rb + k], rx[ra + k] * ru[rb + k]);
+                acc += fma(-s * ru[ra + k], rg[rd + k] - aim, t);
+              }
+            } break;
+            case PA_GT_AIM: {      // rows a = f0, the weight's slot f1
+              double part = 0.0;
+              for (int k = l; k < n; k += lanes) part += ru[h0.z + k];
+              acc = fma(s * pb[h0.w], part, acc);
+            } break;
+            case PA_DIAG_WEIGHT: { // first column f0, coefficients at dtab[f1], the aim's slot f2
+              const double* cf = p.dtab + h0.w;
+              const double aim = pb[h1.x];
+              for (int k = l; k < n; k += lanes) {
+                const int c = h0.z + k;
+                acc = fma(cf[k] * u[c], fma(-cf[k], x[c], aim), acc);
+              }
+            } break;
+            case PA_DIAG_AIM: {    // first column f0, coefficients at dtab[f1], the weight's slot f2
+              const double* cf = p.dtab + h0.w;
+              double part = 0.0;
+              for (int k = l; k < n; k += lanes) part = fma(cf[k], u[h0.z + k], part);
+              acc = fma(pb[h1.x], part, acc);
+            } break;
+            case PA_LIMIT_ARROW: { // lines from R = f0, workspace rows f1 + k f2, the centre's slots f3 + k f4
+              for (int k = l; k < n; k += lanes) {
+                const int R = h0.z + k, row = h0.w + k * h1.x;
+                const double t = -fma(yy[R], ru[row], ww[R] * rx[row]);
+                acc += fma(ww[R], pb[h1.y + k * h1.z] - rg[row], t);
+              }
+            } break;
+            case PA_LIMIT_CENTER:  // lines from R = f0, the arrow's slots f1 + k f2
+              for (int k = l; k < n; k += lanes) acc = fma(ww[h0.z + k], pb[h0.w + k * h1.x], acc);
+              break;
+            default:               // PA_LIMIT_EXTREME: lines from R = f0
+              for (int k = l; k < n; k += lanes) acc += ww[h0.z + k];
+              break;
+          }
+        }
+      }
+      for (int off = lanes >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, lanes);
+      if (l == 0 && slot < np) o[slot] = acc;
     }
     __syncthreads();
   }
@@ -351,6 +495,124 @@ int launch_assemble_adjoint(const PlanDev& p, const SrcTable& eff, const Adjoint
   if (vjp)
     return launch_with_lds(assemble_adjoint_kernel<true>, grid, BLOCK, index.lds, stream, err, p, eff, index.view, a);
   return launch_with_lds(assemble_adjoint_kernel<false>, grid, BLOCK, index.lds, stream, err, p, eff, index.view, a);
+}
+
+// The parameter index of a plan and the geometry of mpcasm_assemble_params_vjp's launch -- the one function both the
+// launch and mpcasm_assemble_params_vjp_info decide with.  Per parameter slot its records in a fixed order: the
+// gterms in the plan's order, then the limits by line and axis.  A record covers the rows of one gterm or the lines
+// of one limit axis that the slot is read on (one line where the field has a row per line, all of them where its one
+// row is broadcast).  Every row and slot stored is checked again here (MPCASM_ERR_PLAN); MPCASM_ERR_LIMIT: one
+// instance beyond the LDS a workgroup can have.  `p` has passed adjoint_build_index (the kernel reads its rowbase
+// and bsplit).
+int params_adjoint_build_index(const PlanDev& p, const int32_t* h, ParamsIndex* out) {
+  if (p.sw_ok || !p.t_ci_ok) return MPCASM_ERR_LIMIT;
+  const int ng = p.ng, no = p.no, nc = p.nc, rtot = p.rtot, np = p.nparams;
+  std::vector<std::vector<int32_t>> recs(np);
+  // (n slots from s0 on, `step` apart, step >= 0)
+  const auto slot_ok = [np](long s0, long n, long step) { return s0 >= 0 && s0 < np && s0 + (n - 1) * step < np; };
+  const auto rows_ok = [rtot](long r0, long n) { return r0 >= 0 && n >= 0 && r0 + n <= rtot; };
+  const auto put = [&recs](int slot, int32_t kind, int n, int f0, int f1 = 0, int f2 = 0, int f3 = 0, int f4 = 0) {
+    for (int32_t word : {kind, (int32_t)n, (int32_t)f0, (int32_t)f1, (int32_t)f2, (int32_t)f3, (int32_t)f4, 0})
+      recs[slot].push_back(word);
+  };
+  for (int g = 0; g < p.ngterm; ++g) {
+    const int32_t* rec = h + p.off_gterm + g * GT_WORDS;
+    const int a = rec[GT_AOFF], b = rec[GT_BOFF], n = rec[GT_NROWS], wp = rec[GT_WPARAM], ap = rec[GT_AIMPARAM];
+    if (n < 0 || !slot_ok(wp, 1, 0) || !slot_ok(ap, 1, 0)) return MPCASM_ERR_PLAN;
+    if (rec[GT_FLAGS] & GT_FLAG_DIAG) {
+      if (a < 0 || a + n > no || b < 0 || b + n > h[H_NDIAGCOEF]) return MPCASM_ERR_PLAN;
+      put(wp, PA_DIAG_WEIGHT, n, a, p.doff_diagcoef + b, ap);
+      put(ap, PA_DIAG_AIM, n, a, p.doff_diagcoef + b, wp);
+      continue;
+    }
+    const int dd = rec[GT_DOFF];
+    const bool hess = (rec[GT_FLAGS] & GT_FLAG_P) != 0;
+    if (!rows_ok(a, n) || !rows_ok(dd, n) || (hess && !rows_ok(b, n))) return MPCASM_ERR_PLAN;
+    const int32_t flags = ((rec[GT_FLAGS] & GT_FLAG_HALF) ? PA_HALF : 0) | (hess ? PA_P : 0);
+    put(wp, PA_GT_WEIGHT | flags, n, a, hess ? b : 0, dd, ap);
+    put(ap, PA_GT_AIM | flags, n, a, wp);
+  }
+  for (int li = 0; li < p.nlimit; ++li) {
+    const int32_t* lm = h + p.off_limit + li * LM_WORDS;
+    const int naxes = lm[LM_NAXES], nr = lm[LM_NROWS], out0 = lm[LM_OUT0];
+    if (out0 < 0 || nr < 0 || out0 + nr > nc || naxes < 0 || lm[LM_LAX0] < 0 || lm[LM_LAX0] + naxes > p.nlax)
+      return MPCASM_ERR_PLAN;
+    const bool a1 = lm[LM_ARROW_ROWS] == 1, c1 = lm[LM_CENTER_ROWS] == 1, e1 = lm[LM_EXTREME_ROWS] == 1;
+    if ((!a1 && lm[LM_ARROW_ROWS] != nr) || (!c1 && lm[LM_CENTER_ROWS] != nr) || (!e1 && lm[LM_EXTREME_ROWS] != nr))
+      return MPCASM_ERR_PLAN;
+    if (nr == 0) continue;
+    // a line's slot of a field: first + (one row ? 0 : line) * step + axis
+    const int astep = a1 ? 0 : naxes, cstep = c1 ? 0 : naxes;
+    if (!slot_ok(lm[LM_EXTREME_P], nr, e1 ? 0 : 1)) return MPCASM_ERR_PLAN;
+    for (int ax = 0; ax < naxes; ++ax)
+      if (!slot_ok(lm[LM_ARROW_P] + ax, nr, astep) || !slot_ok(lm[LM_CENTER_P] + ax, nr, cstep)) return MPCASM_ERR_PLAN;
+    // by line, then by axis: a field of one row takes all the lines in its one record, at line 0's place
+    for (int i = 0; i < nr; ++i) {
+      for (int ax = 0; ax < naxes; ++ax) {
+        const int32_t* lx = h + p.off_lax + (lm[LM_LAX0] + ax) * LX_WORDS;
+        const int rstep = lx[LX_ROWS] == 1 ? 0 : 1;
+        if (lx[LX_ROWOFF] < 0 || lx[LX_ROWOFF] + (long)(nr - 1) * rstep >= rtot) return MPCASM_ERR_PLAN;
+        const int arrow0 = lm[LM_ARROW_P] + ax, center0 = lm[LM_CENTER_P] + ax;
+        if (a1 ? i == 0 : true) {
+          const int first = a1 ? 0 : i, n = a1 ? nr : 1;
+          put(arrow0 + first * astep, PA_LIMIT_ARROW, n, out0 + first, lx[LX_ROWOFF] + first * rstep, rstep,
+              center0 + first * cstep, cstep);
+        }
+        if (c1 ? i == 0 : true) {
+          const int first = c1 ? 0 : i, n = c1 ? nr : 1;
+          put(center0 + first * cstep, PA_LIMIT_CENTER, n, out0 + first, arrow0 + first * astep, astep);
+        }
+      }
+      if (e1 ? i == 0 : true) {
+        const int first = e1 ? 0 : i, n = e1 ? nr : 1;
+        put(lm[LM_EXTREME_P] + (e1 ? 0 : first), PA_LIMIT_EXTREME, n, out0 + first);
+      }
+    }
+  }
+  std::vector<int32_t>& w = out->words;
+  w.clear();
+  ParamsView& v = out->view;
+  v = ParamsView{};
+  v.sl_ptr = 0;
+  w.resize((size_t)np + 1, 0);
+  size_t nrec = 0;
+  for (int s = 0; s < np; ++s) w[s] = (int32_t)nrec, nrec += recs[s].size() / PA_REC_WORDS;
+  w[np] = (int32_t)nrec;
+  while (w.size() & 3) w.push_back(0);   // (int4 reads)
+  v.sl_rec = (int)w.size();
+  for (int s = 0; s < np; ++s) w.insert(w.end(), recs[s].begin(), recs[s].end());
+  // lanes per slot: as many as keep the workgroup busy in one round -- fixed by the plan, never by the batch
+  v.lanes = 1;
+  while (v.lanes < 64 && 2 * v.lanes * std::max(np, 1) <= BLOCK) v.lanes *= 2;
+  v.o_x = 0;
+  v.o_u = v.o_x + even(no);
+  v.o_g = v.o_u + even(no);
+  v.o_y = v.o_g + even(ng);
+  v.o_w = v.o_y + even(nc);
+  v.o_yb = v.o_w + even(nc);
+  v.o_rx = v.o_yb + even(p.t_nbrow);
+  v.o_ru = v.o_rx + even(rtot);
+  v.o_rg = v.o_ru + even(rtot);
+  v.o_bases = v.o_rg + even(rtot);
+  out->lds = ((size_t)v.o_bases + NSTREAM) * sizeof(double);
+  if (out->lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
+  out->per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)CU_LDS_BYTES / out->lds));
+  return MPCASM_OK;
+}
+
+// `adj`: the plan's transposed index on the device (its rowbase and bsplit are read); `index.view.idx`: the device
+// copy of the parameter index
+int launch_assemble_params_adjoint(const PlanDev& p, const SrcTable& eff, const AdjointIndex& adj,
+                                   const ParamsIndex& index, const double* params, const double* given,
+                                   const double* x, const double* u, const double* y, const double* w,
+                                   const int32_t* verdict, double* gparams, int batch, int num_cus,
+                                   hipStream_t stream, hipError_t* err) {
+  *err = hipSuccess;
+  if (batch == 0 || p.nparams == 0) return MPCASM_OK;
+  const unsigned grid = (unsigned)std::min<long>(batch, (long)num_cus * index.per_cu);
+  const ParamsAdjointArgs a{params, given, x, u, y, w, verdict, gparams, batch};
+  return launch_with_lds(assemble_params_adjoint_kernel, grid, BLOCK, index.lds, stream, err, p, eff, adj.view,
+                         index.view, a);
 }
 
 }  // namespace mpcasm

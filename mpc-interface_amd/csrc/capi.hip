@@ -47,6 +47,11 @@ struct mpcasm_plan {
   mutable int adj_hip = 0;
   mutable AdjointIndex adj;
   mutable int32_t* d_adj = nullptr;
+  // ... and the parameter index of mpcasm_assemble_params_vjp, kept the same way under the same mutex
+  mutable int par_rc = 1;
+  mutable int par_hip = 0;
+  mutable ParamsIndex par;
+  mutable int32_t* d_par = nullptr;
 };
 
 namespace {
@@ -347,6 +352,7 @@ int mpcasm_plan_destroy(mpcasm_plan* plan) {
   if (!plan) return MPCASM_OK;
   jit_forget(plan->d_itab);
   if (plan->d_adj) (void)hipFree(plan->d_adj);
+  if (plan->d_par) (void)hipFree(plan->d_par);
   hipError_t e1 = hipFree(plan->d_itab);
   hipError_t e2 = hipFree(plan->d_dtab);
   delete plan;
@@ -581,23 +587,113 @@ int mpcasm_assemble_vjp(const mpcasm_plan* plan, const double* const* h_src, con
                       stream);
 }
 
+namespace {
+// the plan's parameter index on its device: built and uploaded once, by whichever call comes first
+int plan_params_index(const mpcasm_plan* plan, const ParamsIndex** out) {
+  std::lock_guard<std::mutex> lock(plan->adj_mutex);
+  if (plan->par_rc == 1) {
+    plan->par_rc = params_adjoint_build_index(plan->dev, plan->h_itab.data(), &plan->par);
+    if (plan->par_rc == MPCASM_OK) {
+      const size_t bytes = std::max<size_t>(plan->par.words.size(), 1) * sizeof(int32_t);
+      hipError_t e = hipMalloc(&plan->d_par, bytes);
+      if (e == hipSuccess && !plan->par.words.empty())
+        e = hipMemcpy(plan->d_par, plan->par.words.data(), plan->par.words.size() * sizeof(int32_t),
+                      hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        if (plan->d_par) (void)hipFree(plan->d_par);
+        plan->d_par = nullptr;
+        plan->par_rc = MPCASM_ERR_HIP;
+        plan->par_hip = (int)e;
+      }
+      plan->par.view.idx = plan->d_par;
+    }
+  }
+  if (plan->par_rc == MPCASM_ERR_HIP) g_last_hip = plan->par_hip;
+  *out = &plan->par;
+  return plan->par_rc;
+}
+
+// what the two info entries of the assembly's derivative share: the tables checked and viewed, the strides taken,
+// what the pre-pass of a plan compiled with lti= refuses
+int adjoint_info_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                      const int64_t* h_src_stride, PlanDev* d) {
+  const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, d);
+  if (rc != MPCASM_OK) return rc;
+  if (d->nsrc && !h_src_stride) return MPCASM_ERR_ARG;
+  if (d->sw_ok) return MPCASM_ERR_LIMIT;
+  SrcTable src, eff;
+  memset(&src, 0, sizeof src);
+  for (int s = 0; s < d->nsrc; ++s) {
+    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
+    src.stride[s] = h_src_stride[s];
+  }
+  return lti_effective_sources(*d, src, nullptr, h_itab, &eff);
+}
+}  // namespace
+
+int mpcasm_assemble_params_vjp(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
+                               const double* d_params, const double* d_given, const double* d_x, const double* d_u,
+                               const double* d_y, const double* d_w, const int32_t* d_verdict, double* d_gparams,
+                               void* d_work, int batch, void* stream) {
+  if (!plan || batch < 0) return MPCASM_ERR_ARG;
+  const PlanDev& d = plan->dev;
+  if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (per-step dynamics: no S, U; the adjoint is the sweep's backward recursion)
+  if (batch == 0 || d.nparams == 0) return MPCASM_OK;
+  if ((d.nsrc && (!h_src || !h_src_stride)) || !d_params || !d_gparams || (d.ng && !d_given) ||
+      (d.no && (!d_x || !d_u)) || (d.nc && (!d_y || !d_w)))
+    return MPCASM_ERR_ARG;
+  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
+  {  // the plan's tables live on the device it was created on
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  }
+  SrcTable src, eff;
+  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  rc = lti_effective_sources(d, src, static_cast<double*>(d_work), plan->h_itab.data(), &eff);
+  if (rc != MPCASM_OK) return rc;
+  const AdjointIndex* adj;
+  rc = plan_adjoint_index(plan, &adj);
+  if (rc != MPCASM_OK) return rc;
+  const ParamsIndex* index;
+  rc = plan_params_index(plan, &index);
+  if (rc != MPCASM_OK) return rc;
+  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), batch, plan->h_itab.data(), &eff,
+                         static_cast<hipStream_t>(stream));
+  if (rc != MPCASM_OK) return rc;
+  hipError_t err;
+  rc = launch_assemble_params_adjoint(d, eff, *adj, *index, d_params, d_given, d_x, d_u, d_y, d_w, d_verdict,
+                                      d_gparams, batch, plan->num_cus, static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
+}
+
+int mpcasm_assemble_params_vjp_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                                    const int64_t* h_src_stride, int32_t out[4]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  memset(out, 0, 4 * sizeof(int32_t));
+  PlanDev d;
+  const int rc = adjoint_info_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d);
+  if (rc != MPCASM_OK) return rc;
+  AdjointIndex adj;
+  const int first = adjoint_build_index(d, h_itab, &adj);
+  if (first != MPCASM_OK) return first;
+  ParamsIndex index;
+  const int built = params_adjoint_build_index(d, h_itab, &index);
+  if (built != MPCASM_OK) return built;
+  out[0] = (int32_t)index.lds;
+  out[1] = index.lds > 64 * 1024;
+  out[2] = (int32_t)index.words.size();
+  out[3] = index.per_cu;
+  return MPCASM_OK;
+}
+
 int mpcasm_assemble_adjoint_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                                  const int64_t* h_src_stride, int32_t out[4]) {
   if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
   memset(out, 0, 4 * sizeof(int32_t));
   PlanDev d;
-  const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
+  const int rc = adjoint_info_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d);
   if (rc != MPCASM_OK) return rc;
-  if (d.nsrc && !h_src_stride) return MPCASM_ERR_ARG;
-  if (d.sw_ok) return MPCASM_ERR_LIMIT;
-  SrcTable src, eff;
-  memset(&src, 0, sizeof src);
-  for (int s = 0; s < d.nsrc; ++s) {
-    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
-    src.stride[s] = h_src_stride[s];
-  }
-  const int lti = lti_effective_sources(d, src, nullptr, h_itab, &eff);
-  if (lti != MPCASM_OK) return lti;
   AdjointIndex index;
   const int built = adjoint_build_index(d, h_itab, &index);
   if (built != MPCASM_OK) return built;

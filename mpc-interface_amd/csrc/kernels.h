@@ -171,6 +171,37 @@ int adjoint_build_index(const PlanDev& p, const int32_t* h_itab, AdjointIndex* o
 int launch_assemble_adjoint(const PlanDev& p, const SrcTable& eff, const AdjointIndex& index, bool vjp,
                             const double* params, const double* in_x, const double* in_h, double* out_x,
                             double* out_h, int batch, int num_cus, hipStream_t stream, hipError_t* err);
+// ... and with respect to the parameters (mpcasm_assemble_params_vjp).  The parameter index: per slot
+// [SL_PTR[s], SL_PTR[s + 1]) its records of PA_REC_WORDS words -- kind | flags, rows n, f0 .. f4, 0:
+//   PA_GT_WEIGHT    rows a, rows b (PA_P), rows d, the aim's slot      the weight of a non-diagonal gterm
+//   PA_GT_AIM       rows a, the weight's slot                          its aim
+//   PA_DIAG_WEIGHT  first column, coefficients (dtab), the aim's slot  the weight of a GT_FLAG_DIAG gterm
+//   PA_DIAG_AIM     first column, coefficients (dtab), the weight's slot
+//   PA_LIMIT_ARROW  first line R, workspace row and its step per line, the centre's slot and its step per line
+//   PA_LIMIT_CENTER first line R, the arrow's slot and its step per line
+//   PA_LIMIT_EXTREME first line R
+// (PA_HALF: s = 1/2; PA_P: the gterm has a Hessian part).  o_*: doubles into the kernel's dynamic LDS.
+enum { PA_GT_WEIGHT = 0, PA_GT_AIM, PA_DIAG_WEIGHT, PA_DIAG_AIM, PA_LIMIT_ARROW, PA_LIMIT_CENTER, PA_LIMIT_EXTREME };
+constexpr int32_t PA_KIND_MASK = 15, PA_HALF = 1 << 4, PA_P = 1 << 5;
+constexpr int PA_REC_WORDS = 8;
+struct ParamsView {
+  const int32_t* idx;
+  int sl_ptr, sl_rec;     // [NPARAMS + 1], [..][PA_REC_WORDS] (16-byte aligned)
+  int lanes;              // threads per parameter slot
+  int o_x, o_u, o_g, o_y, o_w, o_yb, o_rx, o_ru, o_rg, o_bases;
+};
+struct ParamsIndex {
+  std::vector<int32_t> words;
+  ParamsView view;
+  size_t lds;
+  int per_cu;
+};
+int params_adjoint_build_index(const PlanDev& p, const int32_t* h_itab, ParamsIndex* out);
+int launch_assemble_params_adjoint(const PlanDev& p, const SrcTable& eff, const AdjointIndex& adj,
+                                   const ParamsIndex& index, const double* params, const double* given,
+                                   const double* x, const double* u, const double* y, const double* w,
+                                   const int32_t* verdict, double* gparams, int batch, int num_cus,
+                                   hipStream_t stream, hipError_t* err);
 // rollout.hip: the preview rows and the next given of a plan compiled as ltv, by the forward recursion
 int compile_rollout_table(const PlanDev& p, const int32_t* recs, int nrec, const double* cvec, int ncvec,
                           std::vector<int32_t>* out);

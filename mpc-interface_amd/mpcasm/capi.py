@@ -120,6 +120,11 @@ SIGNATURES = {
                             [_void_p] * 5 + [ctypes.c_int, _void_p]),
     "mpcasm_assemble_adjoint_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
                                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_assemble_params_vjp": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64)] +
+                                   [_void_p] * 9 + [ctypes.c_int, _void_p]),
+    "mpcasm_assemble_params_vjp_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
+                                                       ctypes.POINTER(ctypes.c_int64),
+                                                       ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_goal_distance": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
                                             _void_p, ctypes.c_int, ctypes.c_int, _void_p,
                                             ctypes.c_int, _void_p]),

@@ -15,9 +15,14 @@ Nobody holds ``P, q, G, h`` as leaves: they come out of the assembly.  ``P`` and
 and ``h`` are affine in it, and :meth:`mpcasm.engine.Assembler.given_vjp` / :meth:`~mpcasm.engine.Assembler.given_jvp`
 apply that Jacobian and its transpose matrix-free on the device ("The derivative of the assembly").
 :func:`mpc_solve_diff` chains the two -- ``given.grad`` of a loss on the solution of the MPC's QP -- and
-:func:`tangent` is the tangential predictor ``x*(given + d) ~ x* + dx``.  Still open: gradients with respect to
-``params`` (weights, aims, arrows: they need the contraction with ``dL/dP``, ``dL/dG``), plans compiled with ``ltv=``
-(the sweep's backward recursion) and the fleet's wiring.
+:func:`tangent` is the tangential predictor ``x*(given + d) ~ x* + dx``.
+
+The parameters (weights, aims, arrows, centres, extremes) enter ``P, q, G, h`` as factors of outer products of
+workspace rows, and ``dL/dP``, ``dL/dG`` are of rank two, so ``params.grad`` is a short sum of products of three row
+vectors: :meth:`mpcasm.engine.Assembler.params_vjp` (``mpcasm_assemble_params_vjp``) gathers it on the device without
+the dense gradients, and ``mpc_solve_diff(asm, given, params=p)`` chains it behind the same sensitivity solve.  Still
+open: plans compiled with ``ltv=`` (the sweep's backward recursion), the fleet's wiring (the ``params_map`` chain to
+``commands.grad``) and a JVP in params.
 """
 from . import engine
 from .engine import require_device
@@ -40,6 +45,8 @@ class QpDiffSolution:
     sol = property(lambda self: self._outcome.sol)
     verdict = property(lambda self: self._outcome.verdict)
     lres = property(lambda self: self._outcome.lres)
+    # (mpc_solve_diff with params=: the bool (B, nc) active set its params_vjp ran with; None otherwise)
+    active = property(lambda self: getattr(self._outcome, "active", None))
 
 
 class _Outcome:
@@ -105,11 +112,11 @@ def solve_qp_diff(P, q, G, h, wide=False, **solve_kw):
 class _MpcOutcome(_Outcome):
     """:class:`_Outcome` of :func:`mpc_solve_diff`, with the assembled ``P, G, h`` the solve ran on (plain tensors of
     the call's own: :func:`tangent` reads them)."""
-    __slots__ = ("P", "G", "h")
+    __slots__ = ("P", "G", "h", "active")
 
     def __init__(self):
         super().__init__()
-        self.P = self.G = self.h = None
+        self.P = self.G = self.h = self.active = None
 
 
 _MPC_FUNCTION = None
@@ -152,7 +159,54 @@ def _mpc_function(torch):
     return _MPC_FUNCTION
 
 
-def mpc_solve_diff(asm, given, wide=False, **solve_kw):
+_MPC_PARAMS_FUNCTION = None
+
+
+def _mpc_params_function(torch):
+    global _MPC_PARAMS_FUNCTION
+    if _MPC_PARAMS_FUNCTION is not None:
+        return _MPC_PARAMS_FUNCTION
+
+    class MpcSolveDiffParams(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, given, params, asm, outcome, wide, solve_kw):
+            g, p = given.detach().contiguous(), params.detach().contiguous()
+            f = dict(dtype=torch.float64, device=asm.device)
+            B, no, nc = asm.batch, asm.no, asm.nc
+            out = (torch.empty((B, no, no), **f), torch.empty((B, no), **f), torch.empty((B, nc, no), **f),
+                   torch.empty((B, nc), **f))
+            asm.assemble(g, out=out, stream=solve_kw.get("stream"), params=p)
+            P, q, G, h = out
+            solve = engine.solve_qp_wide if wide else engine.solve_qp
+            sol = solve(P, q, G, h, polish=True, **solve_kw)
+            outcome.sol, outcome.P, outcome.G, outcome.h = sol, P, G, h
+            ctx.asm, ctx.outcome, ctx.wide, ctx.stream = asm, outcome, wide, solve_kw.get("stream")
+            ctx.save_for_backward(P, G, h, sol.x, sol.y, sol.z, sol.status, g, p)
+            return sol.x.view_as(sol.x), sol.y.view_as(sol.y)
+
+        @staticmethod
+        def backward(ctx, gx, gy):
+            P, G, h, x, y, z, status, g, p = ctx.saved_tensors
+            sens = engine.qp_sensitivity_wide if ctx.wide else engine.qp_sensitivity
+            s = sens(P, G, h, (x, y, z), gx.contiguous(), gy.contiguous(), status=status, want_P=False, want_G=False,
+                     stream=ctx.stream)
+            ctx.outcome.verdict, ctx.outcome.lres = s.verdict, s.lres
+            need_given, need_params = ctx.needs_input_grad[:2]
+            ggiven = gparams = None
+            if need_given:
+                ggiven = ctx.asm.given_vjp(-s.u, s.w, stream=ctx.stream, params=p)
+            if need_params:
+                # the polish's own test of a row: one subtraction and one compare, so the same set bit for bit
+                ctx.outcome.active = (h - z) < y
+                gparams = ctx.asm.params_vjp(g, x, s.u, y, s.w, verdict=s.verdict, active=ctx.outcome.active,
+                                             params=p, stream=ctx.stream)
+            return ggiven, gparams, None, None, None, None
+
+    _MPC_PARAMS_FUNCTION = MpcSolveDiffParams
+    return _MPC_PARAMS_FUNCTION
+
+
+def mpc_solve_diff(asm, given, params=None, wide=False, **solve_kw):
     """The MPC's QP as a differentiable function of ``given (B, ng)``, ``B = asm.batch``: ``asm.assemble(given)``, then
     ``solve_qp(P, q, G, h, polish=True, **solve_kw)`` (``wide``: ``solve_qp_wide``).  A :class:`QpDiffSolution`, as
     :func:`solve_qp_diff` returns it; ``backward`` through its ``x`` and ``y`` makes one
@@ -160,7 +214,14 @@ def mpc_solve_diff(asm, given, wide=False, **solve_kw):
     ``given``) and one :meth:`mpcasm.engine.Assembler.given_vjp` ``(-u, w)``.  An instance that is not ``SENS_DONE``
     gets an exactly zero row of ``given.grad``.  The assembler's :attr:`~mpcasm.engine.Assembler.params` and sources
     are read by both passes and not differentiated.  ``soft=`` and ``polish=`` are refused as in
-    :func:`solve_qp_diff`."""
+    :func:`solve_qp_diff`.
+
+    ``params``: a ``(B, n_params)`` float64 tensor to assemble with instead of ``asm.params`` (as
+    ``asm.assemble(params=)``); ``given`` and ``params`` get gradients where they require them.  ``backward`` is then
+    the same sensitivity solve followed by ``given_vjp`` and / or one :meth:`mpcasm.engine.Assembler.params_vjp`
+    ``(given, x, u, y, w)`` with ``verdict`` the solve's and ``active = (h - z) < y`` (kept as ``.active`` of the
+    result): no dense ``dL/dP``, ``dL/dG`` there either.  :meth:`mpcasm.engine.Assembler.param_grad` reads a field
+    out of ``params.grad``."""
     if solve_kw.get("soft") is not None:
         raise ValueError("mpc_solve_diff with soft=: the active-set model of the derivative is the hard problem's")
     if "polish" in solve_kw:
@@ -171,7 +232,13 @@ def mpc_solve_diff(asm, given, wide=False, **solve_kw):
             and tuple(given.shape) == (asm.batch, asm.ng)):
         raise ValueError("given: a float64 tensor of shape (%d, %d) on %s" % (asm.batch, asm.ng, asm.device))
     outcome = _MpcOutcome()
-    x, y = _mpc_function(torch).apply(given, asm, outcome, bool(wide), solve_kw)
+    if params is None:
+        x, y = _mpc_function(torch).apply(given, asm, outcome, bool(wide), solve_kw)
+        return QpDiffSolution(x, y, outcome)
+    if not (torch.is_tensor(params) and params.dtype == torch.float64 and params.device == asm.device
+            and tuple(params.shape) == tuple(asm.params.shape)):
+        raise ValueError("params: a float64 tensor of shape %s on %s" % (tuple(asm.params.shape), asm.device))
+    x, y = _mpc_params_function(torch).apply(given, params, asm, outcome, bool(wide), solve_kw)
     return QpDiffSolution(x, y, outcome)
 
 

@@ -923,6 +923,20 @@ def adjoint_info(plan, src_stride=None):
     return AdjointInfo(*(int(x) for x in out))
 
 
+def params_adjoint_info(plan, src_stride=None):
+    """:func:`adjoint_info` for ``mpcasm_assemble_params_vjp`` (``mpcasm_assemble_params_vjp_info``): an
+    :class:`AdjointInfo` whose ``index_words`` are the words of the parameter index.  Raises
+    :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the plan."""
+    out = (ctypes.c_int32 * 4)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    n = len(plan.sources)
+    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
+    capi.check(capi.load().mpcasm_assemble_params_vjp_info(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides, out),
+        "mpcasm_assemble_params_vjp_info")
+    return AdjointInfo(*(int(x) for x in out))
+
+
 def sweep_route(plan):
     """What ``mpcasm_assemble`` launches for a plan with a dynamics compiled as ``ltv`` -- ``mpcasm_sweep_route``,
     the launch's own decision, no device needed: ``(CPT, specialised, PAIR, per_line, reg_lines, LR, LDS bytes,
@@ -1652,13 +1666,25 @@ class Assembler:
             checked.append(t)
         return n, checked
 
-    def given_jvp(self, d, out=None, count=None, stream=None):
+    def _params_arg(self, params):
+        """:attr:`params`, or the caller's tensor in their place, checked as :meth:`assemble` checks it."""
+        if params is None:
+            return self.params
+        torch = self._torch
+        if (not torch.is_tensor(params) or tuple(params.shape) != tuple(self.params.shape)
+                or params.dtype != torch.float64 or params.device != self.device or not params.is_contiguous()):
+            raise ValueError("params: a contiguous float64 tensor of shape %s on %s"
+                             % (tuple(self.params.shape), self.device))
+        return params
+
+    def given_jvp(self, d, out=None, count=None, stream=None, params=None):
         """How ``q`` and ``h`` of :meth:`assemble` move along a change ``d (B, ng)`` of ``given``:
         ``(dq (B, no), dh (B, nc))``, ``dq = J_q d``, ``dh = -cMg d`` (``mpcasm_assemble_jvp``; ``P`` and ``G`` do not
         depend on ``given``), with this assembler's :attr:`params` and sources, matrix-free.  ``out``: the caller's
-        ``(dq, dh)``, a None among them skipped (not both).  Refused (``ERR_LIMIT``) for a plan compiled with
-        ``ltv=``."""
+        ``(dq, dh)``, a None among them skipped (not both).  ``params``: a ``(B, n_params)`` tensor to read instead of
+        :attr:`params`, as :meth:`assemble` takes it.  Refused (``ERR_LIMIT``) for a plan compiled with ``ltv=``."""
         torch = self._torch
+        prm = self._params_arg(params)
         n, (d,) = self._adjoint_args("given_jvp", count, [(d, self.ng, "d")])
         if out is None:
             f = dict(dtype=torch.float64, device=self.device)
@@ -1675,16 +1701,17 @@ class Assembler:
         work = self._workspace()
         with torch.cuda.device(self.device):
             rc = capi.load().mpcasm_assemble_jvp(
-                self._handle, ptrs, strides, self.params.data_ptr(), ptr(d), ptr(dq), ptr(dh), work.data_ptr(), n,
+                self._handle, ptrs, strides, prm.data_ptr(), ptr(d), ptr(dq), ptr(dh), work.data_ptr(), n,
                 _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_assemble_jvp")
         return dq, dh
 
-    def given_vjp(self, gq, gh, out=None, count=None, stream=None):
+    def given_vjp(self, gq, gh, out=None, count=None, stream=None, params=None):
         """``dL/dgiven (B, ng) = J_q' gq + J_h' gh`` for ``gq = dL/dq (B, no)`` and ``gh = dL/dh (B, nc)`` of
         :meth:`assemble`'s ``q`` and ``h`` (``mpcasm_assemble_vjp``); a None cotangent is zero (not both).  Same
         conventions as :meth:`given_jvp`; ``out``: the caller's ``ggiven``."""
         torch = self._torch
+        prm = self._params_arg(params)
         if gq is None and gh is None:
             raise ValueError("given_vjp: neither gq nor gh")
         n, (gq, gh) = self._adjoint_args("given_vjp", count, [(gq, self.no, "gq"), (gh, self.nc, "gh")])
@@ -1700,7 +1727,7 @@ class Assembler:
         work = self._workspace()
         with torch.cuda.device(self.device):
             rc = capi.load().mpcasm_assemble_vjp(
-                self._handle, ptrs, strides, self.params.data_ptr(), ptr(gq), ptr(gh), out.data_ptr(),
+                self._handle, ptrs, strides, prm.data_ptr(), ptr(gq), ptr(gh), out.data_ptr(),
                 work.data_ptr(), n, _stream_handle(torch, stream))
         capi.check(rc, "mpcasm_assemble_vjp")
         return out
@@ -1708,6 +1735,57 @@ class Assembler:
     def adjoint_info(self):
         """What :meth:`given_jvp` / :meth:`given_vjp` launch with the sources bound now (:func:`adjoint_info`)."""
         return adjoint_info(self.plan, self._src_stride)
+
+    # ---- ... and with respect to the parameters ---------------------------------------------------
+    def params_vjp(self, given, x, u, y, w, verdict=None, active=None, params=None, out=None, count=None,
+                   stream=None):
+        """``dL/dparams (B, n_params)`` of a loss on the solution of the assembled QP (``mpcasm_assemble_params_vjp``):
+        ``x (B, no)`` the solution, ``y (B, nc)`` its multipliers, ``u (B, no)`` and ``w (B, nc)`` what
+        :func:`qp_sensitivity` returned for the loss -- they stand for ``dL/dP = -1/2 (u x' + x u')``, ``dL/dq = -u``,
+        ``dL/dG_R = -(y_R u' + w_R x')``, ``dL/dh = w``, which are never formed.  ``y`` must be zero off the active set:
+        ``active`` (bool ``(B, nc)``) zeroes it there first.  ``verdict`` (int32 ``(B,)``, the sensitivity's): an
+        instance that is not ``SENS_DONE`` gets an exactly zero row and none of its vectors is read.  ``given``: the
+        ``(B, ng)`` the QP was assembled from; ``params``: the tensor it was assembled with (default :attr:`params`).
+        Use :meth:`param_grad` to read a field's gradient.  Refused (``ERR_LIMIT``) for a plan compiled with
+        ``ltv=``."""
+        torch = self._torch
+        prm = self._params_arg(params)
+        if active is not None:
+            y = _as_device(torch, y, self.device).reshape(-1, self.nc) * active.reshape(-1, self.nc)
+        n, (given, x, u, y, w) = self._adjoint_args("params_vjp", count, [
+            (given, self.ng, "given"), (x, self.no, "x"), (u, self.no, "u"), (y, self.nc, "y"), (w, self.nc, "w")])
+        for t, name, need in ((given, "given", self.ng), (x, "x", self.no), (u, "u", self.no), (y, "y", self.nc),
+                              (w, "w", self.nc)):
+            if need and t is None:
+                raise ValueError("params_vjp: %s is missing" % name)
+        if verdict is not None and (not torch.is_tensor(verdict) or verdict.dtype != torch.int32
+                                    or verdict.device != self.device or not verdict.is_contiguous()
+                                    or verdict.numel() < n):
+            raise ValueError("params_vjp: verdict is a contiguous int32 tensor of %d entries on %s" % (n, self.device))
+        width = int(self.params.shape[1])
+        if out is None:
+            out = torch.zeros((self.batch, width), dtype=torch.float64, device=self.device)
+        else:
+            _checked_out(torch, out, (n, width), self.device, "params_vjp")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptrs, strides = self._src_args()
+        work = self._workspace()
+        with torch.cuda.device(self.device):
+            rc = capi.load().mpcasm_assemble_params_vjp(
+                self._handle, ptrs, strides, prm.data_ptr(), ptr(given), ptr(x), ptr(u), ptr(y), ptr(w),
+                ptr(verdict), out.data_ptr(), work.data_ptr(), n, _stream_handle(torch, stream))
+        capi.check(rc, "mpcasm_assemble_params_vjp")
+        return out
+
+    def params_adjoint_info(self):
+        """What :meth:`params_vjp` launches with the sources bound now (:func:`params_adjoint_info`)."""
+        return params_adjoint_info(self.plan, self._src_stride)
+
+    def param_grad(self, gparams, kind, name, field):
+        """The ``(B, rows, cols)`` view of one field in a ``(B, n_params)`` gradient that :meth:`params_vjp` made --
+        the counterpart of :meth:`set_param`, through ``plan.param_slots``."""
+        sl, (rows, cols) = self.param_slice(kind, name, field)
+        return gparams[:, sl].view(gparams.shape[0], rows, cols)
 
     def preview_route(self, goals=False):
         """What :meth:`preview_rows` -- with ``goals`` (the Formulation whose goals :meth:`goal_terms` lists)
