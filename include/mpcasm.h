@@ -42,7 +42,8 @@ typedef struct mpcasm_plan mpcasm_plan; /* opaque, immutable after creation */
 
 /* library / device ------------------------------------------------------- */
 
-/* ABI version of this header (major*1000 + minor).  1003 also for the build that added mpcasm_ltv_rollout_compile,
+/* ABI version of this header (major*1000 + minor).  1004 with mpcasm_staged_route.  1003 for the build that added
+ * mpcasm_qp_solve_wide and also for the build that added mpcasm_ltv_rollout_compile,
  * mpcasm_ltv_rollout and mpcasm_ltv_advance, for the one that added mpcasm_qp_polish_wide and
  * mpcasm_qp_polish_wide_info, for the one that added mpcasm_ltv_rollout_info, for the one that added mpcasm_ltv_lqr,
  * mpcasm_ltv_close and mpcasm_ltv_true_inputs, for the one that added mpcasm_ltv_augment, for the one that added
@@ -410,6 +411,26 @@ int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
  * that fits no kernel.  MPCASM_ERR_ARG: batch < 1, `path` out of range, a flag that is not 0 or 1. */
 int mpcasm_assemble_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int batch,
                           int path, int inputs_aligned, int indexed, int32_t out[4]);
+
+/* Diagnostic, needs no device: what the staged pipeline (MPCASM_KERNEL_STAGED: the route of MPCASM_OPT_PATH 2 and
+ * of every plan no other kernel takes) launches for `batch` instances of the plan whose tables these are, with the
+ * cost half (P, q), the constraint half (G, h) or both wanted (want_* = 0 / 1, not both 0).  The launch takes the
+ * decision from the same function.  out[0]: the Hessian's kernel, MPCASM_STAGED_* (NONE: the cost is not wanted or
+ * the plan has no unknown; BLOCK: a wavefront per 32 x 32 block of [P | q]; GEMM, from 128 unknowns on: a workgroup
+ * per 128 x 128 block of P and the gradient by a kernel of its own); out[1]: MPCASM_STAGED_SYM (GEMM: only the
+ * block pairs bi <= bj are computed, mirrored on store) | MPCASM_STAGED_WHOLE_LINES (rows of G leave as whole
+ * cache lines: 16 | unknowns, constraints wanted) | the most axes of a limit << 8; out[2], out[3]: GEMM: the
+ * blocks of 128 columns and the block pairs per instance; BLOCK: the block rows and block columns (q is the
+ * column behind P); out[4] .. out[7]: workgroups of the composition of the workspace, the Hessian kernel, the
+ * gradient kernel (GEMM only) and the constraint kernel (0: not launched).  Which branch of the constraint kernel
+ * a row takes follows from the parity of the unknowns and that row's own axes (up to two: the unrolled pairs).
+ * MPCASM_ERR_LIMIT exactly where the launch returns it, before anything is launched (out is zeroed): constraints
+ * wanted and a limit of more than 8 axes.  MPCASM_ERR_ARG for a plan the pipeline cannot run (a dynamics
+ * compiled as ltv, lti=[...], results in CSC form). */
+enum { MPCASM_STAGED_NONE = 0, MPCASM_STAGED_BLOCK = 1, MPCASM_STAGED_GEMM = 2 };
+enum { MPCASM_STAGED_SYM = 1, MPCASM_STAGED_WHOLE_LINES = 2 };
+int mpcasm_staged_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int want_cost,
+                        int want_constraints, int batch, int32_t out[8]);
 
 /* f3  sparse hand-off -----------------------------------------------------------
  * Replaces the dense -> CSC conversion in front of the solver call of the walking loop

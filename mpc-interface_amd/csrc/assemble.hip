@@ -585,37 +585,63 @@ size_t assemble_workspace_bytes(const PlanDev& p, int batch) {
   return (size_t)batch * p.rtot * p.ldv * sizeof(double);
 }
 
+// the one decision, taken by launch_assemble_staged and reported by mpcasm_staged_route: which kernels the
+// pipeline launches for the wanted halves and over which grids.  Host only.  The refusal (a limit of more axes
+// than K4 holds in LDS) comes before the first launch.
+int staged_choose(const PlanDev& p, bool want_cost, bool want_constraints, int batch, StagedChoice* out) {
+  *out = StagedChoice{};
+  const bool limits = want_constraints && p.nc > 0;
+  if (limits && p.max_axes > K4_AXMAX) return MPCASM_ERR_LIMIT;
+  out->max_axes = p.max_axes;
+  if (p.rtot > 0) {
+    out->k2_nrb = (int)ceil_div(p.rtot, WAVES * K2_ROWS_PER_WAVE);
+    out->grid_k2 = (unsigned)out->k2_nrb * batch;
+  }
+  if (want_cost && p.no >= GB) {
+    // wide problems: P by the LDS-tiled GEMM, q by the gradient kernel
+    out->hessian = MPCASM_STAGED_GEMM;
+    out->nb = (int)ceil_div(p.no, GB);
+    out->sym = p.rs_sym_any;
+    out->npairs = out->sym ? out->nb * (out->nb + 1) / 2 : out->nb * out->nb;
+    out->grid_k3 = (unsigned)out->npairs * batch;
+    out->ncb = (int)ceil_div(p.no, 64);
+    out->grid_gradient = (unsigned)out->ncb * batch;
+  } else if (want_cost && p.no > 0) {
+    out->hessian = MPCASM_STAGED_BLOCK;
+    out->nbr = (int)ceil_div(p.no, 32);
+    out->nbc = (int)ceil_div(p.no + 1, 32);
+    out->k3_nrb = (int)ceil_div((unsigned)(out->nbr * out->nbc), WAVES);
+    out->grid_k3 = (unsigned)out->k3_nrb * batch;
+  }
+  if (limits) {
+    out->k4_nrb = (int)ceil_div(p.nc, K4_ROWS);
+    out->grid_k4 = (unsigned)out->k4_nrb * ceil_div((unsigned)batch, 8u) * 8;
+    out->whole_lines = (p.no & 15) == 0;   // (what the unrolled pair branch of K4 reads off no itself)
+  }
+  return MPCASM_OK;
+}
+
 int launch_assemble_staged(const PlanDev& p, const AssembleCall& c) {
   double* V = static_cast<double*>(c.work);
   const int batch = c.batch;
-  if (p.rtot > 0) {
-    const unsigned nrb = ceil_div(p.rtot, WAVES * K2_ROWS_PER_WAVE);
-    hipLaunchKernelGGL(compose_rowsets_kernel, dim3(nrb * batch), dim3(BLOCK), 0, c.stream, p, c.src,
-                       c.given, V, (int)nrb);
+  StagedChoice s;
+  const int rc = staged_choose(p, c.P != nullptr, c.G != nullptr, batch, &s);
+  if (rc != MPCASM_OK) return rc;
+  if (s.grid_k2)
+    hipLaunchKernelGGL(compose_rowsets_kernel, dim3(s.grid_k2), dim3(BLOCK), 0, c.stream, p, c.src, c.given, V,
+                       s.k2_nrb);
+  if (s.hessian == MPCASM_STAGED_GEMM) {
+    hipLaunchKernelGGL(hessian_gemm_kernel, dim3(s.grid_k3), dim3(BLOCK), 0, c.stream, p, c.params, V, c.P, s.nb,
+                       s.npairs, s.sym);
+    hipLaunchKernelGGL(gradient_kernel, dim3(s.grid_gradient), dim3(BLOCK), 0, c.stream, p, c.params, V, c.q,
+                       s.ncb);
+  } else if (s.hessian == MPCASM_STAGED_BLOCK) {
+    hipLaunchKernelGGL(hessian_kernel, dim3(s.grid_k3), dim3(BLOCK), 0, c.stream, p, c.params, V, c.P, c.q,
+                       s.k3_nrb, 0);
   }
-  if (c.P && p.no >= GB) {
-    // wide problems: P by the LDS-tiled GEMM, q by the block kernel on its own column
-    const int nb = (int)ceil_div(p.no, GB);
-    const int sym = p.rs_sym_any;
-    const int npairs = sym ? nb * (nb + 1) / 2 : nb * nb;
-    hipLaunchKernelGGL(hessian_gemm_kernel, dim3((unsigned)npairs * batch), dim3(BLOCK), 0, c.stream,
-                       p, c.params, V, c.P, nb, npairs, sym);
-    const unsigned ncb = ceil_div(p.no, 64);
-    hipLaunchKernelGGL(gradient_kernel, dim3(ncb * batch), dim3(BLOCK), 0, c.stream, p, c.params, V, c.q,
-                       (int)ncb);
-  } else if (c.P && p.no > 0) {
-    const unsigned nblk = ceil_div(p.no, 32) * ceil_div(p.no + 1, 32);
-    const unsigned nrb = ceil_div(nblk, WAVES);
-    hipLaunchKernelGGL(hessian_kernel, dim3(nrb * batch), dim3(BLOCK), 0, c.stream, p, c.params, V, c.P,
-                       c.q, (int)nrb, 0);
-  }
-  if (c.G && p.nc > 0) {
-    if (p.max_axes > K4_AXMAX) return MPCASM_ERR_LIMIT;
-    const unsigned nrb = ceil_div(p.nc, K4_ROWS);
-    const unsigned groups = ceil_div((unsigned)batch, 8u);
-    hipLaunchKernelGGL(constraints_kernel, dim3(nrb * groups * 8), dim3(BLOCK), 0, c.stream, p, c.params,
-                       V, c.G, c.h, (int)nrb, batch);
-  }
+  if (s.grid_k4)
+    hipLaunchKernelGGL(constraints_kernel, dim3(s.grid_k4), dim3(BLOCK), 0, c.stream, p, c.params, V, c.G, c.h,
+                       s.k4_nrb, batch);
   *c.err = hipGetLastError();
   return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

@@ -146,7 +146,7 @@ int host_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t
 
 extern "C" {
 
-int mpcasm_abi_version(void) { return 1003; }
+int mpcasm_abi_version(void) { return 1004; }
 
 int mpcasm_device_count(void) {
   int n = 0;
@@ -801,6 +801,36 @@ int mpcasm_assemble_route(const int32_t* h_itab, size_t n_itab, const double* h_
   out[0] = r.kernel;
   out[1] = (int32_t)r.lds;
   out[2] = r.p_direct;
+  return MPCASM_OK;
+}
+
+int mpcasm_staged_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int want_cost,
+                        int want_constraints, int batch, int32_t out[8]) {
+  if (!h_itab || (n_dtab && !h_dtab) || !out || batch < 1 || (want_cost != 0 && want_cost != 1) ||
+      (want_constraints != 0 && want_constraints != 1) || (!want_cost && !want_constraints))
+    return MPCASM_ERR_ARG;
+  memset(out, 0, 8 * sizeof(int32_t));
+  PlanDev d;
+  int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
+  if (rc != MPCASM_OK) return rc;
+  // a plan the pipeline can run at all: what MPCASM_OPT_PATH 2 reaches it with (not a dynamics compiled as ltv,
+  // no horizon matrices generated from (A, B), no CSC results)
+  LaunchOptions opt = launch_options(nullptr);
+  opt.path = 2;
+  AssembleRoute r;
+  if (assemble_route(d, batch, opt, false, false, &r) != MPCASM_OK || r.kernel != MPCASM_KERNEL_STAGED)
+    return MPCASM_ERR_ARG;
+  StagedChoice c;
+  rc = staged_choose(d, want_cost != 0, want_constraints != 0, batch, &c);
+  if (rc != MPCASM_OK) return rc;
+  out[0] = c.hessian;
+  out[1] = (c.sym ? MPCASM_STAGED_SYM : 0) | (c.whole_lines ? MPCASM_STAGED_WHOLE_LINES : 0) | (c.max_axes << 8);
+  out[2] = c.hessian == MPCASM_STAGED_GEMM ? c.nb : c.nbr;
+  out[3] = c.hessian == MPCASM_STAGED_GEMM ? c.npairs : c.nbc;
+  out[4] = (int32_t)c.grid_k2;
+  out[5] = (int32_t)c.grid_k3;
+  out[6] = (int32_t)c.grid_gradient;
+  out[7] = (int32_t)c.grid_k4;
   return MPCASM_OK;
 }
 

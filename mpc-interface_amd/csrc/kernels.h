@@ -89,6 +89,20 @@ int launch_assemble(const PlanDev& plan, const AssembleCall& call);
 // assemble.hip
 size_t assemble_workspace_bytes(const PlanDev& p, int batch);
 int launch_assemble_staged(const PlanDev& p, const AssembleCall& call);
+// host only: what launch_assemble_staged launches for a plan (mpcasm_staged_route).  `hessian`: MPCASM_STAGED_*
+// (NONE: the cost is not wanted, or no unknown); the GEMM (128 unknowns or more): `sym` (only the block pairs
+// bi <= bj, mirrored on store), `nb` blocks of 128 columns, `npairs` workgroups per instance, `ncb` 64-column
+// blocks of the gradient kernel; the block kernel: `nbr` x `nbc` blocks of 32 x 32 of [P | q], `k3_nrb`
+// workgroups per instance; `k2_nrb`, `k4_nrb`: row blocks per instance of K2 and K4; grid_*: workgroups of the
+// four launches (0: not launched; K4's are dealt to the XCDs in groups of eight instances); `whole_lines`: K4's
+// rows are whole cache lines (16 | no); `max_axes`: the most axes of a limit.  Which branch of K4 a row takes
+// follows from that row's own axes and the parity of no.  MPCASM_ERR_LIMIT where nothing is launched.
+struct StagedChoice {
+  int hessian, sym, nb, npairs, ncb, nbr, nbc, whole_lines, max_axes;
+  int k2_nrb, k3_nrb, k4_nrb;
+  unsigned grid_k2, grid_k3, grid_gradient, grid_k4;
+};
+int staged_choose(const PlanDev& p, bool want_cost, bool want_constraints, int batch, StagedChoice* out);
 // tiled.hip
 bool tiled_eligible(const PlanDev& p);
 size_t tiled_workspace_bytes(const PlanDev& p, int batch);

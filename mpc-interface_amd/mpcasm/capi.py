@@ -91,6 +91,8 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_assemble_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t] + [ctypes.c_int] * 4 +
                               [ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_staged_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 +
+                            [ctypes.POINTER(ctypes.c_int32)]),
     "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),
@@ -232,6 +234,9 @@ PREVIEW_ROUTES = {0: "none", 1: "direct", 2: "staged", 3: "blocked"}
 TILED_SCAN, TILED_TOEPLITZ, TILED_SHARED, TILED_GENERAL = range(1, 5)         # out[0] of mpcasm_tiled_route
 TILED_FORMS = {1: "scan", 2: "toeplitz", 3: "shared", 4: "general"}
 TILED_TABLES_NONE, TILED_TABLES_SMALL, TILED_TABLES_SYSTEM = range(3)         # out[8]
+STAGED_NONE, STAGED_BLOCK, STAGED_GEMM = range(3)                             # out[0] of mpcasm_staged_route
+STAGED_FORMS = {0: "none", 1: "block", 2: "gemm"}
+STAGED_SYM, STAGED_WHOLE_LINES = 1, 2                                         # out[1]
 WANT_COST, WANT_CONSTRAINTS = 1, 2
 BOX_RECENTER, BOX_TRANSLATE, BOX_ROTATE, BOX_SCALE, BOX_MARGIN = range(5)
 

@@ -994,6 +994,30 @@ def assemble_route(plan, batch, path=0, aligned=True, indexed=False):
     return AssembleRoute(*(int(x) for x in out[:3]))
 
 
+StagedRoute = collections.namedtuple(
+    "StagedRoute", "hessian sym nb npairs nbr nbc whole_lines max_axes grid_k2 grid_k3 grid_gradient grid_k4")
+
+
+def staged_route(plan, batch, want_cost=True, want_constraints=True):
+    """What the staged pipeline (csrc/assemble.hip; ``MPCASM_OPT_PATH`` 2, and every plan no other kernel takes)
+    launches for ``batch`` instances of ``plan`` with these halves wanted -- ``mpcasm_staged_route``, the launch's
+    own decision, no device needed.  A :class:`StagedRoute`: ``hessian`` one of ``capi.STAGED_*``; ``sym``, ``nb``,
+    ``npairs`` of ``hessian_gemm_kernel`` (128 unknowns or more), or the block rows and columns ``nbr``, ``nbc`` of
+    ``hessian_kernel``; ``whole_lines`` of ``constraints_kernel``; the most axes of a limit; the workgroups of the
+    four launches (0: not launched).  Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch
+    refuses (a limit of more than 8 axes with the constraints wanted), with ``MPCASM_ERR_ARG`` for a plan the
+    pipeline cannot run (``ltv=``, ``lti=``, ``csc=``)."""
+    out = (ctypes.c_int32 * 8)()
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    capi.check(capi.load().mpcasm_staged_route(
+        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, int(bool(want_cost)),
+        int(bool(want_constraints)), int(batch), out), "mpcasm_staged_route")
+    form, flags, a, b, k2, k3, grad, k4 = (int(x) for x in out)
+    gemm = form == capi.STAGED_GEMM
+    return StagedRoute(form, flags & capi.STAGED_SYM, a if gemm else 0, b if gemm else 0, 0 if gemm else a,
+                       0 if gemm else b, (flags & capi.STAGED_WHOLE_LINES) >> 1, flags >> 8, k2, k3, grad, k4)
+
+
 def rollout_table(plan, records=None, cvec=None, sizes=None):
     """The words of the row table ``mpcasm_ltv_rollout`` and ``mpcasm_ltv_advance`` read for ``plan`` (compiled
     with ``ltv=``), an int32 array -- ``mpcasm_ltv_rollout_compile``, host only, no device needed.  ``records``,
@@ -1800,6 +1824,12 @@ class Assembler:
     def sweep_route(self):
         """The instantiation of the sweep kernel :meth:`assemble` launches for this plan (:func:`sweep_route`)."""
         return sweep_route(self.plan)
+
+    def staged_route(self, want_cost=True, want_constraints=True, count=None):
+        """What the staged pipeline launches for this plan where :meth:`assemble` reaches it
+        (:func:`staged_route`)."""
+        return staged_route(self.plan, self.batch if count is None else int(count), want_cost,
+                            want_constraints and bool(self.nc))
 
     def tiled_route(self, want_cost=True, want_constraints=True, count=None):
         """What :meth:`assemble` launches on the tiled path with the sources bound now and this assembler's

@@ -41,7 +41,7 @@ def test_entries_are_declared_exported_and_bound():
     for name in ENTRIES:
         assert name in text and hasattr(lib, name) and name in capi.SIGNATURES
     assert "body.py:266-302" in text and "body.py:236-264" in text and "dh = -cMg d" in text
-    assert capi.load().mpcasm_abi_version() == 1003
+    assert capi.load().mpcasm_abi_version() == 1004
 
 
 def test_the_cases_hold_every_kind_of_record(cpu_api):

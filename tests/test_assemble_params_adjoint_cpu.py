@@ -55,7 +55,7 @@ def test_entries_are_declared_exported_and_bound():
     for formula in ("gP = -1/2 (u x' + x u')", "g[arrow_Ri]  += -(y_R r_u[row] + w_R r_x[row])", "g[extreme_R] += w_R",
                     "g[ap] += s t[wp] sum_k r_u[a+k]"):
         assert formula in text, formula
-    assert capi.load().mpcasm_abi_version() == 1003
+    assert capi.load().mpcasm_abi_version() == 1004
 
 
 def test_the_cases_hold_every_kind_of_record(cpu_api):

@@ -19,6 +19,7 @@ def declared_functions():
 def test_every_declared_symbol_is_exported_and_bound():
     names = declared_functions()
     assert "mpcasm_fill_su" in names and "mpcasm_assemble" in names and "mpcasm_fill_route" in names and len(names) >= 12
+    assert "mpcasm_staged_route" in names
     lib = ctypes.CDLL(capi.LIB_PATH)
     for name in names:
         assert hasattr(lib, name), "%s declared in mpcasm.h but not exported" % name
@@ -28,7 +29,7 @@ def test_every_declared_symbol_is_exported_and_bound():
 
 def test_library_answers_without_a_device():
     lib = capi.load()
-    assert lib.mpcasm_abi_version() >= 1000
+    assert lib.mpcasm_abi_version() == 1004         # (1004: mpcasm_staged_route)
     assert lib.mpcasm_device_count() >= 0
     assert lib.mpcasm_status_string(0) == b"ok"
     assert lib.mpcasm_status_string(-2) == b"malformed plan tables"

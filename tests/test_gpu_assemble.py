@@ -694,8 +694,11 @@ def test_edge_shapes(gpu_api):
 
 
 def test_wide_hessian_with_a_crossed_term(gpu_api):
-    """no >= 128 takes the LDS-tiled GEMM for P; a crossed cost makes P non-symmetric, so
-    every block (not only bi <= bj) has to be computed."""
+    """A crossed cost makes P non-symmetric, so every block pair (not only bi <= bj) has to be computed.  At the
+    default path a plan of 144 unknowns runs on the tiled path (mpcasm_assemble_route: MPCASM_KERNEL_TILED, its
+    general form with sym = 0), not on the staged pipeline's LDS-tiled GEMM this test was written for: that one's
+    all-pairs form is reached where a test forces MPCASM_OPT_PATH 2 (test_gpu_staged_variants.py, the crossed
+    cases, element by element)."""
     form = problems.random_lti(gpu_api, np.random.default_rng(7), nx=4, nu=3, N=48)
     form.incorporate_goal("crossed", gpu_api.Cost("s0", 0.3, aim=[0.1], cross="s2",
                                                   cross_aim=[-0.2]))

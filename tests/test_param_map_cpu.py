@@ -199,4 +199,4 @@ def test_the_symbol_is_bound_and_the_version_stays():
     lib = capi.load()
     assert "mpcasm_params_map" in capi.SIGNATURES and hasattr(lib, "mpcasm_params_map")
     assert (capi.PMAP_SIGNED, capi.PMAP_CONST) == (pm.SIGNED, pm.CONST) == (1, 2)
-    assert lib.mpcasm_abi_version() == 1003
+    assert lib.mpcasm_abi_version() == 1004

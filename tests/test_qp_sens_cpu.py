@@ -343,7 +343,7 @@ def test_the_binding_and_the_python_entry_points():
     for name in ("qp_sensitivity", "qp_sensitivity_wide", "qp_sens_lds_bytes", "qp_sens_wide_info", "qp_vjp", "qp_jvp"):
         assert callable(getattr(engine, name))
     assert callable(diff.solve_qp_diff)
-    assert capi.load().mpcasm_abi_version() == 1003
+    assert capi.load().mpcasm_abi_version() == 1004
     # soft= is refused before anything else is looked at
     with pytest.raises(ValueError):
         diff.solve_qp_diff(None, None, None, None, soft=(1.0, 0.0))

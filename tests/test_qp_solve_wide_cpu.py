@@ -50,7 +50,7 @@ def test_bad_arguments_and_the_lds_path_unchanged():
     assert lib.mpcasm_qp_solve_wide_info(0, 4, ctypes.byref(lds), ctypes.byref(on)) == -1
     assert lib.mpcasm_qp_solve_wide_info(4, -1, ctypes.byref(lds), ctypes.byref(on)) == -1
     assert lib.mpcasm_qp_solve_wide_info(4, 4, None, ctypes.byref(on)) == -1
-    assert lib.mpcasm_abi_version() == 1003
+    assert lib.mpcasm_abi_version() == 1004
     # the LDS path still refuses C3
     with pytest.raises(capi.MpcasmError) as err:
         engine.qp_solve_lds_bytes(96, 196)

@@ -167,7 +167,7 @@ def test_the_header_symbols_are_bound_and_the_strings_unchanged():
     lib = capi.load()
     for name in ("mpcasm_qp_warm_store", "mpcasm_qp_warm_start"):
         assert name in capi.SIGNATURES and hasattr(lib, name)
-    assert lib.mpcasm_abi_version() == 1003
+    assert lib.mpcasm_abi_version() == 1004
     assert lib.mpcasm_status_string(0) == b"ok"
     assert lib.mpcasm_status_string(-1) == lib.mpcasm_status_string(capi.ERR_ARG)
     assert lib.mpcasm_status_string(-2) == b"malformed plan tables"
