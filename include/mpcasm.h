@@ -269,6 +269,9 @@ int mpcasm_plan_last_kernel(const mpcasm_plan* plan);
  * Replaces Formulation.make_preview_matrices   body.py:149-193
  * d_PM [batch][preview_rows][ng+no]: for every definition, in definition
  * order, the rows of [Mg | Mo] (Formulation.PM[var] = (Mg, Mo)).
+ * Like every entry that launches with a plan's tables: MPCASM_ERR_ARG when the
+ * current device is not the one the plan was created on.  (Until the entries
+ * shared that check this one had none and launched there; ABI 1004 as before.)
  */
 int mpcasm_preview_matrices(const mpcasm_plan* plan, const double* const* h_src,
                             const int64_t* h_src_stride, double* d_PM, int batch,

@@ -30,6 +30,49 @@ struct PlanOptions {
   int path = -1, jit = -1, per_cu = -1, grid = -1;
 };
 
+namespace {
+
+thread_local int g_last_hip = 0;
+
+// an index a plan derives from its host tables and keeps on its device (adjoint.hip): built and uploaded once, by
+// whichever call comes first, under the plan's index_mutex -- held across build and upload
+template <class Index>
+struct DeviceIndex {
+  int rc = 1;   // what that attempt returned (1: not tried yet)
+  int hip = 0;  // ... and its hipError_t, published again by every call that meets the failure
+  Index index;
+  int32_t* d_words = nullptr;
+
+  int get(std::mutex& mutex, const PlanDev& dev, const int32_t* h_itab,
+          int (*build)(const PlanDev&, const int32_t*, Index*), const Index** out) {
+    std::lock_guard<std::mutex> lock(mutex);
+    if (rc == 1) {
+      rc = build(dev, h_itab, &index);
+      if (rc == MPCASM_OK) {
+        const size_t bytes = std::max<size_t>(index.words.size(), 1) * sizeof(int32_t);
+        hipError_t e = hipMalloc(&d_words, bytes);
+        if (e == hipSuccess && !index.words.empty())
+          e = hipMemcpy(d_words, index.words.data(), index.words.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+          release();
+          rc = MPCASM_ERR_HIP;
+          hip = (int)e;
+        }
+        index.view.idx = d_words;
+      }
+    }
+    if (rc == MPCASM_ERR_HIP) g_last_hip = hip;
+    *out = &index;
+    return rc;
+  }
+  void release() {
+    if (d_words) (void)hipFree(d_words);
+    d_words = nullptr;
+  }
+};
+
+}  // namespace
+
 struct mpcasm_plan {
   PlanDev dev;
   int32_t* d_itab;
@@ -40,23 +83,13 @@ struct mpcasm_plan {
   PlanOptions opt;
   // mpcasm_plan_last_kernel: what the latest mpcasm_assemble launched (two threads on one plan: the last writer)
   mutable std::atomic<int> last_kernel{0};
-  // the transposed index of mpcasm_assemble_jvp / _vjp (adjoint.hip): derived from h_itab and uploaded by the
-  // first call, under the mutex; adj_rc: what that attempt returned (1: not tried yet)
-  mutable std::mutex adj_mutex;
-  mutable int adj_rc = 1;
-  mutable int adj_hip = 0;
-  mutable AdjointIndex adj;
-  mutable int32_t* d_adj = nullptr;
-  // ... and the parameter index of mpcasm_assemble_params_vjp, kept the same way under the same mutex
-  mutable int par_rc = 1;
-  mutable int par_hip = 0;
-  mutable ParamsIndex par;
-  mutable int32_t* d_par = nullptr;
+  // the transposed index of mpcasm_assemble_jvp / _vjp and the parameter index of mpcasm_assemble_params_vjp
+  mutable std::mutex index_mutex;
+  mutable DeviceIndex<AdjointIndex> adj;
+  mutable DeviceIndex<ParamsIndex> par;
 };
 
 namespace {
-
-thread_local int g_last_hip = 0;
 
 int hip_fail(hipError_t e) {
   g_last_hip = (int)e;
@@ -118,8 +151,22 @@ bool qp_polish_settings_ok(const QpPolish& p) {
   return p.refine_iters >= 0 && p.delta > 0.0 && std::isfinite(p.delta);
 }
 
-int make_src_table(const mpcasm_plan* plan, const double* const* h_src,
-                   const int64_t* h_src_stride, SrcTable* out) {
+bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// ---- what the entries are composed of, each in its own order ------------------------
+// the plan's tables (and its compiled kernels) live on the device it was created on
+bool on_plan_device(const mpcasm_plan* plan) {
+  int current = -1;
+  return hipGetDevice(&current) == hipSuccess && current == plan->device;
+}
+
+// a plan with sources and no table of them (an entry whose OK or LIMIT answers come first asks this early)
+bool sources_missing(const PlanDev& d, const void* h_src, const int64_t* h_src_stride) {
+  return d.nsrc != 0 && (!h_src || !h_src_stride);
+}
+// the sources of a launch: every one there, no stride negative
+int plan_sources(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride, SrcTable* out) {
+  if (sources_missing(plan->dev, h_src, h_src_stride)) return MPCASM_ERR_ARG;
   memset(out, 0, sizeof(*out));
   for (int s = 0; s < plan->dev.nsrc; ++s) {
     if (!h_src[s] || h_src_stride[s] < 0) return MPCASM_ERR_ARG;
@@ -128,9 +175,36 @@ int make_src_table(const mpcasm_plan* plan, const double* const* h_src,
   }
   return MPCASM_OK;
 }
+// ... and of a host-only query, which decides by the strides alone
+int stride_table(const PlanDev& d, const int64_t* h_src_stride, SrcTable* out) {
+  if (d.nsrc != 0 && !h_src_stride) return MPCASM_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  for (int s = 0; s < d.nsrc; ++s) {
+    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
+    out->stride[s] = h_src_stride[s];
+  }
+  return MPCASM_OK;
+}
 
-// what every entry that takes plan tables begins with: the tables checked (plan_check.cpp), then their view,
-// with the persistent kernel's hand-over of P chosen
+// the streams a launch reads (eff) where the plan was compiled with lti=: its horizon tables are made in the
+// workspace, so it needs one.  lti_prepass: the pre-pass of n instances; lti_refusals: what it refuses, nothing
+// launched (for an entry that builds an index between the two)
+int lti_prepass(const mpcasm_plan* plan, const SrcTable& src, void* d_work, int n, void* stream, SrcTable* eff) {
+  if (plan->dev.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
+  return launch_lti_tables(plan->dev, src, static_cast<double*>(d_work), n, plan->h_itab.data(), eff,
+                           static_cast<hipStream_t>(stream));
+}
+int lti_refusals(const mpcasm_plan* plan, const SrcTable& src, void* d_work, SrcTable* eff) {
+  if (plan->dev.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
+  return lti_effective_sources(plan->dev, src, static_cast<double*>(d_work), plan->h_itab.data(), eff);
+}
+
+// the table pointers of a host-only query (and of mpcasm_plan_create); the entry checks its own pointers and
+// scalars beside them, zeroes its results, and goes on to host_plan: ERR_ARG leaves the results as they were
+bool tables_missing(const int32_t* h_itab, const double* h_dtab, size_t n_dtab) {
+  return !h_itab || (n_dtab && !h_dtab);
+}
+// the tables checked (plan_check.cpp), then their view, with the persistent kernel's hand-over of P chosen
 int host_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, PlanDev* d) {
   const int rc = validate_plan(h_itab, h_dtab, n_itab, n_dtab);
   if (rc != MPCASM_OK) return rc;
@@ -139,6 +213,24 @@ int host_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t
   d->rs_p_direct = d->rs_ok ? resident_choose_p_direct(*d, g_options.p_direct.load(std::memory_order_relaxed)) : 0;
   // the CSC form of P is read out of its LDS copy: such a plan has no other way
   if (d->csc_pnnz != 0 && d->rs_ok) d->rs_p_direct = resident_choose_p_direct(*d, 2);
+  return MPCASM_OK;
+}
+
+// out[0..3] of the two infos of the assembly's derivative
+template <class Index>
+void index_info(const Index& index, int32_t out[4]) {
+  out[0] = (int32_t)index.lds;
+  out[1] = index.lds > 64 * 1024;
+  out[2] = (int32_t)index.words.size();
+  out[3] = index.per_cu;
+}
+
+// how a compile entry ends: the size alone for a caller that passes no buffer, else the words copied out
+int words_out(const std::vector<int32_t>& made, int32_t* h_out, int64_t capacity, int64_t* words) {
+  *words = (int64_t)made.size();
+  if (h_out == nullptr) return MPCASM_OK;
+  if (capacity < (int64_t)made.size()) return MPCASM_ERR_ARG;
+  memcpy(h_out, made.data(), made.size() * sizeof(int32_t));
   return MPCASM_OK;
 }
 
@@ -217,7 +309,7 @@ int mpcasm_fill_route(int batch, int N, int n, int m, int ltv, int aligned16, in
 
 int mpcasm_plan_create(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                        mpcasm_plan** out_plan) {
-  if (!h_itab || !out_plan || (n_dtab && !h_dtab)) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out_plan) return MPCASM_ERR_ARG;
   *out_plan = nullptr;
   PlanDev view;
   const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &view);
@@ -265,7 +357,7 @@ int mpcasm_plan_create(const int32_t* h_itab, size_t n_itab, const double* h_dta
 
 int mpcasm_resident_lds_bytes(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                               int64_t out[2]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out) return MPCASM_ERR_ARG;
   PlanDev d;
   const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
   if (rc != MPCASM_OK) return rc;
@@ -278,7 +370,7 @@ int mpcasm_resident_lds_bytes(const int32_t* h_itab, size_t n_itab, const double
 
 int mpcasm_jit_check(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                      char* log, size_t log_capacity) {
-  if (!h_itab || (n_dtab && !h_dtab)) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab)) return MPCASM_ERR_ARG;
   if (log && log_capacity) log[0] = 0;
   PlanDev d;
   const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
@@ -310,7 +402,7 @@ int mpcasm_jit_check(const int32_t* h_itab, size_t n_itab, const double* h_dtab,
 
 int mpcasm_fetch_segments(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                           int limit, int32_t* out, size_t capacity, int64_t* n_words) {
-  if (!h_itab || (n_dtab && !h_dtab) || !n_words || (capacity && !out) || limit < 0) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !n_words || (capacity && !out) || limit < 0) return MPCASM_ERR_ARG;
   PlanDev d;
   const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
   if (rc != MPCASM_OK) return rc;
@@ -333,9 +425,7 @@ int mpcasm_jit_stats(int64_t out[3]) {
 }
 
 int mpcasm_plan_prepare(const mpcasm_plan* plan, int batch) {
-  if (!plan || batch < 0) return MPCASM_ERR_ARG;
-  int current = -1;
-  if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
+  if (!plan || batch < 0 || !on_plan_device(plan)) return MPCASM_ERR_ARG;
   const LaunchOptions opt = launch_options(plan);
   AssembleRoute r;
   // (nothing is compiled per plan for the other kernels; input alignment is taken as given)
@@ -351,8 +441,8 @@ int mpcasm_plan_prepare(const mpcasm_plan* plan, int batch) {
 int mpcasm_plan_destroy(mpcasm_plan* plan) {
   if (!plan) return MPCASM_OK;
   jit_forget(plan->d_itab);
-  if (plan->d_adj) (void)hipFree(plan->d_adj);
-  if (plan->d_par) (void)hipFree(plan->d_par);
+  plan->adj.release();
+  plan->par.release();
   hipError_t e1 = hipFree(plan->d_itab);
   hipError_t e2 = hipFree(plan->d_dtab);
   delete plan;
@@ -407,21 +497,15 @@ static int assemble_impl(const mpcasm_plan* plan, const double* const* h_src,
   if (!plan || batch < 0) return MPCASM_ERR_ARG;
   if (batch == 0) return MPCASM_OK;  // nothing to do (empty buffers may be null)
   const PlanDev& d = plan->dev;
-  if ((d.nsrc && (!h_src || !h_src_stride)) || (d.nparams && !d_params) || (d.ng && !d_given))
-    return MPCASM_ERR_ARG;
+  if ((d.nparams && !d_params) || (d.ng && !d_given)) return MPCASM_ERR_ARG;
   if ((d_P == nullptr) != (d_q == nullptr) || (d_G == nullptr) != (d_h == nullptr))
     return MPCASM_ERR_ARG;
   if (d.rtot && !d_work && !d.sw_ok) return MPCASM_ERR_ARG;
-  {  // the plan's tables (and its compiled kernel) live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if (!on_plan_device(plan)) return MPCASM_ERR_ARG;
   // results leave the chip in 16-byte stores
-  if ((reinterpret_cast<uintptr_t>(d_P) | reinterpret_cast<uintptr_t>(d_q) |
-       reinterpret_cast<uintptr_t>(d_G) | reinterpret_cast<uintptr_t>(d_h)) & 15)
-    return MPCASM_ERR_ARG;
+  if (misaligned(d_P, 15) || misaligned(d_q, 15) || misaligned(d_G, 15) || misaligned(d_h, 15)) return MPCASM_ERR_ARG;
   SrcTable src;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
   if (rc != MPCASM_OK) return rc;
   if (d_given_index != nullptr) {
     // the index of `given`'s rows rides in the last slot of the source table (resident.hip)
@@ -463,11 +547,12 @@ int mpcasm_plan_last_kernel(const mpcasm_plan* plan) {
 int mpcasm_preview_matrices(const mpcasm_plan* plan, const double* const* h_src,
                             const int64_t* h_src_stride, double* d_PM, int batch, void* stream) {
   if (!plan || !d_PM || batch < 0) return MPCASM_ERR_ARG;
-  if (plan->dev.nsrc && (!h_src || !h_src_stride)) return MPCASM_ERR_ARG;
+  if (sources_missing(plan->dev, h_src, h_src_stride)) return MPCASM_ERR_ARG;
   if (plan->dev.rs_nlti != 0 || plan->dev.sw_ok) return MPCASM_ERR_LIMIT;  // the plan has no S, U to read
   if (batch == 0) return MPCASM_OK;
+  if (!on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
   rc = launch_preview_matrices(plan->dev, src, d_PM, batch, static_cast<hipStream_t>(stream), &err);
@@ -490,51 +575,28 @@ int mpcasm_preview_direct(const mpcasm_plan* plan, const double* const* h_src,
                           double* d_out, void* d_work, int batch, void* stream) {
   if (!plan || !d_out || batch < 0) return MPCASM_ERR_ARG;
   const PlanDev& d = plan->dev;
-  if ((d.nsrc && (!h_src || !h_src_stride)) || (d.ng && !d_given) || (d.no && !d_optim))
-    return MPCASM_ERR_ARG;
+  if (sources_missing(d, h_src, h_src_stride) || (d.ng && !d_given) || (d.no && !d_optim)) return MPCASM_ERR_ARG;
   if (batch == 0 || d.pmrows == 0) return MPCASM_OK;
   if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (per-step dynamics: no horizon tables to preview from)
-  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
-  {  // the plan's tables live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if (!on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src, eff;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  rc = lti_prepass(plan, src, d_work, batch, stream, &eff);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
-  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), batch, plan->h_itab.data(), &eff,
-                         static_cast<hipStream_t>(stream));
-  if (rc != MPCASM_OK) return rc;
   rc = launch_preview_direct(d, eff, d_given, d_optim, d_out, batch, plan->num_cus,
                              static_cast<hipStream_t>(stream), &err, plan->h_itab.data());
   return launched(rc, err);
 }
 
 namespace {
-// the plan's transposed index on its device: built and uploaded once, by whichever call comes first
+// the plan's transposed index on its device, and (mpcasm_assemble_params_vjp) its parameter index
 int plan_adjoint_index(const mpcasm_plan* plan, const AdjointIndex** out) {
-  std::lock_guard<std::mutex> lock(plan->adj_mutex);
-  if (plan->adj_rc == 1) {
-    plan->adj_rc = adjoint_build_index(plan->dev, plan->h_itab.data(), &plan->adj);
-    if (plan->adj_rc == MPCASM_OK) {
-      const size_t bytes = std::max<size_t>(plan->adj.words.size(), 1) * sizeof(int32_t);
-      hipError_t e = hipMalloc(&plan->d_adj, bytes);
-      if (e == hipSuccess && !plan->adj.words.empty())
-        e = hipMemcpy(plan->d_adj, plan->adj.words.data(), plan->adj.words.size() * sizeof(int32_t),
-                      hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        if (plan->d_adj) (void)hipFree(plan->d_adj);
-        plan->d_adj = nullptr;
-        plan->adj_rc = MPCASM_ERR_HIP;
-        plan->adj_hip = (int)e;
-      }
-      plan->adj.view.idx = plan->d_adj;
-    }
-  }
-  if (plan->adj_rc == MPCASM_ERR_HIP) g_last_hip = plan->adj_hip;
-  *out = &plan->adj;
-  return plan->adj_rc;
+  return plan->adj.get(plan->index_mutex, plan->dev, plan->h_itab.data(), adjoint_build_index, out);
+}
+int plan_params_index(const mpcasm_plan* plan, const ParamsIndex** out) {
+  return plan->par.get(plan->index_mutex, plan->dev, plan->h_itab.data(), params_adjoint_build_index, out);
 }
 
 // JVP: in_x = d, out_x = dq, out_h = dh;  VJP: in_x = gq, in_h = gh, out_x = ggiven
@@ -546,25 +608,16 @@ int adjoint_impl(const mpcasm_plan* plan, bool vjp, const double* const* h_src, 
   if (vjp ? (!in_x && !in_h) : (!out_x && !out_h)) return MPCASM_ERR_ARG;
   if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (per-step dynamics: no S, U; the adjoint is the sweep's backward recursion)
   if (batch == 0 || d.ng == 0) return MPCASM_OK;
-  if ((d.nsrc && (!h_src || !h_src_stride)) || (d.nparams && !d_params) || (vjp ? !out_x : !in_x))
-    return MPCASM_ERR_ARG;
-  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
-  {  // the plan's tables live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if ((d.nparams && !d_params) || (vjp ? !out_x : !in_x) || !on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src, eff;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
   if (rc != MPCASM_OK) return rc;
-  {  // (what the pre-pass refuses, before the index is built for nothing)
-    rc = lti_effective_sources(d, src, static_cast<double*>(d_work), plan->h_itab.data(), &eff);
-    if (rc != MPCASM_OK) return rc;
-  }
+  rc = lti_refusals(plan, src, d_work, &eff);  // (before the index is built for nothing)
+  if (rc != MPCASM_OK) return rc;
   const AdjointIndex* index;
   rc = plan_adjoint_index(plan, &index);
   if (rc != MPCASM_OK) return rc;
-  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), batch, plan->h_itab.data(), &eff,
-                         static_cast<hipStream_t>(stream));
+  rc = lti_prepass(plan, src, d_work, batch, stream, &eff);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
   rc = launch_assemble_adjoint(d, eff, *index, vjp, d_params, in_x, in_h, out_x, out_h, batch, plan->num_cus,
@@ -588,46 +641,19 @@ int mpcasm_assemble_vjp(const mpcasm_plan* plan, const double* const* h_src, con
 }
 
 namespace {
-// the plan's parameter index on its device: built and uploaded once, by whichever call comes first
-int plan_params_index(const mpcasm_plan* plan, const ParamsIndex** out) {
-  std::lock_guard<std::mutex> lock(plan->adj_mutex);
-  if (plan->par_rc == 1) {
-    plan->par_rc = params_adjoint_build_index(plan->dev, plan->h_itab.data(), &plan->par);
-    if (plan->par_rc == MPCASM_OK) {
-      const size_t bytes = std::max<size_t>(plan->par.words.size(), 1) * sizeof(int32_t);
-      hipError_t e = hipMalloc(&plan->d_par, bytes);
-      if (e == hipSuccess && !plan->par.words.empty())
-        e = hipMemcpy(plan->d_par, plan->par.words.data(), plan->par.words.size() * sizeof(int32_t),
-                      hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        if (plan->d_par) (void)hipFree(plan->d_par);
-        plan->d_par = nullptr;
-        plan->par_rc = MPCASM_ERR_HIP;
-        plan->par_hip = (int)e;
-      }
-      plan->par.view.idx = plan->d_par;
-    }
-  }
-  if (plan->par_rc == MPCASM_ERR_HIP) g_last_hip = plan->par_hip;
-  *out = &plan->par;
-  return plan->par_rc;
-}
-
-// what the two info entries of the assembly's derivative share: the tables checked and viewed, the strides taken,
-// what the pre-pass of a plan compiled with lti= refuses
-int adjoint_info_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
-                      const int64_t* h_src_stride, PlanDev* d) {
-  const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, d);
+// what the host-only queries about a plan with horizon matrices share (the two infos of the assembly's derivative,
+// mpcasm_preview_route): the tables checked and viewed, the strides taken -- missing ones before, negative ones
+// after the refusal of a plan compiled with ltv= -- and what the pre-pass of a plan compiled with lti= refuses
+int horizon_query_plan(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
+                       const int64_t* h_src_stride, PlanDev* d, SrcTable* eff) {
+  int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, d);
   if (rc != MPCASM_OK) return rc;
   if (d->nsrc && !h_src_stride) return MPCASM_ERR_ARG;
-  if (d->sw_ok) return MPCASM_ERR_LIMIT;
-  SrcTable src, eff;
-  memset(&src, 0, sizeof src);
-  for (int s = 0; s < d->nsrc; ++s) {
-    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
-    src.stride[s] = h_src_stride[s];
-  }
-  return lti_effective_sources(*d, src, nullptr, h_itab, &eff);
+  if (d->sw_ok) return MPCASM_ERR_LIMIT;  // (as mpcasm_preview_direct, adjoint_impl)
+  SrcTable src;
+  rc = stride_table(*d, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  return lti_effective_sources(*d, src, nullptr, h_itab, eff);
 }
 }  // namespace
 
@@ -639,18 +665,13 @@ int mpcasm_assemble_params_vjp(const mpcasm_plan* plan, const double* const* h_s
   const PlanDev& d = plan->dev;
   if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (per-step dynamics: no S, U; the adjoint is the sweep's backward recursion)
   if (batch == 0 || d.nparams == 0) return MPCASM_OK;
-  if ((d.nsrc && (!h_src || !h_src_stride)) || !d_params || !d_gparams || (d.ng && !d_given) ||
-      (d.no && (!d_x || !d_u)) || (d.nc && (!d_y || !d_w)))
+  if (!d_params || !d_gparams || (d.ng && !d_given) || (d.no && (!d_x || !d_u)) || (d.nc && (!d_y || !d_w)) ||
+      !on_plan_device(plan))
     return MPCASM_ERR_ARG;
-  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
-  {  // the plan's tables live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
   SrcTable src, eff;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
   if (rc != MPCASM_OK) return rc;
-  rc = lti_effective_sources(d, src, static_cast<double*>(d_work), plan->h_itab.data(), &eff);
+  rc = lti_refusals(plan, src, d_work, &eff);  // (before an index is built for nothing)
   if (rc != MPCASM_OK) return rc;
   const AdjointIndex* adj;
   rc = plan_adjoint_index(plan, &adj);
@@ -658,8 +679,7 @@ int mpcasm_assemble_params_vjp(const mpcasm_plan* plan, const double* const* h_s
   const ParamsIndex* index;
   rc = plan_params_index(plan, &index);
   if (rc != MPCASM_OK) return rc;
-  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), batch, plan->h_itab.data(), &eff,
-                         static_cast<hipStream_t>(stream));
+  rc = lti_prepass(plan, src, d_work, batch, stream, &eff);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
   rc = launch_assemble_params_adjoint(d, eff, *adj, *index, d_params, d_given, d_x, d_u, d_y, d_w, d_verdict,
@@ -669,10 +689,11 @@ int mpcasm_assemble_params_vjp(const mpcasm_plan* plan, const double* const* h_s
 
 int mpcasm_assemble_params_vjp_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                                     const int64_t* h_src_stride, int32_t out[4]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out) return MPCASM_ERR_ARG;
   memset(out, 0, 4 * sizeof(int32_t));
   PlanDev d;
-  const int rc = adjoint_info_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d);
+  SrcTable eff;
+  const int rc = horizon_query_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d, &eff);
   if (rc != MPCASM_OK) return rc;
   AdjointIndex adj;
   const int first = adjoint_build_index(d, h_itab, &adj);
@@ -680,52 +701,38 @@ int mpcasm_assemble_params_vjp_info(const int32_t* h_itab, size_t n_itab, const 
   ParamsIndex index;
   const int built = params_adjoint_build_index(d, h_itab, &index);
   if (built != MPCASM_OK) return built;
-  out[0] = (int32_t)index.lds;
-  out[1] = index.lds > 64 * 1024;
-  out[2] = (int32_t)index.words.size();
-  out[3] = index.per_cu;
+  index_info(index, out);
   return MPCASM_OK;
 }
 
 int mpcasm_assemble_adjoint_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                                  const int64_t* h_src_stride, int32_t out[4]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out) return MPCASM_ERR_ARG;
   memset(out, 0, 4 * sizeof(int32_t));
   PlanDev d;
-  const int rc = adjoint_info_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d);
+  SrcTable eff;
+  const int rc = horizon_query_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d, &eff);
   if (rc != MPCASM_OK) return rc;
   AdjointIndex index;
   const int built = adjoint_build_index(d, h_itab, &index);
   if (built != MPCASM_OK) return built;
-  out[0] = (int32_t)index.lds;
-  out[1] = index.lds > 64 * 1024;
-  out[2] = (int32_t)index.words.size();
-  out[3] = index.per_cu;
+  index_info(index, out);
   return MPCASM_OK;
 }
 
 int mpcasm_preview_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                          const int64_t* h_src_stride, int nterms, int ngoals, int32_t out[8]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out || nterms < 0 || ngoals < 0) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out || nterms < 0 || ngoals < 0) return MPCASM_ERR_ARG;
   memset(out, 0, 8 * sizeof(int32_t));
   PlanDev d;
-  const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
+  SrcTable eff;
+  const int rc = horizon_query_plan(h_itab, n_itab, h_dtab, n_dtab, h_src_stride, &d, &eff);
   if (rc != MPCASM_OK) return rc;
-  if (d.nsrc && !h_src_stride) return MPCASM_ERR_ARG;
-  if (d.sw_ok) return MPCASM_ERR_LIMIT;  // (as mpcasm_preview_direct)
-  SrcTable src, eff;
-  memset(&src, 0, sizeof src);
-  for (int s = 0; s < d.nsrc; ++s) {
-    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
-    src.stride[s] = h_src_stride[s];
-  }
-  const int lti = lti_effective_sources(d, src, nullptr, h_itab, &eff);
-  if (lti != MPCASM_OK) return lti;
   return preview_route(d, eff, h_itab, nterms, ngoals, out);
 }
 
 int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int32_t out[8]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out) return MPCASM_ERR_ARG;
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out) return MPCASM_ERR_ARG;
   memset(out, 0, 8 * sizeof(int32_t));
   PlanDev d;
   const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
@@ -747,19 +754,15 @@ int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
 
 int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                        const int64_t* h_src_stride, int batch, int want, int path, int32_t out[16]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out || batch < 1 || path < -1 || path > 4 || want < 1 || want > 3)
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out || batch < 1 || path < -1 || path > 4 || want < 1 || want > 3)
     return MPCASM_ERR_ARG;
   memset(out, 0, 16 * sizeof(int32_t));
   PlanDev d;
-  const int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
+  int rc = host_plan(h_itab, n_itab, h_dtab, n_dtab, &d);
   if (rc != MPCASM_OK) return rc;
-  if (d.nsrc && !h_src_stride) return MPCASM_ERR_ARG;
   SrcTable src;
-  memset(&src, 0, sizeof src);
-  for (int s = 0; s < d.nsrc; ++s) {
-    if (h_src_stride[s] < 0) return MPCASM_ERR_ARG;
-    src.stride[s] = h_src_stride[s];
-  }
+  rc = stride_table(d, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
   LaunchOptions opt = launch_options(nullptr);
   if (path >= 0) opt.path = path;
   AssembleRoute r;
@@ -786,7 +789,7 @@ int mpcasm_tiled_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
 
 int mpcasm_assemble_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int batch,
                           int path, int inputs_aligned, int indexed, int32_t out[4]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out || batch < 1 || path < -1 || path > 4 ||
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out || batch < 1 || path < -1 || path > 4 ||
       (inputs_aligned != 0 && inputs_aligned != 1) || (indexed != 0 && indexed != 1))
     return MPCASM_ERR_ARG;
   memset(out, 0, 4 * sizeof(int32_t));
@@ -806,7 +809,7 @@ int mpcasm_assemble_route(const int32_t* h_itab, size_t n_itab, const double* h_
 
 int mpcasm_staged_route(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab, int want_cost,
                         int want_constraints, int batch, int32_t out[8]) {
-  if (!h_itab || (n_dtab && !h_dtab) || !out || batch < 1 || (want_cost != 0 && want_cost != 1) ||
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !out || batch < 1 || (want_cost != 0 && want_cost != 1) ||
       (want_constraints != 0 && want_constraints != 1) || (!want_cost && !want_constraints))
     return MPCASM_ERR_ARG;
   memset(out, 0, 8 * sizeof(int32_t));
@@ -849,11 +852,7 @@ int mpcasm_given_map_compile(const mpcasm_plan* plan, const int32_t* h_rows, con
   std::vector<int32_t> map;
   const int rc = compile_given_map(d, plan->h_itab.data(), h_rows, h_values, &map);
   if (rc != MPCASM_OK) return rc;
-  *words = (int64_t)map.size();
-  if (h_map == nullptr) return MPCASM_OK;
-  if (capacity < (int64_t)map.size()) return MPCASM_ERR_ARG;
-  memcpy(h_map, map.data(), map.size() * sizeof(int32_t));
-  return MPCASM_OK;
+  return words_out(map, h_map, capacity, words);
 }
 
 int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const int64_t* h_src_stride,
@@ -864,20 +863,14 @@ int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const
   const PlanDev& d = plan->dev;
   if (d.sw_ok || !d.t_ci_ok) return MPCASM_ERR_LIMIT;  // (as mpcasm_preview_direct)
   if (count == 0 || d.ng == 0) return MPCASM_OK;
-  if (!d_given || !d_map || (d.no && !d_optim) || (d.nsrc && (!h_src || !h_src_stride))) return MPCASM_ERR_ARG;
-  if (!d_index && rows < count) return MPCASM_ERR_ARG;
-  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
-  {  // the plan's tables live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if (!d_given || !d_map || (d.no && !d_optim)) return MPCASM_ERR_ARG;
+  if ((!d_index && rows < count) || !on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src, eff;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  rc = lti_prepass(plan, src, d_work, count, stream, &eff);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
-  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), count, plan->h_itab.data(), &eff,
-                         static_cast<hipStream_t>(stream));
-  if (rc != MPCASM_OK) return rc;
   rc = launch_next_given(d, eff, d_map, map_words, d_given, rows, d_optim, d_index, d_status, apply_mask, count,
                          plan->num_cus, static_cast<hipStream_t>(stream), &err);
   return launched(rc, err);
@@ -886,7 +879,7 @@ int mpcasm_next_given(const mpcasm_plan* plan, const double* const* h_src, const
 int mpcasm_ltv_rollout_compile(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                                const int32_t h_sizes[7], const int32_t* h_recs, int nrec, const double* h_cvec,
                                int ncvec, int32_t* h_table, int64_t capacity, int64_t* words) {
-  if (!h_itab || (n_dtab && !h_dtab) || !h_sizes || !h_recs || !words || nrec < 1 || ncvec < 0 ||
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !h_sizes || !h_recs || !words || nrec < 1 || ncvec < 0 ||
       (ncvec && !h_cvec) || capacity < 0)
     return MPCASM_ERR_ARG;
   PlanDev d;
@@ -898,11 +891,7 @@ int mpcasm_ltv_rollout_compile(const int32_t* h_itab, size_t n_itab, const doubl
   std::vector<int32_t> table;
   const int made = compile_rollout_table(d, h_recs, nrec, h_cvec, ncvec, &table);
   if (made != MPCASM_OK) return made;
-  *words = (int64_t)table.size();
-  if (h_table == nullptr) return MPCASM_OK;
-  if (capacity < (int64_t)table.size()) return MPCASM_ERR_ARG;
-  memcpy(h_table, table.data(), table.size() * sizeof(int32_t));
-  return MPCASM_OK;
+  return words_out(table, h_table, capacity, words);
 }
 
 namespace {
@@ -916,13 +905,9 @@ int rollout_impl(const mpcasm_plan* plan, const double* const* h_src, const int6
   if (count == 0 || (!write_given && d.pmrows == 0)) return MPCASM_OK;
   if (!d_given || !d_optim || !d_table || !h_src || !h_src_stride || (!write_given && !d_out)) return MPCASM_ERR_ARG;
   if (!d_index && rows < count) return MPCASM_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(d_out) & 7) return MPCASM_ERR_ARG;
-  {  // the plan's tables live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if (misaligned(d_out, 7) || !on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
   rc = launch_ltv_rollout(d, src, d_table, table_words, d_given, rows, d_optim, d_index, d_status, apply_mask, d_out,
@@ -949,7 +934,7 @@ int mpcasm_ltv_advance(const mpcasm_plan* plan, const double* const* h_src, cons
 int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* h_dtab, size_t n_dtab,
                             int64_t table_words, int rows_out, int count, int32_t* group, int64_t* lds_bytes,
                             int32_t* workgroups) {
-  if (!h_itab || (n_dtab && !h_dtab) || !group || !lds_bytes || !workgroups || table_words < 0 ||
+  if (tables_missing(h_itab, h_dtab, n_dtab) || !group || !lds_bytes || !workgroups || table_words < 0 ||
       (rows_out != 0 && rows_out != 1) || count < 0)
     return MPCASM_ERR_ARG;
   *group = 0;
@@ -968,10 +953,6 @@ int mpcasm_ltv_rollout_info(const int32_t* h_itab, size_t n_itab, const double* 
   *workgroups = (int32_t)geo.grid;
   return MPCASM_OK;
 }
-
-namespace {
-bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-}  // namespace
 
 int mpcasm_ltv_lqr(int n, int m, int T, int batch, const double* d_A, int64_t a_stride, const double* d_B,
                    int64_t b_stride, const double* d_Q, const double* d_R, const double* d_PT, double* d_K,
@@ -1028,13 +1009,9 @@ int mpcasm_ltv_true_inputs(const mpcasm_plan* plan, const double* const* h_src, 
   if (!d_K || !d_given || !d_optim || !d_out || !h_src || !h_src_stride || misaligned(d_K, 7) ||
       misaligned(d_given, 7) || misaligned(d_optim, 7) || misaligned(d_out, 7) || misaligned(d_index, 3))
     return MPCASM_ERR_ARG;
-  if (!d_index && rows < count) return MPCASM_ERR_ARG;
-  {  // the plan's tables live on the device it was created on
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if ((!d_index && rows < count) || !on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
   rc = launch_ltv_true_inputs(d, src, d_K, k_stride, d_given, rows, d_optim, d_index, d_out, count,
@@ -1050,22 +1027,17 @@ int mpcasm_preview_goal_distance(const mpcasm_plan* plan, const double* const* h
   if (!plan || batch < 0 || nterms < 0 || ngoals < 0) return MPCASM_ERR_ARG;
   const PlanDev& d = plan->dev;
   if (batch == 0 || ngoals == 0) return MPCASM_OK;
-  if (!d_out || (d.nsrc && (!h_src || !h_src_stride)) || (d.ng && !d_given) || (d.no && !d_optim) ||
+  if (!d_out || sources_missing(d, h_src, h_src_stride) || (d.ng && !d_given) || (d.no && !d_optim) ||
       (nterms && (!d_terms || !d_params)))
     return MPCASM_ERR_ARG;
   if (d.sw_ok) return MPCASM_ERR_LIMIT;
-  if (d.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
-  {
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != plan->device) return MPCASM_ERR_ARG;
-  }
+  if (!on_plan_device(plan)) return MPCASM_ERR_ARG;
   SrcTable src, eff;
-  int rc = make_src_table(plan, h_src, h_src_stride, &src);
+  int rc = plan_sources(plan, h_src, h_src_stride, &src);
+  if (rc != MPCASM_OK) return rc;
+  rc = lti_prepass(plan, src, d_work, batch, stream, &eff);
   if (rc != MPCASM_OK) return rc;
   hipError_t err;
-  rc = launch_lti_tables(d, src, static_cast<double*>(d_work), batch, plan->h_itab.data(), &eff,
-                         static_cast<hipStream_t>(stream));
-  if (rc != MPCASM_OK) return rc;
   rc = launch_preview_goals(d, eff, d_given, d_optim, d_params, d.nparams, d_terms, nterms, ngoals, d_out,
                             batch, plan->num_cus, static_cast<hipStream_t>(stream), &err, plan->h_itab.data());
   return launched(rc, err);
@@ -1129,10 +1101,19 @@ int mpcasm_admm(int no, int nc, const double* d_P, const double* d_q, const doub
   return launched(launch_admm(b, rho, s, static_cast<hipStream_t>(stream), &err), err);
 }
 
-// mpcasm_qp_solve and mpcasm_qp_solve_wide: the same arguments, checked in the same order; the wide entry also
-// asks its launch where K^-1 lives, before it looks at the batch
+// the four mpcasm_qp_solve* entries: the same arguments, checked in the same order; the wide ones also ask their
+// launch where K^-1 lives, before they look at the batch
 // soft: the penalties of the _soft entries (NULL: the hard ones), their stride nc or 0
-static int qp_solve_entry(bool wide, const QpBatch& b, const QpSolve& s, void* stream, const QpSoft* soft = nullptr) {
+static int qp_solve_entry(bool wide, const QpSoft* soft, int no, int nc, const double* d_P, const double* d_q,
+                          const double* d_G, const double* d_h, double* d_x, double* d_y, double* d_z, int warm,
+                          double* d_rho, double sigma, double alpha, double eps_abs, double eps_rel,
+                          double eps_prim_inf, double eps_dual_inf, int max_iter, int check_every,
+                          int adaptive_rho_interval, int32_t* d_status, int32_t* d_iters, double* d_res, int batch,
+                          double* d_kinv, int kinv_valid, void* stream) {
+  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
+  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
+                   adaptive_rho_interval},
+                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
   if (!qp_solve_settings_ok(s) || !qp_sizes_ok(b.no, b.nc) || b.batch < 0) return MPCASM_ERR_ARG;
   if (soft && soft->stride != 0 && soft->stride != b.nc) return MPCASM_ERR_ARG;
   int32_t on_chip = 1;
@@ -1158,11 +1139,9 @@ int mpcasm_qp_solve(int no, int nc, const double* d_P, const double* d_q, const 
                     double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
                     int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
                     int kinv_valid, void* stream) {
-  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
-  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
-                   adaptive_rho_interval},
-                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
-  return qp_solve_entry(false, b, s, stream);
+  return qp_solve_entry(false, nullptr, no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm, d_rho, sigma, alpha,
+                        eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every, adaptive_rho_interval,
+                        d_status, d_iters, d_res, batch, d_kinv, kinv_valid, stream);
 }
 
 int mpcasm_qp_solve_lds_bytes(int no, int nc, int64_t* out) {
@@ -1177,11 +1156,9 @@ int mpcasm_qp_solve_wide(int no, int nc, const double* d_P, const double* d_q, c
                          double eps_dual_inf, int max_iter, int check_every, int adaptive_rho_interval,
                          int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
                          int kinv_valid, void* stream) {
-  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
-  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
-                   adaptive_rho_interval},
-                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
-  return qp_solve_entry(true, b, s, stream);
+  return qp_solve_entry(true, nullptr, no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm, d_rho, sigma, alpha,
+                        eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every, adaptive_rho_interval,
+                        d_status, d_iters, d_res, batch, d_kinv, kinv_valid, stream);
 }
 
 int mpcasm_qp_solve_wide_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
@@ -1196,12 +1173,10 @@ int mpcasm_qp_solve_soft(int no, int nc, const double* d_P, const double* d_q, c
                          int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
                          int kinv_valid, void* stream, const double* d_soft_lin, const double* d_soft_quad,
                          int64_t soft_stride) {
-  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
-  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
-                   adaptive_rho_interval},
-                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
   const QpSoft soft{d_soft_lin, d_soft_quad, soft_stride};
-  return qp_solve_entry(false, b, s, stream, &soft);
+  return qp_solve_entry(false, &soft, no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm, d_rho, sigma, alpha,
+                        eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every, adaptive_rho_interval,
+                        d_status, d_iters, d_res, batch, d_kinv, kinv_valid, stream);
 }
 
 int mpcasm_qp_solve_soft_lds_bytes(int no, int nc, int64_t* out) {
@@ -1217,17 +1192,23 @@ int mpcasm_qp_solve_wide_soft(int no, int nc, const double* d_P, const double* d
                               int32_t* d_status, int32_t* d_iters, double* d_res, int batch, double* d_kinv,
                               int kinv_valid, void* stream, const double* d_soft_lin, const double* d_soft_quad,
                               int64_t soft_stride) {
-  const QpBatch b{no, nc, batch, d_P, d_q, d_G, d_h, d_x, d_y, d_z};
-  const QpSolve s{{d_rho, d_status, d_iters, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, check_every,
-                   adaptive_rho_interval},
-                  sigma, alpha, max_iter, warm != 0, d_kinv, kinv_valid != 0, d_res};
   const QpSoft soft{d_soft_lin, d_soft_quad, soft_stride};
-  return qp_solve_entry(true, b, s, stream, &soft);
+  return qp_solve_entry(true, &soft, no, nc, d_P, d_q, d_G, d_h, d_x, d_y, d_z, warm, d_rho, sigma, alpha,
+                        eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every, adaptive_rho_interval,
+                        d_status, d_iters, d_res, batch, d_kinv, kinv_valid, stream);
 }
 
 int mpcasm_qp_solve_wide_soft_info(int no, int nc, int64_t* lds_bytes, int32_t* kinv_on_chip) {
   if (!qp_sizes_ok(no, nc) || !lds_bytes || !kinv_on_chip) return MPCASM_ERR_ARG;
   return qp_solve_wide_soft_info(no, nc, lds_bytes, kinv_on_chip);
+}
+
+// the workspace of the two _wide entries behind the solve: past their size limit, then missing, misaligned or small
+static int qp_wide_work(int no, int nc, int batch, const void* d_work, size_t work_bytes) {
+  int64_t need = 0;
+  const int limit = qp_polish_wide_info(no, nc, batch, nullptr, &need, nullptr);
+  if (limit != MPCASM_OK) return limit;
+  return !d_work || misaligned(d_work, 15) || work_bytes < (size_t)need ? MPCASM_ERR_ARG : MPCASM_OK;
 }
 
 // what the two polish entries decide alike: MPCASM_OK with *go set where there is something to launch
@@ -1267,10 +1248,8 @@ int mpcasm_qp_polish_wide(int no, int nc, const double* d_P, const double* d_q, 
   bool go;
   const int rc = qp_polish_checks(b, p, &go);
   if (!go) return rc;
-  int64_t need = 0;
-  const int limit = qp_polish_wide_info(no, nc, batch, nullptr, &need, nullptr);
-  if (limit != MPCASM_OK) return limit;
-  if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0 || work_bytes < (size_t)need) return MPCASM_ERR_ARG;
+  const int work = qp_wide_work(no, nc, batch, d_work, work_bytes);
+  if (work != MPCASM_OK) return work;
   hipError_t err;
   return launched(launch_qp_polish_wide(b, p, static_cast<double*>(d_work), static_cast<hipStream_t>(stream), &err),
                   err);
@@ -1321,10 +1300,8 @@ int mpcasm_qp_sens_wide(int no, int nc, const double* d_P, const double* d_G, co
   bool go;
   const int rc = qp_sens_checks(s, &go);
   if (!go) return rc;
-  int64_t need = 0;
-  const int limit = qp_polish_wide_info(no, nc, batch, nullptr, &need, nullptr);
-  if (limit != MPCASM_OK) return limit;
-  if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0 || work_bytes < (size_t)need) return MPCASM_ERR_ARG;
+  const int work = qp_wide_work(no, nc, batch, d_work, work_bytes);
+  if (work != MPCASM_OK) return work;
   hipError_t err;
   return launched(launch_qp_sens_wide(s, static_cast<double*>(d_work), static_cast<hipStream_t>(stream), &err), err);
 }

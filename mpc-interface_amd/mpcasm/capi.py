@@ -62,163 +62,111 @@ def qp_bit(status):
 # every symbol include/mpcasm.h declares: name -> (restype, argtypes)
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _void_p = ctypes.c_void_p
+_int32_p, _int64_p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+# the argument runs many entries open with: a plan's host tables (h_itab, n_itab, h_dtab, n_dtab); a plan and its
+# sources (plan, h_src, h_src_stride); everything the four mpcasm_qp_solve* entries take up to and including `stream`
+_TABLES = [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t]
+_PLAN_SRC = [_void_p, ctypes.POINTER(_void_p), _int64_p]
+_QP_SOLVE = ([ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] + [ctypes.c_double] * 6 +
+             [ctypes.c_int] * 3 + [_void_p] * 3 + [ctypes.c_int, _void_p, ctypes.c_int, _void_p])
+_QP_SOFT = [_void_p, _void_p, ctypes.c_int64]
 SIGNATURES = {
     "mpcasm_abi_version": (ctypes.c_int, []),
     "mpcasm_device_count": (ctypes.c_int, []),
     "mpcasm_last_hip": (ctypes.c_int, []),
     "mpcasm_status_string": (ctypes.c_char_p, [ctypes.c_int]),
     "mpcasm_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "mpcasm_fill_su": (ctypes.c_int, [_void_p, _void_p, _void_p, _void_p, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      _void_p]),
-    "mpcasm_fill_route": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_plan_create": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                          ctypes.POINTER(_void_p)]),
+    "mpcasm_fill_su": (ctypes.c_int, [_void_p, _void_p, _void_p, _void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_int, ctypes.c_int, _void_p]),
+    "mpcasm_fill_route": (ctypes.c_int, [ctypes.c_int] * 6 + [_int32_p]),
+    "mpcasm_plan_create": (ctypes.c_int, _TABLES + [ctypes.POINTER(_void_p)]),
     "mpcasm_plan_destroy": (ctypes.c_int, [_void_p]),
-    "mpcasm_resident_lds_bytes": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                                 ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_jit_check": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                        ctypes.c_char_p, ctypes.c_size_t]),
-    "mpcasm_fetch_segments": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, ctypes.c_int,
-                                             _void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_preview_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                            ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int,
-                                            ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_sweep_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                          ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_tiled_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                          ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_assemble_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t] + [ctypes.c_int] * 4 +
-                              [ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_staged_route": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 +
-                            [ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "mpcasm_resident_lds_bytes": (ctypes.c_int, _TABLES + [_int64_p]),
+    "mpcasm_jit_check": (ctypes.c_int, _TABLES + [ctypes.c_char_p, ctypes.c_size_t]),
+    "mpcasm_fetch_segments": (ctypes.c_int, _TABLES + [ctypes.c_int, _void_p, ctypes.c_size_t, _int64_p]),
+    "mpcasm_preview_route": (ctypes.c_int, _TABLES + [_int64_p, ctypes.c_int, ctypes.c_int, _int32_p]),
+    "mpcasm_sweep_route": (ctypes.c_int, _TABLES + [_int32_p]),
+    "mpcasm_tiled_route": (ctypes.c_int, _TABLES + [_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _int32_p]),
+    "mpcasm_assemble_route": (ctypes.c_int, _TABLES + [ctypes.c_int] * 4 + [_int32_p]),
+    "mpcasm_staged_route": (ctypes.c_int, _TABLES + [ctypes.c_int] * 3 + [_int32_p]),
+    "mpcasm_plan_sizes": (ctypes.c_int, [_void_p, _int64_p]),
+    "mpcasm_plan_csc_sizes": (ctypes.c_int, [_void_p, _int64_p]),
     "mpcasm_plan_set_option": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.c_int]),
-    "mpcasm_assemble_indexed": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p),
-                                               ctypes.POINTER(ctypes.c_int64), _void_p, _void_p, _void_p,
-                                               _void_p, _void_p, _void_p, _void_p, _void_p, ctypes.c_int,
-                                               _void_p]),
+    "mpcasm_assemble_indexed": (ctypes.c_int, _PLAN_SRC + [_void_p] * 8 + [ctypes.c_int, _void_p]),
     "mpcasm_plan_last_kernel": (ctypes.c_int, [_void_p]),
     "mpcasm_plan_prepare": (ctypes.c_int, [_void_p, ctypes.c_int]),
-    "mpcasm_jit_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_workspace_bytes": (ctypes.c_int, [_void_p, ctypes.c_int,
-                                              ctypes.POINTER(ctypes.c_size_t)]),
-    "mpcasm_assemble": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p),
-                                       ctypes.POINTER(ctypes.c_int64), _void_p, _void_p, _void_p,
-                                       _void_p, _void_p, _void_p, _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_preview_matrices": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p),
-                                               ctypes.POINTER(ctypes.c_int64), _void_p,
-                                               ctypes.c_int, _void_p]),
-    "mpcasm_preview": (ctypes.c_int, [_void_p, _void_p, _void_p, _void_p, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, _void_p]),
-    "mpcasm_preview_direct": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p),
-                                             ctypes.POINTER(ctypes.c_int64), _void_p, _void_p,
-                                             _void_p, _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_assemble_jvp": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64)] +
-                            [_void_p] * 5 + [ctypes.c_int, _void_p]),
-    "mpcasm_assemble_vjp": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64)] +
-                            [_void_p] * 5 + [ctypes.c_int, _void_p]),
-    "mpcasm_assemble_adjoint_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_assemble_params_vjp": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64)] +
-                                   [_void_p] * 9 + [ctypes.c_int, _void_p]),
-    "mpcasm_assemble_params_vjp_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t,
-                                                       ctypes.POINTER(ctypes.c_int64),
-                                                       ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_goal_distance": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
-                                            _void_p, ctypes.c_int, ctypes.c_int, _void_p,
-                                            ctypes.c_int, _void_p]),
-    "mpcasm_preview_goal_distance": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p),
-                                                    ctypes.POINTER(ctypes.c_int64), _void_p, _void_p,
-                                                    _void_p, _void_p, ctypes.c_int, ctypes.c_int,
-                                                    _void_p, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_jit_stats": (ctypes.c_int, [_int64_p]),
+    "mpcasm_workspace_bytes": (ctypes.c_int, [_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "mpcasm_assemble": (ctypes.c_int, _PLAN_SRC + [_void_p] * 7 + [ctypes.c_int, _void_p]),
+    "mpcasm_preview_matrices": (ctypes.c_int, _PLAN_SRC + [_void_p, ctypes.c_int, _void_p]),
+    "mpcasm_preview": (ctypes.c_int, [_void_p, _void_p, _void_p, _void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_int, _void_p]),
+    "mpcasm_preview_direct": (ctypes.c_int, _PLAN_SRC + [_void_p, _void_p, _void_p, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_assemble_jvp": (ctypes.c_int, _PLAN_SRC + [_void_p] * 5 + [ctypes.c_int, _void_p]),
+    "mpcasm_assemble_vjp": (ctypes.c_int, _PLAN_SRC + [_void_p] * 5 + [ctypes.c_int, _void_p]),
+    "mpcasm_assemble_adjoint_info": (ctypes.c_int, _TABLES + [_int64_p, _int32_p]),
+    "mpcasm_assemble_params_vjp": (ctypes.c_int, _PLAN_SRC + [_void_p] * 9 + [ctypes.c_int, _void_p]),
+    "mpcasm_assemble_params_vjp_info": (ctypes.c_int, _TABLES + [_int64_p, _int32_p]),
+    "mpcasm_goal_distance": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64, _void_p, ctypes.c_int,
+                             ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_preview_goal_distance": (ctypes.c_int, _PLAN_SRC + [_void_p, _void_p, _void_p, _void_p, ctypes.c_int,
+                                     ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_admm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 + [ctypes.c_double] * 3 +
                     [ctypes.c_int, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_qp_solve": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] +
-                        [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
-                        [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_qp_solve_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_qp_solve_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] +
-                             [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
-                             [ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_qp_solve_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
-                                                 ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_qp_solve_soft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 + [ctypes.c_int, _void_p] +
-                             [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [_void_p] * 3 +
-                             [ctypes.c_int, _void_p, ctypes.c_int, _void_p, _void_p, _void_p, ctypes.c_int64]),
-    "mpcasm_qp_solve_soft_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_qp_solve_wide_soft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 7 +
-                                  [ctypes.c_int, _void_p] + [ctypes.c_double] * 6 + [ctypes.c_int] * 3 +
-                                  [_void_p] * 3 + [ctypes.c_int, _void_p, ctypes.c_int, _void_p, _void_p, _void_p,
-                                                   ctypes.c_int64]),
-    "mpcasm_qp_solve_wide_soft_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
-                                                      ctypes.POINTER(ctypes.c_int32)]),
+    "mpcasm_qp_solve": (ctypes.c_int, _QP_SOLVE),
+    "mpcasm_qp_solve_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _int64_p]),
+    "mpcasm_qp_solve_wide": (ctypes.c_int, _QP_SOLVE),
+    "mpcasm_qp_solve_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _int64_p, _int32_p]),
+    "mpcasm_qp_solve_soft": (ctypes.c_int, _QP_SOLVE + _QP_SOFT),
+    "mpcasm_qp_solve_soft_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _int64_p]),
+    "mpcasm_qp_solve_wide_soft": (ctypes.c_int, _QP_SOLVE + _QP_SOFT),
+    "mpcasm_qp_solve_wide_soft_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _int64_p, _int32_p]),
     "mpcasm_qp_polish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 + [ctypes.c_double, ctypes.c_int,
-                                                                                       _void_p, _void_p, ctypes.c_int,
-                                                                                       _void_p]),
-    "mpcasm_qp_polish_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_qp_polish_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 +
-                              [ctypes.c_double, ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p,
-                               ctypes.c_size_t, _void_p]),
-    "mpcasm_qp_polish_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                                  ctypes.POINTER(ctypes.c_int32)]),
+                         _void_p, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_qp_polish_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _int64_p]),
+    "mpcasm_qp_polish_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 8 + [ctypes.c_double,
+                              ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_size_t, _void_p]),
+    "mpcasm_qp_polish_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _int64_p, _int64_p,
+                                   _int32_p]),
     "mpcasm_qp_sens": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 9 + [ctypes.c_double, ctypes.c_int] +
                        [_void_p] * 6 + [ctypes.c_int, _void_p]),
-    "mpcasm_qp_sens_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_qp_sens_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 9 +
-                            [ctypes.c_double, ctypes.c_int] + [_void_p] * 6 +
-                            [ctypes.c_int, _void_p, ctypes.c_size_t, _void_p]),
-    "mpcasm_qp_sens_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                                ctypes.POINTER(ctypes.c_int32)]),
-    "mpcasm_qp_warm_store": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 4 + [ctypes.c_int] +
-                             [_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int,
-                                              _void_p]),
-    "mpcasm_qp_warm_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 6 +
-                             [ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [_void_p] * 3 +
-                             [ctypes.c_int, ctypes.c_uint32, ctypes.c_double] + [_void_p] * 5 +
-                             [ctypes.c_int, _void_p]),
+    "mpcasm_qp_sens_lds_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _int64_p]),
+    "mpcasm_qp_sens_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 9 + [ctypes.c_double,
+                            ctypes.c_int] + [_void_p] * 6 + [ctypes.c_int, _void_p, ctypes.c_size_t, _void_p]),
+    "mpcasm_qp_sens_wide_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _int64_p, _int64_p,
+                                 _int32_p]),
+    "mpcasm_qp_warm_store": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 4 + [ctypes.c_int] + [_void_p] *
+                             4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_qp_warm_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_void_p] * 6 + [ctypes.c_int64,
+                             ctypes.c_int, ctypes.c_int] + [_void_p] * 3 + [ctypes.c_int, ctypes.c_uint32,
+                             ctypes.c_double] + [_void_p] * 5 + [ctypes.c_int, _void_p]),
     "mpcasm_params_map": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, _void_p, ctypes.c_int, _void_p,
-                                         ctypes.c_int64, ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p]),
+                          ctypes.c_int64, ctypes.c_int, _void_p, _void_p, ctypes.c_int, _void_p]),
     "mpcasm_given_map_compile": (ctypes.c_int, [_void_p, _void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
-                                                ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_next_given": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
-                                         ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_uint32, _void_p,
-                                         ctypes.c_int64, _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_ltv_rollout_compile": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, _void_p, _void_p,
-                                                  ctypes.c_int, _void_p, ctypes.c_int, _void_p, ctypes.c_int64,
-                                                  ctypes.POINTER(ctypes.c_int64)]),
-    "mpcasm_ltv_rollout": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
-                                          ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_int64, _void_p,
-                                          ctypes.c_int, _void_p]),
-    "mpcasm_ltv_advance": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64), _void_p,
-                                          ctypes.c_int64, _void_p, _void_p, _void_p, ctypes.c_uint32, _void_p,
-                                          ctypes.c_int64, ctypes.c_int, _void_p]),
-    "mpcasm_ltv_rollout_info": (ctypes.c_int, [_void_p, ctypes.c_size_t, _void_p, ctypes.c_size_t, ctypes.c_int64,
-                                               ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
-                                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
+                                 _int64_p]),
+    "mpcasm_next_given": (ctypes.c_int, _PLAN_SRC + [_void_p, ctypes.c_int64, _void_p, _void_p, _void_p,
+                          ctypes.c_uint32, _void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_ltv_rollout_compile": (ctypes.c_int, _TABLES + [_void_p, _void_p, ctypes.c_int, _void_p, ctypes.c_int,
+                                   _void_p, ctypes.c_int64, _int64_p]),
+    "mpcasm_ltv_rollout": (ctypes.c_int, _PLAN_SRC + [_void_p, ctypes.c_int64, _void_p, _void_p, _void_p,
+                           ctypes.c_int64, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_ltv_advance": (ctypes.c_int, _PLAN_SRC + [_void_p, ctypes.c_int64, _void_p, _void_p, _void_p,
+                           ctypes.c_uint32, _void_p, ctypes.c_int64, ctypes.c_int, _void_p]),
+    "mpcasm_ltv_rollout_info": (ctypes.c_int, _TABLES + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _int32_p,
+                                _int64_p, _int32_p]),
     "mpcasm_ltv_lqr": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64] +
                        [_void_p] * 7),
     "mpcasm_ltv_close": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
-                                                             _void_p, ctypes.c_int64, ctypes.c_int64, _void_p,
-                                                             _void_p]),
+                         _void_p, ctypes.c_int64, ctypes.c_int64, _void_p, _void_p]),
     "mpcasm_ltv_augment": (ctypes.c_int, [ctypes.c_int] * 4 + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64,
-                                                               _void_p, ctypes.c_int64, ctypes.c_int64, _void_p,
-                                                               _void_p, _void_p, _void_p]),
-    "mpcasm_ltv_true_inputs": (ctypes.c_int, [_void_p, ctypes.POINTER(_void_p), ctypes.POINTER(ctypes.c_int64),
-                                              _void_p, ctypes.c_int64, _void_p, ctypes.c_int64, _void_p, _void_p,
-                                              _void_p, ctypes.c_int, _void_p]),
-    "mpcasm_gather": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p,
-                                     ctypes.c_int, _void_p]),
-    "mpcasm_box_transform": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p,
-                                            ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int64,
-                                            _void_p]),
-    "mpcasm_box_transform_ss": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p,
-                                               ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int,
-                                               ctypes.c_int, _void_p, ctypes.c_int64, _void_p]),
+                           _void_p, ctypes.c_int64, ctypes.c_int64, _void_p, _void_p, _void_p, _void_p]),
+    "mpcasm_ltv_true_inputs": (ctypes.c_int, _PLAN_SRC + [_void_p, ctypes.c_int64, _void_p, ctypes.c_int64, _void_p,
+                               _void_p, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_gather": (ctypes.c_int, [_void_p, ctypes.c_int64, _void_p, ctypes.c_int, _void_p, ctypes.c_int, _void_p]),
+    "mpcasm_box_transform": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p, ctypes.c_int,
+                             ctypes.c_int, _void_p, ctypes.c_int64, _void_p]),
+    "mpcasm_box_transform_ss": (ctypes.c_int, [_void_p, ctypes.c_int64, ctypes.c_int, _void_p, ctypes.c_int,
+                                ctypes.c_int, _void_p, ctypes.c_int, ctypes.c_int, _void_p, ctypes.c_int64, _void_p]),
 }
 KERNEL_NAMES = {0: "none", 1: "resident_assemble_kernel (persistent, ahead of time)",
                 2: "resident_spec_kernel (persistent, compiled for the plan by hiprtc)",

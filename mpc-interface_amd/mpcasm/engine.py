@@ -874,14 +874,24 @@ def checked_index(idx, rows):
 HALF_CU_LDS = 80 * 1024      # two workgroups of the persistent kernel share a CU's 160 KB
 
 
+def _table_args(plan):
+    """The four leading arguments of every entry that takes a plan's tables.  The arrays' ``.ctypes`` objects pass
+    as their addresses and keep the arrays alive as long as the tuple lives: hold it across the call."""
+    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
+    return itab.ctypes, itab.size, dtab.ctypes if dtab.size else None, dtab.size
+
+
+def _stride_arg(plan, src_stride):
+    """``h_src_stride`` of a host-only query: one entry per source of ``plan`` (None: every source shared)."""
+    n = len(plan.sources)
+    return (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
+
+
 def resident_lds_bytes(plan):
     """LDS bytes a workgroup of the persistent kernel needs for ``plan`` -- with ``P`` handed over
     directly, with ``P`` collected in LDS (``mpcasm_resident_lds_bytes``; 0: not on that kernel)."""
     out = (ctypes.c_int64 * 2)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    capi.check(capi.load().mpcasm_resident_lds_bytes(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, out),
-        "mpcasm_resident_lds_bytes")
+    capi.check(capi.load().mpcasm_resident_lds_bytes(*_table_args(plan), out), "mpcasm_resident_lds_bytes")
     return int(out[0]), int(out[1])
 
 
@@ -892,12 +902,8 @@ def preview_route(plan, src_stride=None, nterms=0, ngoals=0):
     ``(route, E1, R1, E2, R2, DIST, LDS bytes, whole LDS)`` with ``route`` one of ``capi.PREVIEW_*``, or
     ``None`` where the launch returns ``MPCASM_ERR_LIMIT``."""
     out = (ctypes.c_int32 * 8)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    n = len(plan.sources)
-    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
-    rc = capi.load().mpcasm_preview_route(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides,
-        int(nterms), int(ngoals), out)
+    rc = capi.load().mpcasm_preview_route(*_table_args(plan), _stride_arg(plan, src_stride), int(nterms),
+                                          int(ngoals), out)
     if rc == capi.ERR_LIMIT:
         return None
     capi.check(rc, "mpcasm_preview_route")
@@ -914,12 +920,8 @@ def adjoint_info(plan, src_stride=None):
     resident workgroups per CU)``.  Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launches
     refuse the plan (compiled with ``ltv=``, or one instance beyond a CU's LDS)."""
     out = (ctypes.c_int32 * 4)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    n = len(plan.sources)
-    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
-    capi.check(capi.load().mpcasm_assemble_adjoint_info(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides, out),
-        "mpcasm_assemble_adjoint_info")
+    capi.check(capi.load().mpcasm_assemble_adjoint_info(*_table_args(plan), _stride_arg(plan, src_stride), out),
+               "mpcasm_assemble_adjoint_info")
     return AdjointInfo(*(int(x) for x in out))
 
 
@@ -928,12 +930,8 @@ def params_adjoint_info(plan, src_stride=None):
     :class:`AdjointInfo` whose ``index_words`` are the words of the parameter index.  Raises
     :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the plan."""
     out = (ctypes.c_int32 * 4)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    n = len(plan.sources)
-    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
-    capi.check(capi.load().mpcasm_assemble_params_vjp_info(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides, out),
-        "mpcasm_assemble_params_vjp_info")
+    capi.check(capi.load().mpcasm_assemble_params_vjp_info(*_table_args(plan), _stride_arg(plan, src_stride), out),
+               "mpcasm_assemble_params_vjp_info")
     return AdjointInfo(*(int(x) for x in out))
 
 
@@ -944,9 +942,7 @@ def sweep_route(plan):
     Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the plan, with
     ``MPCASM_ERR_ARG`` for a plan that does not run on the sweep kernel."""
     out = (ctypes.c_int32 * 8)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    capi.check(capi.load().mpcasm_sweep_route(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, out), "mpcasm_sweep_route")
+    capi.check(capi.load().mpcasm_sweep_route(*_table_args(plan), out), "mpcasm_sweep_route")
     return tuple(int(x) for x in out)
 
 
@@ -966,12 +962,8 @@ def tiled_route(plan, batch, src_stride=None, want=capi.WANT_COST | capi.WANT_CO
     :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses the plan, with ``MPCASM_ERR_ARG``
     for a plan that does not run on the tiled path."""
     out = (ctypes.c_int32 * 16)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    n = len(plan.sources)
-    strides = (ctypes.c_int64 * max(n, 1))(*([0] * n if src_stride is None else [int(x) for x in src_stride]))
-    capi.check(capi.load().mpcasm_tiled_route(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, strides, int(batch),
-        int(want), int(path), out), "mpcasm_tiled_route")
+    capi.check(capi.load().mpcasm_tiled_route(*_table_args(plan), _stride_arg(plan, src_stride), int(batch),
+                                              int(want), int(path), out), "mpcasm_tiled_route")
     return TiledRoute(*(int(x) for x in out[:11]))
 
 
@@ -987,10 +979,8 @@ def assemble_route(plan, batch, path=0, aligned=True, indexed=False):
     the persistent or fused kernel, and whether the persistent kernel hands ``P`` over directly at this batch.
     Raises :class:`capi.MpcasmError` with ``MPCASM_ERR_LIMIT`` where the launch refuses."""
     out = (ctypes.c_int32 * 4)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    capi.check(capi.load().mpcasm_assemble_route(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, int(batch), int(path),
-        int(aligned), int(indexed), out), "mpcasm_assemble_route")
+    capi.check(capi.load().mpcasm_assemble_route(*_table_args(plan), int(batch), int(path), int(aligned),
+                                                 int(indexed), out), "mpcasm_assemble_route")
     return AssembleRoute(*(int(x) for x in out[:3]))
 
 
@@ -1008,10 +998,8 @@ def staged_route(plan, batch, want_cost=True, want_constraints=True):
     refuses (a limit of more than 8 axes with the constraints wanted), with ``MPCASM_ERR_ARG`` for a plan the
     pipeline cannot run (``ltv=``, ``lti=``, ``csc=``)."""
     out = (ctypes.c_int32 * 8)()
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
-    capi.check(capi.load().mpcasm_staged_route(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, int(bool(want_cost)),
-        int(bool(want_constraints)), int(batch), out), "mpcasm_staged_route")
+    capi.check(capi.load().mpcasm_staged_route(*_table_args(plan), int(bool(want_cost)), int(bool(want_constraints)),
+                                               int(batch), out), "mpcasm_staged_route")
     form, flags, a, b, k2, k3, grad, k4 = (int(x) for x in out)
     gemm = form == capi.STAGED_GEMM
     return StagedRoute(form, flags & capi.STAGED_SYM, a if gemm else 0, b if gemm else 0, 0 if gemm else a,
@@ -1033,10 +1021,9 @@ def rollout_table(plan, records=None, cvec=None, sizes=None):
         sw = plan.sweep or {}
         sizes = rollout_sizes(plan) if sw else np.zeros(7, dtype=np.int32)
     sizes = np.ascontiguousarray(sizes, dtype=np.int32)
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
     lib, words = capi.load(), ctypes.c_int64()
-    args = (itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, sizes.ctypes.data,
-            records.ctypes.data, records.shape[0], cvec.ctypes.data if cvec.size else None, cvec.shape[0])
+    args = _table_args(plan) + (sizes.ctypes.data, records.ctypes.data, records.shape[0],
+                                cvec.ctypes.data if cvec.size else None, cvec.shape[0])
     capi.check(lib.mpcasm_ltv_rollout_compile(*args, None, 0, ctypes.byref(words)), "mpcasm_ltv_rollout_compile")
     host = np.zeros(words.value, dtype=np.int32)
     capi.check(lib.mpcasm_ltv_rollout_compile(*args, host.ctypes.data, host.size, ctypes.byref(words)),
@@ -1052,12 +1039,10 @@ def rollout_info(plan, rows=True, count=1, table_words=None):
     the launch's own ``MPCASM_ERR_ARG`` / ``MPCASM_ERR_LIMIT``."""
     if table_words is None:
         table_words = rollout_table(plan).size
-    itab, dtab = np.ascontiguousarray(plan.itab), np.ascontiguousarray(plan.dtab)
     group, lds, groups = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
     capi.check(capi.load().mpcasm_ltv_rollout_info(
-        itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size, int(table_words),
-        1 if rows else 0, int(count), ctypes.byref(group), ctypes.byref(lds), ctypes.byref(groups)),
-        "mpcasm_ltv_rollout_info")
+        *_table_args(plan), int(table_words), 1 if rows else 0, int(count), ctypes.byref(group), ctypes.byref(lds),
+        ctypes.byref(groups)), "mpcasm_ltv_rollout_info")
     return group.value, lds.value, groups.value
 
 
@@ -1262,12 +1247,8 @@ class Assembler:
 
         lib = capi.load()
         self._handle = ctypes.c_void_p()
-        itab = np.ascontiguousarray(p.itab)
-        dtab = np.ascontiguousarray(p.dtab)
         with torch.cuda.device(self.device):
-            rc = lib.mpcasm_plan_create(
-                itab.ctypes.data, itab.size, dtab.ctypes.data if dtab.size else None, dtab.size,
-                ctypes.byref(self._handle))
+            rc = lib.mpcasm_plan_create(*_table_args(p), ctypes.byref(self._handle))
         capi.check(rc, "mpcasm_plan_create")
 
         # sources: shared copies of the formulation's horizon matrices
@@ -1519,6 +1500,18 @@ class Assembler:
             self._src_key, self._src_ctypes = key, (ptrs, strides)
         return self._src_ctypes
 
+    def _call_rc(self, name, *args, stream=None):
+        """The status of the entry ``name`` called the way every entry that takes the plan and its sources is:
+        ``name(plan, h_src, h_src_stride, *args, stream)`` with this assembler's device current."""
+        torch = self._torch
+        ptrs, strides = self._src_args()
+        with torch.cuda.device(self.device):
+            return getattr(capi.load(), name)(self._handle, ptrs, strides, *args, _stream_handle(torch, stream))
+
+    def _call(self, name, *args, stream=None):
+        """:meth:`_call_rc`, a status that is not ``MPCASM_OK`` raised."""
+        capi.check(self._call_rc(name, *args, stream=stream), name)
+
     def assemble(self, given=None, out=None, stream=None, want_cost=True, want_constraints=True,
                  count=None, index=None, params=None):
         """Assemble the batch; returns ``(P, q, G, h)`` device tensors (``None`` for a
@@ -1638,12 +1631,7 @@ class Assembler:
         W = self.ng + self.no
         PM = torch.empty((self.batch, self.plan.pmrows, W), dtype=torch.float64,
                          device=self.device)
-        ptrs, strides = self._src_args()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_preview_matrices(
-                self._handle, ptrs, strides, PM.data_ptr(), self.batch,
-                _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_preview_matrices")
+        self._call("mpcasm_preview_matrices", PM.data_ptr(), self.batch, stream=stream)
         return PM
 
     def preview_rows(self, given, optim, out=None, stream=None, count=None):
@@ -1664,14 +1652,9 @@ class Assembler:
             out = torch.empty((self.batch, self.plan.pmrows), dtype=torch.float64, device=self.device)
         else:
             _checked_out(torch, out, (n, self.plan.pmrows), self.device, "preview_rows")
-        ptrs, strides = self._src_args()
-        work = self._workspace()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_preview_direct(
-                self._handle, ptrs, strides, g.data_ptr() if g is not None else None,
-                x.data_ptr() if x is not None else None, out.data_ptr(), work.data_ptr(), n,
-                _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_preview_direct")
+        self._call("mpcasm_preview_direct", g.data_ptr() if g is not None else None,
+                   x.data_ptr() if x is not None else None, out.data_ptr(), self._workspace().data_ptr(), n,
+                   stream=stream)
         return out
 
     # ---- the derivative of the assembly with respect to `given` ---------------------------------
@@ -1721,13 +1704,8 @@ class Assembler:
         if dh is not None:
             _checked_out(torch, dh, (n, self.nc), self.device, "given_jvp dh")
         ptr = lambda t: t.data_ptr() if t is not None else None
-        ptrs, strides = self._src_args()
-        work = self._workspace()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_assemble_jvp(
-                self._handle, ptrs, strides, prm.data_ptr(), ptr(d), ptr(dq), ptr(dh), work.data_ptr(), n,
-                _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_assemble_jvp")
+        self._call("mpcasm_assemble_jvp", prm.data_ptr(), ptr(d), ptr(dq), ptr(dh), self._workspace().data_ptr(), n,
+                   stream=stream)
         return dq, dh
 
     def given_vjp(self, gq, gh, out=None, count=None, stream=None, params=None):
@@ -1747,13 +1725,8 @@ class Assembler:
             out[:n].zero_()
             return out
         ptr = lambda t: t.data_ptr() if t is not None else None
-        ptrs, strides = self._src_args()
-        work = self._workspace()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_assemble_vjp(
-                self._handle, ptrs, strides, prm.data_ptr(), ptr(gq), ptr(gh), out.data_ptr(),
-                work.data_ptr(), n, _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_assemble_vjp")
+        self._call("mpcasm_assemble_vjp", prm.data_ptr(), ptr(gq), ptr(gh), out.data_ptr(),
+                   self._workspace().data_ptr(), n, stream=stream)
         return out
 
     def adjoint_info(self):
@@ -1792,13 +1765,8 @@ class Assembler:
         else:
             _checked_out(torch, out, (n, width), self.device, "params_vjp")
         ptr = lambda t: t.data_ptr() if t is not None else None
-        ptrs, strides = self._src_args()
-        work = self._workspace()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_assemble_params_vjp(
-                self._handle, ptrs, strides, prm.data_ptr(), ptr(given), ptr(x), ptr(u), ptr(y), ptr(w),
-                ptr(verdict), out.data_ptr(), work.data_ptr(), n, _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_assemble_params_vjp")
+        self._call("mpcasm_assemble_params_vjp", prm.data_ptr(), ptr(given), ptr(x), ptr(u), ptr(y), ptr(w),
+                   ptr(verdict), out.data_ptr(), self._workspace().data_ptr(), n, stream=stream)
         return out
 
     def params_adjoint_info(self):
@@ -1952,15 +1920,10 @@ class Assembler:
                 raise ValueError("%s: a contiguous int32 tensor of >= %d entries on %s" % (name, n, self.device))
         if index is None and given.shape[0] < n:
             raise ValueError("given must have %d rows, got %d" % (n, given.shape[0]))
-        ptrs, strides = self._src_args()
-        work = self._workspace()
         ptr = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_next_given(
-                self._handle, ptrs, strides, given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index),
-                ptr(status), int(apply_mask) & 0xFFFFFFFF, gmap.table.data_ptr(), gmap.words, work.data_ptr(), n,
-                _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_next_given")
+        self._call("mpcasm_next_given", given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index), ptr(status),
+                   int(apply_mask) & 0xFFFFFFFF, gmap.table.data_ptr(), gmap.words, self._workspace().data_ptr(), n,
+                   stream=stream)
         return given
 
     # ---- a plan compiled as ltv: rows and the next given by the forward recursion ------------------------
@@ -2025,13 +1988,9 @@ class Assembler:
             out = torch.empty((self.batch, self.plan.pmrows), dtype=torch.float64, device=self.device)
         else:
             _checked_out(torch, out, (n, self.plan.pmrows), self.device, "rollout")
-        ptrs, strides = self._src_args()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_ltv_rollout(
-                self._handle, ptrs, strides, given.data_ptr(), given.shape[0], optim.data_ptr(),
-                index.data_ptr() if index is not None else None, table.data_ptr(), table.numel(), out.data_ptr(),
-                n, _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_ltv_rollout")
+        self._call("mpcasm_ltv_rollout", given.data_ptr(), given.shape[0], optim.data_ptr(),
+                   index.data_ptr() if index is not None else None, table.data_ptr(), table.numel(), out.data_ptr(),
+                   n, stream=stream)
         return out
 
     def advance(self, given, optim, index=None, status=None, apply_mask=APPLY_SOLVED, count=None, stream=None):
@@ -2050,14 +2009,9 @@ class Assembler:
                                        and status.device == self.device and status.is_contiguous()
                                        and status.dim() == 1 and status.numel() >= n):
             raise ValueError("status: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
-        ptrs, strides = self._src_args()
         ptr = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_ltv_advance(
-                self._handle, ptrs, strides, given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index),
-                ptr(status), int(apply_mask) & 0xFFFFFFFF, table.data_ptr(), table.numel(), n,
-                _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_ltv_advance")
+        self._call("mpcasm_ltv_advance", given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index), ptr(status),
+                   int(apply_mask) & 0xFFFFFFFF, table.data_ptr(), table.numel(), n, stream=stream)
         return given
 
     def true_inputs(self, K_seq, t, given, optim, index=None, out=None, count=None, stream=None):
@@ -2088,13 +2042,9 @@ class Assembler:
             out = torch.empty((self.batch, axes, N, m), dtype=torch.float64, device=self.device)
         else:
             _checked_out(torch, out, (cnt, axes, N, m), self.device, "true_inputs")
-        ptrs, strides = self._src_args()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_ltv_true_inputs(
-                self._handle, ptrs, strides, K_seq.data_ptr() + 8 * t * m * n, T * m * n if K_seq.dim() == 4 else 0,
-                given.data_ptr(), given.shape[0], optim.data_ptr(), index.data_ptr() if index is not None else None,
-                out.data_ptr(), cnt, _stream_handle(torch, stream))
-        capi.check(rc, "mpcasm_ltv_true_inputs")
+        self._call("mpcasm_ltv_true_inputs", K_seq.data_ptr() + 8 * t * m * n, T * m * n if K_seq.dim() == 4 else 0,
+                   given.data_ptr(), given.shape[0], optim.data_ptr(), index.data_ptr() if index is not None else None,
+                   out.data_ptr(), cnt, stream=stream)
         return out
 
     def goal_terms(self, form):
@@ -2155,13 +2105,9 @@ class Assembler:
             out = torch.empty((self.batch, len(names)), dtype=torch.float64, device=self.device)
         else:
             _checked_out(torch, out, (n, len(names)), self.device, "full_goal_distances")
-        ptrs, strides = self._src_args()
-        work = self._workspace()
-        with torch.cuda.device(self.device):
-            rc = capi.load().mpcasm_preview_goal_distance(
-                self._handle, ptrs, strides, g.data_ptr() if g is not None else None,
-                x.data_ptr() if x is not None else None, self.params.data_ptr(), table.data_ptr(),
-                table.shape[0], len(names), out.data_ptr(), work.data_ptr(), n, _stream_handle(torch, stream))
+        rc = self._call_rc("mpcasm_preview_goal_distance", g.data_ptr() if g is not None else None,
+                           x.data_ptr() if x is not None else None, self.params.data_ptr(), table.data_ptr(),
+                           table.shape[0], len(names), out.data_ptr(), self._workspace().data_ptr(), n, stream=stream)
         if rc == capi.ERR_LIMIT:
             rows = self.preview_rows(given, optim, stream=stream, count=count)
             return self.goal_distance(form, rows, out=out, stream=stream, count=count)
