@@ -142,8 +142,8 @@ std::vector<int32_t> jit_fetch_plan(const PlanDev& d, const int32_t* it, int lim
 std::string jit_spec_header(const PlanDev& d, const int32_t* it, int seg_limit) {
   std::string s = "// generated by libmpcasm (jit.hip) for one plan\n#pragma once\n"
                   "namespace mpcasm {\nnamespace spec {\nstruct PlanConst {\n";
-#define MPCASM_X(f) append(s, "  static constexpr int " #f " = %lld;\n", (long long)d.f);
-  MPCASM_PLAN_INT_FIELDS(MPCASM_X)
+#define MPCASM_X(f, ...) append(s, "  static constexpr int " #f " = %lld;\n", (long long)d.f);
+  MPCASM_PLAN_INT_FIELDS(MPCASM_X, MPCASM_X)
 #undef MPCASM_X
   append(s, "  static constexpr unsigned rs_src16 = %lldu;\n};\n", (long long)d.rs_src16);
   const int jc = d.rs_jc <= 3 ? 3 : d.rs_jc <= 4 ? 4 : d.rs_jc <= 5 ? 5 : d.rs_jc <= 8 ? 8 : RS_JC_MAX;

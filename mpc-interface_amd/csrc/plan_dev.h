@@ -10,31 +10,47 @@
 
 namespace mpcasm {
 
-// every int field of PlanDev, once: the struct and the constants of a specialised kernel (jit.hip) are
-// generated from this list; the fields are filled from the tables by hand (plan_check.cpp plan_view)
-#define MPCASM_PLAN_INT_FIELDS(X)                                                                   \
-  X(ng) X(no) X(nc) X(nparams) X(nsrc) X(nbase) X(nseg) X(rtot) X(nent) X(ngterm) X(nlimit)         \
-  X(nlax) X(pmrows) X(pm_nent) X(ldv) X(off_seg) X(off_colseg) X(off_rowptr) X(off_entbase)         \
-  X(off_entk) X(off_gterm) X(off_limit) X(off_lax) X(off_rowlimit) X(off_pm_rowptr)                 \
-  X(off_pm_entbase) X(off_pm_entk) X(doff_entcoef) X(doff_pm_entcoef) X(fused_ok) X(arena_total)    \
-  X(off_arena) X(nfd) X(off_fd_idx) X(off_fd_ptr) X(nops) X(off_op) X(ncoef) X(doff_coefpool)       \
-  X(max_axes) X(rs_sym_any) X(rs_ok) X(rs_jc) X(rs_sym) X(rs_ntrip) X(off_rs_src) X(off_rs_gidx)    \
-  X(off_rs_dst) X(doff_rs_coef) X(off_rs_trip) X(off_rs_wtrip) X(rs_nsplit) X(off_rs_split)         \
-  X(off_rs_rr) X(rs_unit) X(rs_nchunk) X(off_rs_inmeta) X(rs_img) X(rs_img_given)                   \
-  X(rs_img_params) X(doff_rs_const) X(rs_nlti) X(off_rs_lti) X(rs_img_dma) X(rs_ab)                 \
-  X(off_rs_abmeta) X(rr_packed) X(off_rs_dpar) X(doff_rs_dcoef) X(rs_ngdesc) X(off_rs_gdesc)        \
-  X(pm_nfd) X(off_pm_map) X(off_pm_fdptr) X(off_pm_op) X(doff_pm_pool) X(doff_diagcoef) X(ndiag)      \
-  X(rs_nzblk) X(off_rs_zblk) X(rs_p_direct) X(rs_gsingle)                                           \
-  X(csc_pnnz) X(off_csc_p) X(csc_gnnz) X(off_csc_g) X(csc_gsingle)                                  \
-  X(t_ci_ok) X(t_nop) X(off_t_cig) X(off_t_cio) X(t_doff_delta) X(t_ok) X(t_nstage)                 \
-  X(off_t_stage) X(t_nlti) X(off_t_lti) X(off_t_lti_ids) X(t_work) X(off_t_grow)                    \
-  X(off_t_srow) X(t_doff_scoef) X(off_t_pig) X(t_ngrest) X(off_t_grest) X(off_t_brow0) X(t_nbrow) X(t_toeplitz) X(rs_diag_table) X(off_t_bcolptr) X(off_t_bcols) \
-  X(rs_ngfix) X(off_rs_gfix) X(rs_compact) X(rs_ldv) X(rs_vd) X(rs_vrow0) X(off_rs_rrwin) X(t_np1) X(off_t_p1ptr) X(off_t_p1ent) X(off_t_p2y) \
-  X(t_scan) X(t_scan_nblk) X(off_t_scan_blk) X(off_t_scan_gt) X(t_doff_scan_gc) X(off_t_scan_grow)      \
-  X(t_doff_scan_gcoef) X(t_scan_ngrest) X(off_t_scan_grest) X(off_t_scan_colblk) X(t_scan_nother) \
-  X(sw_ok) X(sw_n) X(sw_m) X(sw_horizon) X(sw_src_a) X(sw_src_b) X(sw_naxes) X(off_sw_axis) X(sw_nterm)  \
-  X(off_sw_term) X(sw_nlim) X(off_sw_lim) X(off_sw_col) X(sw_doff_cvec) X(sw_ncvec) \
-  X(off_sw_cptr) X(off_sw_cent) X(sw_ncent) X(off_sw_gptr) X(off_sw_gent) X(sw_ngent) X(off_rs_prog) X(t_scan_fused)
+// every int field of PlanDev, once, in the struct's order: X(field, WORD) is copied from header word H_WORD of
+// itab, D(field) is derived from the tables by plan_view's own code (plan_check.cpp; rs_p_direct by host_plan).
+// The struct, plan_view's copies and the constants of a specialised kernel (jit.hip) are generated from this
+// list.  Eight header words have no field: MAGIC, VERSION, NITAB, NDTAB, NDIAGCOEF, PM_NOPS, PM_NPOOL, T_NDELTA.
+#define MPCASM_PLAN_INT_FIELDS(X, D)                                                                                    \
+  X(ng, NG) X(no, NO) X(nc, NC) X(nparams, NPARAMS) X(nsrc, NSRC) X(nbase, NBASE) X(nseg, NSEG) X(rtot, RTOT)           \
+  X(nent, NENT) X(ngterm, NGTERM) X(nlimit, NLIMIT) X(nlax, NLAX) X(pmrows, PMROWS) X(pm_nent, PM_NENT) X(ldv, LDV)     \
+  X(off_seg, OFF_SEG) X(off_colseg, OFF_COLSEG) X(off_rowptr, OFF_ROWPTR) X(off_entbase, OFF_ENTBASE)                   \
+  X(off_entk, OFF_ENTK) X(off_gterm, OFF_GTERM) X(off_limit, OFF_LIMIT) X(off_lax, OFF_LAX)                             \
+  X(off_rowlimit, OFF_ROWLIMIT) X(off_pm_rowptr, OFF_PM_ROWPTR) X(off_pm_entbase, OFF_PM_ENTBASE)                       \
+  X(off_pm_entk, OFF_PM_ENTK) X(doff_entcoef, DOFF_ENTCOEF) X(doff_pm_entcoef, DOFF_PM_ENTCOEF) X(fused_ok, FUSED_OK)   \
+  X(arena_total, ARENA_TOTAL) X(off_arena, OFF_ARENA) X(nfd, NFD) X(off_fd_idx, OFF_FD_IDX) X(off_fd_ptr, OFF_FD_PTR)   \
+  X(nops, NOPS) X(off_op, OFF_OP) X(ncoef, NCOEF) X(doff_coefpool, DOFF_COEFPOOL) D(max_axes) D(rs_sym_any)             \
+  X(rs_ok, RS_OK) X(rs_jc, RS_JC) X(rs_sym, RS_SYM) X(rs_ntrip, RS_NTRIP) X(off_rs_src, OFF_RS_SRC)                     \
+  X(off_rs_gidx, OFF_RS_GIDX) X(off_rs_dst, OFF_RS_DST) X(doff_rs_coef, DOFF_RS_COEF) X(off_rs_trip, OFF_RS_TRIP)       \
+  X(off_rs_wtrip, OFF_RS_WTRIP) X(rs_nsplit, RS_NSPLIT) X(off_rs_split, OFF_RS_SPLIT) X(off_rs_rr, OFF_RS_RR)           \
+  X(rs_unit, RS_UNIT) X(rs_nchunk, RS_NCHUNK) X(off_rs_inmeta, OFF_RS_INMETA) X(rs_img, RS_IMG)                         \
+  X(rs_img_given, RS_IMG_GIVEN) X(rs_img_params, RS_IMG_PARAMS) X(doff_rs_const, DOFF_RS_CONST) X(rs_nlti, RS_NLTI)     \
+  X(off_rs_lti, OFF_RS_LTI) X(rs_img_dma, RS_IMG_DMA) X(rs_ab, RS_AB) X(off_rs_abmeta, OFF_RS_ABMETA)                   \
+  X(rr_packed, RR_PACKED) X(off_rs_dpar, OFF_RS_DPAR) X(doff_rs_dcoef, DOFF_RS_DCOEF) X(rs_ngdesc, RS_NGDESC)           \
+  X(off_rs_gdesc, OFF_RS_GDESC) X(pm_nfd, PM_NFD) X(off_pm_map, OFF_PM_MAP) X(off_pm_fdptr, OFF_PM_FDPTR)               \
+  X(off_pm_op, OFF_PM_OP) X(doff_pm_pool, DOFF_PM_POOL) X(doff_diagcoef, DOFF_DIAGCOEF) D(ndiag) X(rs_nzblk, RS_NZBLK)  \
+  X(off_rs_zblk, OFF_RS_ZBLK) D(rs_p_direct) X(rs_gsingle, RS_GSINGLE) X(csc_pnnz, CSC_PNNZ) X(off_csc_p, OFF_CSC_P)    \
+  X(csc_gnnz, CSC_GNNZ) X(off_csc_g, OFF_CSC_G) X(csc_gsingle, CSC_GSINGLE) X(t_ci_ok, T_CI_OK) X(t_nop, T_NOP)         \
+  X(off_t_cig, OFF_T_CIG) X(off_t_cio, OFF_T_CIO) X(t_doff_delta, T_DOFF_DELTA) X(t_ok, T_OK) X(t_nstage, T_NSTAGE)     \
+  X(off_t_stage, OFF_T_STAGE) X(t_nlti, T_NLTI) X(off_t_lti, OFF_T_LTI) X(off_t_lti_ids, OFF_T_LTI_IDS)                 \
+  X(t_work, T_WORK) X(off_t_grow, OFF_T_GROW) X(off_t_srow, OFF_T_SROW) X(t_doff_scoef, T_DOFF_SCOEF)                   \
+  X(off_t_pig, OFF_T_PIG) X(t_ngrest, T_NGREST) X(off_t_grest, OFF_T_GREST) X(off_t_brow0, OFF_T_BROW0) D(t_nbrow)      \
+  X(t_toeplitz, T_TOEPLITZ) D(rs_diag_table) X(off_t_bcolptr, OFF_T_BCOLPTR) X(off_t_bcols, OFF_T_BCOLS)                \
+  X(rs_ngfix, RS_NGFIX) X(off_rs_gfix, OFF_RS_GFIX) X(rs_compact, RS_COMPACT) X(rs_ldv, RS_LDV) X(rs_vd, RS_VD)         \
+  X(rs_vrow0, RS_VROW0) X(off_rs_rrwin, OFF_RS_RRWIN) X(t_np1, T_NP1) X(off_t_p1ptr, OFF_T_P1PTR)                       \
+  X(off_t_p1ent, OFF_T_P1ENT) X(off_t_p2y, OFF_T_P2Y) X(t_scan, T_SCAN) X(t_scan_nblk, T_SCAN_NBLK)                     \
+  X(off_t_scan_blk, OFF_T_SCAN_BLK) X(off_t_scan_gt, OFF_T_SCAN_GT) X(t_doff_scan_gc, T_DOFF_SCAN_GC)                   \
+  X(off_t_scan_grow, OFF_T_SCAN_GROW) X(t_doff_scan_gcoef, T_DOFF_SCAN_GCOEF) X(t_scan_ngrest, T_SCAN_NGREST)           \
+  X(off_t_scan_grest, OFF_T_SCAN_GREST) X(off_t_scan_colblk, OFF_T_SCAN_COLBLK) X(t_scan_nother, T_SCAN_NOTHER)         \
+  X(sw_ok, SW_OK) X(sw_n, SW_N) X(sw_m, SW_M) X(sw_horizon, SW_HORIZON) X(sw_src_a, SW_SRC_A) X(sw_src_b, SW_SRC_B)     \
+  X(sw_naxes, SW_NAXES) X(off_sw_axis, OFF_SW_AXIS) X(sw_nterm, SW_NTERM) X(off_sw_term, OFF_SW_TERM)                   \
+  X(sw_nlim, SW_NLIM) X(off_sw_lim, OFF_SW_LIM) X(off_sw_col, OFF_SW_COL) X(sw_doff_cvec, SW_DOFF_CVEC)                 \
+  X(sw_ncvec, SW_NCVEC) X(off_sw_cptr, OFF_SW_CPTR) X(off_sw_cent, OFF_SW_CENT) X(sw_ncent, SW_NCENT)                   \
+  X(off_sw_gptr, OFF_SW_GPTR) X(off_sw_gent, OFF_SW_GENT) X(sw_ngent, SW_NGENT) X(off_rs_prog, OFF_RS_PROG)             \
+  X(t_scan_fused, T_SCAN_FUSED)
 
 // device-side view of a plan (pointers into the device copies of the tables).
 //   rs_p_direct: the persistent kernel sends the blocks of P straight to HBM (set by
@@ -44,8 +60,8 @@ namespace mpcasm {
 struct PlanDev {
   const int32_t* itab;
   const double* dtab;
-#define MPCASM_X(f) int f;
-  MPCASM_PLAN_INT_FIELDS(MPCASM_X)
+#define MPCASM_X(f, ...) int f;
+  MPCASM_PLAN_INT_FIELDS(MPCASM_X, MPCASM_X)
 #undef MPCASM_X
   unsigned rs_src16;
 };

@@ -1,5 +1,6 @@
 // plan_tables.h -- layout of the flat plan tables shared by the host plan
-// compiler (mpcasm/plan.py, which mirrors these constants) and the kernels.
+// compiler (mpcasm/plan.py, which reads this file through mpcasm/_tables.py: keep every
+// initialiser an integer expression over literals and earlier names) and the kernels.
 //
 // A plan is two arrays: int32 `itab` (structure) and double `dtab` (numbers
 // that are the same for every instance of the batch: definition coefficients

@@ -18,46 +18,24 @@ from types import SimpleNamespace
 import numpy as np
 import scipy.sparse as sp
 
-PLAN_MAGIC = 0x4D504341
-PLAN_VERSION = 30
+from . import _tables
 
-# header words (csrc/plan_tables.h, enum HeaderWord)
-_H = {name: i for i, name in enumerate([
-    "MAGIC", "VERSION", "NG", "NO", "NC", "NPARAMS", "NSRC", "NBASE", "NSEG", "RTOT", "NENT",
-    "NGTERM", "NLIMIT", "NLAX", "PMROWS", "PM_NENT", "LDV",
-    "OFF_SEG", "OFF_COLSEG", "OFF_ROWPTR", "OFF_ENTBASE", "OFF_ENTK", "OFF_GTERM", "OFF_LIMIT",
-    "OFF_LAX", "OFF_ROWLIMIT", "OFF_PM_ROWPTR", "OFF_PM_ENTBASE", "OFF_PM_ENTK",
-    "DOFF_ENTCOEF", "DOFF_PM_ENTCOEF", "NITAB", "NDTAB",
-    "FUSED_OK", "ARENA_TOTAL", "OFF_ARENA", "NFD", "OFF_FD_IDX", "OFF_FD_PTR", "NOPS", "OFF_OP",
-    "NCOEF", "DOFF_COEFPOOL",
-    "RS_OK", "RS_JC", "RS_SYM", "RS_NTRIP", "OFF_RS_SRC", "OFF_RS_GIDX", "OFF_RS_DST",
-    "DOFF_RS_COEF", "OFF_RS_TRIP", "OFF_RS_WTRIP", "RS_NSPLIT", "OFF_RS_SPLIT",
-    "OFF_RS_RR", "RS_UNIT", "RS_NCHUNK", "OFF_RS_INMETA", "RS_IMG", "RS_IMG_GIVEN",
-    "RS_IMG_PARAMS", "DOFF_RS_CONST", "DOFF_DIAGCOEF", "NDIAGCOEF", "RS_NLTI", "OFF_RS_LTI",
-    "RS_IMG_DMA", "RS_AB", "OFF_RS_ABMETA", "RR_PACKED", "OFF_RS_DPAR", "DOFF_RS_DCOEF",
-    "RS_NGDESC", "OFF_RS_GDESC", "PM_NFD", "OFF_PM_MAP", "OFF_PM_FDPTR", "OFF_PM_OP", "PM_NOPS",
-    "DOFF_PM_POOL", "PM_NPOOL", "RS_NZBLK", "OFF_RS_ZBLK", "RS_GSINGLE",
-    "CSC_PNNZ", "OFF_CSC_P", "CSC_GNNZ", "OFF_CSC_G", "CSC_GSINGLE",
-    "T_CI_OK", "T_NOP", "OFF_T_CIG", "OFF_T_CIO", "T_DOFF_DELTA", "T_NDELTA",
-    "T_OK", "T_NSTAGE", "OFF_T_STAGE", "T_NLTI", "OFF_T_LTI", "OFF_T_LTI_IDS", "T_WORK",
-    "OFF_T_GROW", "OFF_T_SROW", "T_DOFF_SCOEF", "OFF_T_PIG", "T_NGREST", "OFF_T_GREST", "OFF_T_BROW0", "OFF_T_BCOLPTR", "OFF_T_BCOLS", "T_TOEPLITZ",
-    "RS_NGFIX", "OFF_RS_GFIX", "RS_COMPACT", "RS_LDV", "RS_VD", "RS_VROW0", "OFF_RS_RRWIN",
-    "T_NP1", "OFF_T_P1PTR", "OFF_T_P1ENT", "OFF_T_P2Y",
-    "T_SCAN", "T_SCAN_NBLK", "OFF_T_SCAN_BLK", "OFF_T_SCAN_GT", "T_DOFF_SCAN_GC", "OFF_T_SCAN_GROW",
-    "T_DOFF_SCAN_GCOEF", "T_SCAN_NGREST", "OFF_T_SCAN_GREST", "OFF_T_SCAN_COLBLK", "T_SCAN_NOTHER",
-    "SW_OK", "SW_N", "SW_M", "SW_HORIZON", "SW_SRC_A", "SW_SRC_B", "SW_NAXES", "OFF_SW_AXIS", "SW_NTERM",
-    "OFF_SW_TERM", "SW_NLIM", "OFF_SW_LIM", "OFF_SW_COL", "SW_DOFF_CVEC", "SW_NCVEC",
-    "OFF_SW_CPTR", "OFF_SW_CENT", "SW_NCENT", "OFF_SW_GPTR", "OFF_SW_GENT", "SW_NGENT",
-    "OFF_RS_PROG", "T_SCAN_FUSED",
-])}
-H_WORDS = 160
-assert len(_H) <= H_WORDS
-RS_NW, RS_NT = 4, 512                     # matrix wavefronts (they fetch the inputs), threads per instance
-RS_WAVES = RS_NT // 64
-RS_BLOCKS_MAX = 255                       # 4-column blocks of the unknowns, a byte each
-RS_LTI_WORDS, RS_LTI_MAX = 8, 4           # record of a source group generated on chip; groups per plan
-RS_JC_MAX = 12                            # compose ops a thread can keep in registers
-RS_TRIP_WORDS = 8
+# The layout (csrc/plan_tables.h, where each name is explained), as _tables reads it: no value is restated here.
+globals().update({_n: _tables.VALUES[_n] for _n in """
+    PLAN_MAGIC PLAN_VERSION H_WORDS MAX_SOURCES SEG_WORDS GT_WORDS LM_WORDS LX_WORDS
+    GT_FLAG_P GT_FLAG_HALF GT_FLAG_DIAG
+    RS_NW RS_NT RS_WAVES RS_JC_MAX RS_TRIP_WORDS RS_BLOCKS_MAX RS_LTI_WORDS RS_LTI_MAX RS_AXMAX RS_RR_WORDS
+    RS_GDESC_PIECES RS_GDESC_THREADS RS_GFIX_NONE RS_DST_ACC RS_DIAG_MAX
+    RT_A RT_B RT_D RT_W RT_AIM RT_WORD RT_BI RT_BJ
+    RT_SHORT RT_HALF RT_NOP RT_FIRST RT_LAST RT_LIVE RT_QMASK RT_TERM_END
+    T_BLOCK T_SID_CONST T_STAGE_WORDS T_LTI_WORDS T_PIG_MAX
+    TS_FLAG_P TS_FLAG_HALF TS_FLAG_SIMPLE_A TS_FLAG_SIMPLE_B TS_FLAG_SAME TS_FLAG_G TS_FLAG_TOEPLITZ
+    T_SCAN_KMAX T_SCAN_BLKMAX T_SCAN_NMAX T_SCAN_GT_WORDS
+    SW_NMAX SW_MMAX SW_AXMAX SW_AXIS_WORDS SW_TERM_WORDS SW_LIM_WORDS SW_LAX_WORDS""".split()})
+SEG_GATHER, SEG_IDENTITY = _tables.VALUES["SEG_KIND_GATHER"], _tables.VALUES["SEG_KIND_IDENTITY"]
+# header words: name without its H_ -> index into itab
+_H = {_n[2:]: _tables.VALUES[_n] for _n in _tables.ENUMS["HeaderWord"] if _n != "H_WORDS"}
+
 # cost model of the wavefront assignment (rounded cycles of one wavefront), see _resident_program
 TRIP_COST, TRIP_STEP_COST, TERM_COST, TRIP_Q_COST, PACK_COST, G_PIECE_COST = 200, 30, 60, 60, 250, 500
 G_DESC_PIECE_COST = 330     # ... a piece of G by the descriptor table (small problems; stamps: 1 950 cycles for six)
@@ -74,32 +52,9 @@ if _os.environ.get("MPCASM_TRIP_COSTS"):          # tuning aid: "trip,step,term,
     if len(_c) > 6:
         TABLES_COST, STREAM_WAVE_COST, FETCH_CHUNK_COST = _c[6:9]
         TABLES_COST_GENERAL = TABLES_COST
-# trip record (csrc/plan_tables.h RT_*): words A, B, D, W, AIM, WORD, BI, BJ;
-# WORD = rows (16 or 4) | short << 5 | half << 6 | nop << 7 | first << 8 | last << 9 | live << 10
-#        | qmask << 14 | last trip of its term in the pack << 18
-RT_A, RT_B, RT_D, RT_W, RT_AIM, RT_WORD, RT_BI, RT_BJ = range(8)
-RT_SHORT, RT_HALF, RT_NOP, RT_FIRST, RT_LAST, RT_LIVE, RT_QMASK, RT_TERM_END = 5, 6, 7, 8, 9, 10, 14, 18
-RS_DIAG_MAX = 2                           # diagonal gterms per column (persistent kernel)
-RS_AXMAX = 4                              # axes per constraint row record
-RS_DST_ACC = 1 << 30                      # compose destination shared by two threads
-RS_GDESC_PIECES, RS_GDESC_THREADS = 6, 256   # descriptor table of G: pieces per stream-wave thread
-RS_GFIX_NONE = 7
 RS_COMPACT_FROM_BYTES = 65536           # a dense workspace beyond this is compacted (tools/ab_workspace.py)
-RS_RR_WORDS = 16                          # row record: voff[4], arrow param[4], center param[4], naxes, extreme param, pad
-SEG_WORDS, GT_WORDS, LM_WORDS, LX_WORDS = 8, 10, 12, 2
 FUSED_MAX_OPS = 1 << 18           # beyond this the staged pipeline is used
 FUSED_MAX_ARENA = 1 << 14         # doubles
-SEG_GATHER, SEG_IDENTITY = 0, 1
-GT_FLAG_P, GT_FLAG_HALF, GT_FLAG_DIAG = 1, 2, 4
-MAX_SOURCES = 32
-# tiled kernel (csrc/tiled.hip, plan_tables.h T_* / TS_* / TL_*)
-T_BLOCK, T_SID_CONST, T_STAGE_WORDS, T_LTI_WORDS = 128, 32, 16, 8
-TS_FLAG_P, TS_FLAG_HALF, TS_FLAG_SIMPLE_A, TS_FLAG_SIMPLE_B, TS_FLAG_SAME, TS_FLAG_G, TS_FLAG_TOEPLITZ = 1, 2, 4, 8, 16, 32, 64
-T_PIG_MAX = 2
-# scan form of the tiled kernel (csrc/tiled.hip toeplitz_scan_kernel, plan_tables.h T_SCAN*)
-T_SCAN_KMAX, T_SCAN_BLKMAX, T_SCAN_NMAX, T_SCAN_GT_WORDS = 16, 8, 64, 4
-# sweep kernel (csrc/sweep.hip, plan_tables.h SW_*): per-step dynamics, the Hessian by two recursions
-SW_NMAX, SW_MMAX, SW_AXMAX, SW_AXIS_WORDS, SW_TERM_WORDS, SW_LIM_WORDS, SW_LAX_WORDS = 4, 4, 4, 8, 8, 8, 8
 
 
 class Source:

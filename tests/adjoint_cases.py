@@ -14,6 +14,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from mpcasm._tables import VALUES
 from mpcasm.plan import (GT_FLAG_DIAG, GT_FLAG_HALF, GT_WORDS, LM_WORDS, LX_WORDS)
 
 N, NS, NI = 6, 3, 1
@@ -23,10 +24,10 @@ Case = namedtuple("Case", "name kind streams")
 CASES = [Case("%s-%s" % (kind, streams), kind, streams) for kind in ("mix", "diag") for streams in STREAMS]
 IDS = [c.name for c in CASES]
 
-# GT_* / LM_* / LX_* word offsets (csrc/plan_tables.h)
-GT_AOFF, GT_BOFF, GT_NROWS, GT_WPARAM, GT_DOFF, GT_AIMPARAM, GT_FLAGS = range(7)
-LM_OUT0, LM_NROWS, LM_NAXES, LM_LAX0, LM_ARROW_P, LM_ARROW_ROWS = range(6)
-LX_ROWOFF, LX_ROWS = range(2)
+# word offsets inside a gterm, a limit and a limit-axis record
+globals().update({n: VALUES[n] for n in (
+    "GT_AOFF GT_BOFF GT_NROWS GT_WPARAM GT_DOFF GT_AIMPARAM GT_FLAGS LX_ROWOFF LX_ROWS LM_OUT0 LM_NROWS LM_NAXES LM_LAX0 "
+    "LM_ARROW_P LM_ARROW_ROWS LM_CENTER_P LM_CENTER_ROWS LM_EXTREME_P LM_EXTREME_ROWS").split()})
 
 
 def build(api, rng, kind, plant=None):

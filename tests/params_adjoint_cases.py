@@ -5,9 +5,9 @@ per-instance set-up of a case (parameters, sources, long-double Jacobians)."""
 import numpy as np
 
 import adjoint_cases as ac
+from adjoint_cases import LM_CENTER_P, LM_CENTER_ROWS, LM_EXTREME_P, LM_EXTREME_ROWS
 from mpcasm import plan as P
 
-LM_CENTER_P, LM_CENTER_ROWS, LM_EXTREME_P, LM_EXTREME_ROWS = 6, 7, 8, 9   # (csrc/plan_tables.h)
 WIDEST = 10     # rounded operations of the widest contribution (a row of a gterm with a Hessian part, below)
 
 

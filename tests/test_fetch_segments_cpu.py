@@ -16,9 +16,10 @@ import numpy as np
 import pytest
 
 from mpcasm import capi, engine, problems
+from mpcasm._tables import VALUES
 from mpcasm.plan import _H, compile_plan
 
-LIMIT = 8                                     # runs per chunk the kernel takes (plan_tables.h FS_MAX)
+LIMIT = VALUES["FS_MAX"]                      # runs per chunk the kernel takes
 
 
 def biped(api, samples, times, reduced=False):

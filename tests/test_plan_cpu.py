@@ -376,23 +376,33 @@ def test_invalid_problems_raise(cpu_api):
         compile_plan(form)
 
 
-def test_header_slots_agree_with_the_kernels_enum():
-    """The table header is written by mpcasm/plan.py and read by csrc/plan_tables.h: same
-    slots in the same order, same constants."""
-    import os
-    import re
-
+def test_the_reader_of_the_layout_header(tmp_path):
+    """mpcasm/plan.py takes the layout from csrc/plan_tables.h through mpcasm/_tables.py: one literal per
+    syntactic form the reader handles, and a header it cannot evaluate is refused, not skipped."""
     import mpcasm.plan as P
+    from mpcasm import _tables
 
-    text = open(os.path.join(os.path.dirname(__file__), "..", "mpc-interface_amd", "csrc",
-                             "plan_tables.h")).read()
-    body = text[text.index("H_MAGIC = 0"):text.index("H_WORDS =")]
-    names = re.findall(r"^\s*H_([A-Z0-9_]+)\s*(?:=\s*\d+\s*)?,", body, flags=re.M)
-    assert names == [n for n, _ in sorted(P._H.items(), key=lambda kv: kv[1])]
-    for const in ("PLAN_VERSION", "H_WORDS", "RS_TRIP_WORDS", "RS_RR_WORDS", "RS_LTI_WORDS",
-                  "RS_BLOCKS_MAX"):
-        m = re.search(r"\b%s\s*=\s*(\d+)" % const, text)
-        assert m and int(m.group(1)) == getattr(P, const), const
+    V, words = _tables.VALUES, _tables.ENUMS["HeaderWord"]
+    assert P.PLAN_MAGIC == V["PLAN_MAGIC"] == 0x4D504341                     # hex
+    assert words[-1] == "H_WORDS" and P.H_WORDS == V["H_WORDS"] == 160
+    assert list(P._H.items()) == [(n[2:], V[n]) for n in words[:-1]] and list(P._H.values()) == list(range(158))
+    assert P._H["T_SCAN_FUSED"] == 157
+    assert P.RS_GDESC_THREADS == 256 and P.RS_WAVES == 8                     # expressions over earlier names
+    assert P.RS_DST_ACC == 1 << 30
+    assert V["LM_EXTREME_ROWS"] == 9 and P.RT_BJ == 7                        # implicit counting
+    assert P.T_STAGE_WORDS == 16 and P.RT_TERM_END == 18                     # explicit values inside an enum
+    assert P.SW_LAX_WORDS == 8                                               # a declaration spanning two lines
+    assert (P.SEG_GATHER, P.SEG_IDENTITY) == (V["SEG_KIND_GATHER"], V["SEG_KIND_IDENTITY"]) == (0, 1)
+    text = open(_tables.HEADER).read()
+    for good, bad in (("RS_GFIX_NONE = 7", "RS_GFIX_NONE = foo(3)"), ("T_STAGE_WORDS = 16", "T_STAGE_WORDS = 16u"),
+                      ("RS_WAVES = RS_NT / 64", "RS_WAVES = RS_NTT / 64"), ("T_PIG_MAX = 2", "T_PIG_MAX"),
+                      ("constexpr int T_PIG_MAX", "constexpr double T_PIG_MAX")):
+        assert text.count(good) == 1, good
+        (tmp_path / "bad.h").write_text(text.replace(good, bad))
+        with pytest.raises(ValueError):                 # a call, a suffix, an unknown name, no value, another type
+            _tables.read(str(tmp_path / "bad.h"))
+    with pytest.raises(OSError):
+        _tables.read(str(tmp_path / "absent.h"))
 
 
 def test_plan_tables_rejected_or_accepted_by_the_library(cpu_api):
@@ -423,14 +433,10 @@ def test_plan_tables_rejected_or_accepted_by_the_library(cpu_api):
 
 
 def record_fields(first):
-    """Index of every field of the record whose enum in csrc/plan_tables.h starts with ``first = 0``."""
-    import os
-    import re
+    """Index of every field of the record whose enum in the layout header starts with ``first``."""
+    from mpcasm import _tables
 
-    text = open(os.path.join(os.path.dirname(__file__), "..", "mpc-interface_amd", "csrc", "plan_tables.h")).read()
-    body = re.search(r"enum\s*\{\s*(%s = 0,[^}]*)\}" % first, text).group(1)
-    names = [n.split("=")[0].strip() for n in body.split(",")]
-    return {n: i for i, n in enumerate(names) if n and not n.endswith("_WORDS")}
+    return {n: _tables.VALUES[n] for n in _tables.ENUMS[first] if not n.endswith("_WORDS")}
 
 
 def test_a_limit_whose_rows_overflow_is_refused(cpu_api, tmp_path):

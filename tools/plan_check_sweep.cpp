@@ -12,10 +12,13 @@
 //
 // With a stride S > 1 (third argument) only the header, every S-th word and the `dense` words (fourth argument,
 // default 64) behind every section's start and before it are swept: for plans whose full sweep takes too long.
+// With `view` in the stride's place nothing is swept: plan_view's result is printed, every int field of PlanDev by
+// name and rs_src16 -- what a change of the field list (csrc/plan_dev.h) is compared against (profiles/plan_view.txt).
 #include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -50,7 +53,7 @@ T* read_exact(const char* path, size_t* count) {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    fprintf(stderr, "usage: %s ITAB DTAB [stride [dense]]\n", argv[0]);
+    fprintf(stderr, "usage: %s ITAB DTAB [stride [dense] | view]\n", argv[0]);
     return 2;
   }
   size_t n = 0, nd = 0;
@@ -60,6 +63,18 @@ int main(int argc, char** argv) {
   if (validate_plan(it, dt, n, nd) != MPCASM_OK) {
     fprintf(stderr, "%s: the untouched tables are refused\n", argv[1]);
     return 1;
+  }
+  if (argc > 3 && !strcmp(argv[3], "view")) {
+    PlanDev d = {};  // (rs_p_direct is not plan_view's: it stays 0)
+    plan_view(it, &d);
+    printf("%s: sizeof(PlanDev) %zu\n", argv[1], sizeof(PlanDev));
+#define SHOW(f, ...) printf("  %s %d\n", #f, d.f);
+    MPCASM_PLAN_INT_FIELDS(SHOW, SHOW)
+#undef SHOW
+    printf("  rs_src16 %u\n", d.rs_src16);
+    free(it);
+    free(dt);
+    return 0;
   }
   // where sections start: every header word that can be an offset into itab
   std::vector<size_t> starts;
