@@ -54,6 +54,49 @@ def _as_device(torch, x, device):
     return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=device)
 
 
+def _tensor(torch, t, dtype, shape, device, what, at_least=False):
+    """``t`` where it is a contiguous tensor of ``dtype`` and ``shape`` on ``device``, else ``ValueError(what)`` -- or,
+    for a caller with more to ask and a text of its own, None where ``what`` is None.  ``shape``: None for any, or a
+    tuple whose None entries stand for any size; ``at_least``: ``shape[0]`` is the fewest rows.  ``device``: None for
+    any HIP device."""
+    ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() \
+        and (t.is_cuda if device is None else t.device == device)
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(
+            want is None or have == want or (at_least and i == 0 and have > want)
+            for i, (have, want) in enumerate(zip(t.shape, shape)))
+    if not ok and what is not None:
+        raise ValueError(what)
+    return t if ok else None
+
+
+def _iterates(sol_or_xyz):
+    """``x, y, z, res`` of a :class:`QpSolution` or of ``(x, y, z)`` (``res`` None)."""
+    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
+        return sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z, sol_or_xyz.res
+    x, y, z = sol_or_xyz
+    return x, y, z, None
+
+
+def _wide_work(torch, info, no, nc, batch, work, device):
+    """The workspace of a wide KKT solve as the entry takes it, ``(address, bytes)``: sized by ``info`` (the entry's
+    ``*_wide_info``), allocated when ``work`` is None."""
+    need = info(no, nc, batch)[1]
+    if work is None:
+        work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=device)
+    if _tensor(torch, work, torch.uint8, None, device, None) is None:
+        _tensor(torch, work, torch.float64, None, device, "work: a contiguous uint8 or float64 tensor on P's device")
+    return work.data_ptr(), work.numel() * work.element_size()
+
+
+def _query(entry, args, *outs):
+    """A host-only size query of the C boundary: ``entry`` called with the integers ``args`` and one out-parameter
+    per ctypes type of ``outs``; ``MpcasmError`` where it refuses, else the values it wrote, as ints."""
+    outs = [kind() for kind in outs]
+    capi.check(getattr(capi.load(), entry)(*(int(a) for a in args), *(ctypes.byref(o) for o in outs)), entry)
+    return tuple(int(o.value) for o in outs)
+
+
 # --------------------------------------------------------------------------
 # K1
 # --------------------------------------------------------------------------
@@ -127,8 +170,7 @@ def _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid):
     """The checks :func:`admm` and :func:`solve_qp` share: ``batch, no, nc, warm, x, y, z`` with the
     iterates of a cold start allocated."""
     for t in (P, q, G, h):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError("P, q, G, h: contiguous float64 device tensors")
+        _tensor(torch, t, torch.float64, None, None, "P, q, G, h: contiguous float64 device tensors")
     if P.dim() != 3 or P.shape[1] != P.shape[2] or q.shape != P.shape[:2] or G.dim() != 3 or \
             G.shape[0] != P.shape[0] or G.shape[2] != P.shape[1] or h.shape != G.shape[:2]:
         raise ValueError("shapes: P (B, no, no), q (B, no), G (B, nc, no), h (B, nc)")
@@ -138,16 +180,15 @@ def _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid):
         if x is None or y is None or z is None:
             raise ValueError("a warm start takes x, y and z")
         for t, shape in ((x, (batch, no)), (y, (batch, nc)), (z, (batch, nc))):
-            if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == torch.float64
-                    and t.is_contiguous() and tuple(t.shape) == shape):
-                raise ValueError("x (B, no), y (B, nc), z (B, nc): contiguous float64 tensors on P's device")
+            _tensor(torch, t, torch.float64, shape, P.device,
+                    "x (B, no), y (B, nc), z (B, nc): contiguous float64 tensors on P's device")
     else:
         x = torch.empty((batch, no), dtype=torch.float64, device=P.device)
         y = torch.empty((batch, nc), dtype=torch.float64, device=P.device)
         z = torch.empty((batch, nc), dtype=torch.float64, device=P.device)
-    if kinv is not None and not (isinstance(kinv, torch.Tensor) and kinv.device == P.device and kinv.dtype == torch.float64
-                                 and kinv.is_contiguous() and tuple(kinv.shape) == (batch, no, no)):
-        raise ValueError("kinv: a contiguous float64 (B, no, no) tensor on P's device")
+    if kinv is not None:
+        _tensor(torch, kinv, torch.float64, (batch, no, no), P.device,
+                "kinv: a contiguous float64 (B, no, no) tensor on P's device")
     if kinv_valid and kinv is None:
         raise ValueError("kinv_valid without kinv")
     return batch, no, nc, warm, x, y, z
@@ -226,15 +267,9 @@ def solve_qp(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps
     models the hard problem.  Scalars and arrays are copied to the device here, on torch's current stream, in
     tensors that are freed on return: a caller that passes ``stream=`` or captures a graph must pass contiguous
     float64 DEVICE tensors (:meth:`Assembler.soft_rows`), which are handed on as they are."""
-    if polish and soft is not None:
-        raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
-    sol = _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
-                    max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out,
-                    warm_out=warm, soft=soft)
-    if not polish:
-        return sol
-    verdict = polish_qp(P, q, G, h, sol, status=sol.status, stream=stream)[3]
-    return PolishedQpSolution(*sol, verdict)
+    return _solve_qp("mpcasm_qp_solve", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
+                     max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out,
+                     warm_out=warm, soft=soft, polish=polish_qp if polish else None)
 
 
 def polish_qp(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE, stream=None,
@@ -255,10 +290,7 @@ def polish_qp(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine_iter
 def qp_polish_lds_bytes(no, nc):
     """LDS bytes one instance of :func:`polish_qp` takes; ``MpcasmError`` with ``ERR_LIMIT`` when that is more
     than a workgroup may have (``mpcasm_qp_polish_lds_bytes``)."""
-    out = ctypes.c_int64()
-    rc = capi.load().mpcasm_qp_polish_lds_bytes(int(no), int(nc), ctypes.byref(out))
-    capi.check(rc, "mpcasm_qp_polish_lds_bytes")
-    return int(out.value)
+    return _query("mpcasm_qp_polish_lds_bytes", (no, nc), ctypes.c_int64)[0]
 
 
 def polish_qp_wide(P, q, G, h, sol_or_xyz, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE,
@@ -278,10 +310,7 @@ def _polish_qp(entry, P, q, G, h, sol_or_xyz, status, delta, refine_iters, strea
     """:func:`polish_qp` and :func:`polish_qp_wide` through the C entry ``entry``; ``wide``: the entry takes the
     workspace ``work`` (allocated when None) and its size in bytes."""
     torch = require_device()
-    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
-        x, y, z, res = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z, sol_or_xyz.res
-    else:
-        (x, y, z), res = sol_or_xyz, None
+    x, y, z, res = _iterates(sol_or_xyz)
     if x is None or y is None or z is None:
         raise ValueError("%s takes the iterates x, y and z" % ("polish_qp_wide" if wide else "polish_qp"))
     batch, no, nc, _warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, None, False)
@@ -294,18 +323,9 @@ def _polish_qp(entry, P, q, G, h, sol_or_xyz, status, delta, refine_iters, strea
         res = torch.full((batch, 2), float("nan"), dtype=torch.float64, device=P.device)
     for t, dtype, shape in ((verdict, torch.int32, (batch,)), (res, torch.float64, (batch, 2))) + \
             (((status, torch.int32, (batch,)),) if status is not None else ()):
-        if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
-                and tuple(t.shape) == shape):
-            raise ValueError("status, polish (B,) int32 and res (B, 2) float64: contiguous, on P's device")
-    extra = ()
-    if wide:
-        need = qp_polish_wide_info(no, nc, batch)[1]
-        if work is None:
-            work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=P.device)
-        if not (isinstance(work, torch.Tensor) and work.device == P.device and work.is_contiguous()
-                and work.dtype in (torch.uint8, torch.float64)):
-            raise ValueError("work: a contiguous uint8 or float64 tensor on P's device")
-        extra = (work.data_ptr(), work.numel() * work.element_size())
+        _tensor(torch, t, dtype, shape, P.device,
+                "status, polish (B,) int32 and res (B, 2) float64: contiguous, on P's device")
+    extra = _wide_work(torch, qp_polish_wide_info, no, nc, batch, work, P.device) if wide else ()
     with torch.cuda.device(P.device):
         rc = getattr(capi.load(), entry)(no, nc, P.data_ptr(), q.data_ptr(), G.data_ptr(), h.data_ptr(),
                                          x.data_ptr(), y.data_ptr(), z.data_ptr(),
@@ -320,11 +340,7 @@ def qp_polish_wide_info(no, nc, batch):
     """``(lds_bytes, work_bytes, workgroups)`` of :func:`polish_qp_wide` on ``batch`` instances: the LDS of a
     workgroup, the workspace the call needs and the workgroups it launches, ``min(batch, capi.POLISH_WIDE_CAP)``;
     ``MpcasmError`` with ``ERR_LIMIT`` past its size limit (``mpcasm_qp_polish_wide_info``).  Needs no device."""
-    lds, work, groups = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-    rc = capi.load().mpcasm_qp_polish_wide_info(int(no), int(nc), int(batch), ctypes.byref(lds), ctypes.byref(work),
-                                                ctypes.byref(groups))
-    capi.check(rc, "mpcasm_qp_polish_wide_info")
-    return int(lds.value), int(work.value), int(groups.value)
+    return _query("mpcasm_qp_polish_wide_info", (no, nc, batch), ctypes.c_int64, ctypes.c_int64, ctypes.c_int32)
 
 
 # ---- the derivative of a solve: one more solve with the polish's KKT system --------------------------------------
@@ -370,13 +386,9 @@ def _qp_sens(entry, P, G, h, sol_or_xyz, rx, ry, status, delta, refine_iters, wa
              work=None):
     """:func:`qp_sensitivity` and :func:`qp_sensitivity_wide` through the C entry ``entry``."""
     torch = require_device()
-    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
-        x, y, z = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z
-    else:
-        x, y, z = sol_or_xyz
+    x, y, z, _ = _iterates(sol_or_xyz)
     for t in (P, G, h):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError("P, G, h: contiguous float64 device tensors")
+        _tensor(torch, t, torch.float64, None, None, "P, G, h: contiguous float64 device tensors")
     if P.dim() != 3 or P.shape[1] != P.shape[2] or G.dim() != 3 or G.shape[0] != P.shape[0] or \
             G.shape[2] != P.shape[1] or h.shape != G.shape[:2]:
         raise ValueError("shapes: P (B, no, no), G (B, nc, no), h (B, nc)")
@@ -400,19 +412,10 @@ def _qp_sens(entry, P, G, h, sol_or_xyz, rx, ry, status, delta, refine_iters, wa
     checked += [(gP, torch.float64, (batch, no, no))] if gP is not None else []
     checked += [(gG, torch.float64, (batch, nc, no))] if gG is not None else []
     for t, dtype, shape in checked:
-        if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype and t.is_contiguous()
-                and tuple(t.shape) == shape):
-            raise ValueError("x, rx, u (B, no), y, z, ry, w (B, nc), gP (B, no, no), gG (B, nc, no), lres (B,) float64 "
-                             "and status, verdict (B,) int32: contiguous, on P's device")
-    extra = ()
-    if wide:
-        need = qp_sens_wide_info(no, nc, batch)[1]
-        if work is None:
-            work = torch.empty((max(need, 16) // 8,), dtype=torch.float64, device=P.device)
-        if not (isinstance(work, torch.Tensor) and work.device == P.device and work.is_contiguous()
-                and work.dtype in (torch.uint8, torch.float64)):
-            raise ValueError("work: a contiguous uint8 or float64 tensor on P's device")
-        extra = (work.data_ptr(), work.numel() * work.element_size())
+        _tensor(torch, t, dtype, shape, P.device,
+                "x, rx, u (B, no), y, z, ry, w (B, nc), gP (B, no, no), gG (B, nc, no), lres (B,) float64 "
+                "and status, verdict (B,) int32: contiguous, on P's device")
+    extra = _wide_work(torch, qp_sens_wide_info, no, nc, batch, work, P.device) if wide else ()
     ptr = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(P.device):
         rc = getattr(capi.load(), entry)(no, nc, P.data_ptr(), G.data_ptr(), h.data_ptr(), x.data_ptr(), y.data_ptr(),
@@ -427,20 +430,13 @@ def _qp_sens(entry, P, G, h, sol_or_xyz, rx, ry, status, delta, refine_iters, wa
 def qp_sens_lds_bytes(no, nc):
     """LDS bytes one instance of :func:`qp_sensitivity` takes -- :func:`qp_polish_lds_bytes`' figure and limit
     (``mpcasm_qp_sens_lds_bytes``).  Needs no device."""
-    out = ctypes.c_int64()
-    rc = capi.load().mpcasm_qp_sens_lds_bytes(int(no), int(nc), ctypes.byref(out))
-    capi.check(rc, "mpcasm_qp_sens_lds_bytes")
-    return int(out.value)
+    return _query("mpcasm_qp_sens_lds_bytes", (no, nc), ctypes.c_int64)[0]
 
 
 def qp_sens_wide_info(no, nc, batch):
     """``(lds_bytes, work_bytes, workgroups)`` of :func:`qp_sensitivity_wide` on ``batch`` instances --
     :func:`qp_polish_wide_info`'s figures and limit (``mpcasm_qp_sens_wide_info``).  Needs no device."""
-    lds, work, groups = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-    rc = capi.load().mpcasm_qp_sens_wide_info(int(no), int(nc), int(batch), ctypes.byref(lds), ctypes.byref(work),
-                                              ctypes.byref(groups))
-    capi.check(rc, "mpcasm_qp_sens_wide_info")
-    return int(lds.value), int(work.value), int(groups.value)
+    return _query("mpcasm_qp_sens_wide_info", (no, nc, batch), ctypes.c_int64, ctypes.c_int64, ctypes.c_int32)
 
 
 def qp_vjp(P, G, h, sol_or_xyz, gx, gy, status=None, delta=OSQP_DELTA, refine_iters=OSQP_POLISH_REFINE, want_P=False,
@@ -464,10 +460,7 @@ def qp_jvp(P, G, h, sol_or_xyz, dq, dh, dP=None, dG=None, status=None, delta=OSQ
     ``ry = dh - dG x`` is formed with torch ops (the active mask is ``(h - z) < y``) on the stream of the solve --
     ``stream`` where one is passed, else torch's current one -- and the solve is one :func:`qp_sensitivity` call (``wide``: :func:`qp_sensitivity_wide`)."""
     torch = require_device()
-    if isinstance(sol_or_xyz, (QpSolution, PolishedQpSolution)):
-        x, y, z = sol_or_xyz.x, sol_or_xyz.y, sol_or_xyz.z
-    else:
-        x, y, z = sol_or_xyz
+    x, y, z, _ = _iterates(sol_or_xyz)
     # (the torch ops run on the stream the solve is launched on: `stream` where one is passed)
     with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
         rx, ry = -dq, dh.clone()
@@ -487,10 +480,12 @@ def qp_jvp(P, G, h, sol_or_xyz, dq, dh, dP=None, dG=None, status=None, delta=OSQ
 
 def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, max_iter, check_every,
               adaptive_rho_interval, sigma, alpha, kinv, kinv_valid, stream, out, workspace=False, warm_out=False,
-              soft=None):
+              soft=None, polish=None):
     """:func:`solve_qp` and :func:`solve_qp_wide` through the C entry ``entry``; ``workspace``: allocate
     ``kinv`` when it is None (the wide path's K^-1 off chip); ``warm_out``: ``out``'s iterates hold the start;
-    ``soft``: the penalties, through ``entry`` + ``_soft``."""
+    ``soft``: the penalties, through ``entry`` + ``_soft``; ``polish``: the polish to run after the solve."""
+    if polish is not None and soft is not None:
+        raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
     if warm_out and out is None:
         raise ValueError("warm=True is for out=: pass x, y, z for a warm start into new tensors")
     torch = require_device()
@@ -501,15 +496,13 @@ def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, e
         batch = P.shape[0]
         for t, dtype, shape in ((status, torch.int32, (batch,)), (iters, torch.int32, (batch,)),
                                 (res, torch.float64, (batch, 2))):
-            if not (isinstance(t, torch.Tensor) and t.device == P.device and t.dtype == dtype
-                    and t.is_contiguous() and tuple(t.shape) == shape):
-                raise ValueError("out: status, iters (B,) int32 and res (B, 2) float64, contiguous, on P's device")
+            _tensor(torch, t, dtype, shape, P.device,
+                    "out: status, iters (B,) int32 and res (B, 2) float64, contiguous, on P's device")
     batch, no, nc, warm, x, y, z = _qp_operands(torch, P, q, G, h, x, y, z, kinv, kinv_valid)
     warm = warm and (out is None or bool(warm_out))
     if isinstance(rho, torch.Tensor):
-        if not (rho.device == P.device and rho.dtype == torch.float64 and rho.is_contiguous()
-                and tuple(rho.shape) == (batch,)):
-            raise ValueError("rho: a float or a contiguous float64 (B,) tensor on P's device")
+        _tensor(torch, rho, torch.float64, (batch,), P.device,
+                "rho: a float or a contiguous float64 (B,) tensor on P's device")
     else:
         rho = torch.full((batch,), float(rho), dtype=torch.float64, device=P.device)
     if out is None:
@@ -535,7 +528,10 @@ def _solve_qp(entry, P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf, e
                                          kinv.data_ptr() if kinv is not None else None, 1 if kinv_valid else 0,
                                          _stream_handle(torch, stream), *extra)
     capi.check(rc, entry)
-    return QpSolution(x, y, z, status, iters, res, rho)
+    sol = QpSolution(x, y, z, status, iters, res, rho)
+    if polish is None:
+        return sol
+    return PolishedQpSolution(*sol, polish(P, q, G, h, sol, status=sol.status, stream=stream)[3])
 
 
 def _soft_operands(torch, soft, batch, nc, device):
@@ -571,27 +567,19 @@ def soft_pair(soft, nc, device):
 
 def qp_solve_soft_lds_bytes(no, nc):
     """:func:`qp_solve_lds_bytes` for ``solve_qp(soft=...)`` (``mpcasm_qp_solve_soft_lds_bytes``)."""
-    out = ctypes.c_int64()
-    rc = capi.load().mpcasm_qp_solve_soft_lds_bytes(int(no), int(nc), ctypes.byref(out))
-    capi.check(rc, "mpcasm_qp_solve_soft_lds_bytes")
-    return int(out.value)
+    return _query("mpcasm_qp_solve_soft_lds_bytes", (no, nc), ctypes.c_int64)[0]
 
 
 def qp_solve_wide_soft_info(no, nc):
     """:func:`qp_solve_wide_info` for ``solve_qp_wide(soft=...)`` (``mpcasm_qp_solve_wide_soft_info``)."""
-    lds, on = ctypes.c_int64(), ctypes.c_int32()
-    rc = capi.load().mpcasm_qp_solve_wide_soft_info(int(no), int(nc), ctypes.byref(lds), ctypes.byref(on))
-    capi.check(rc, "mpcasm_qp_solve_wide_soft_info")
-    return int(lds.value), bool(on.value)
+    lds, on = _query("mpcasm_qp_solve_wide_soft_info", (no, nc), ctypes.c_int64, ctypes.c_int32)
+    return lds, bool(on)
 
 
 def qp_solve_lds_bytes(no, nc):
     """LDS bytes one instance of :func:`solve_qp` (and of :func:`admm`) takes; ``MpcasmError`` with
     ``ERR_LIMIT`` when that is more than a workgroup may have (``mpcasm_qp_solve_lds_bytes``)."""
-    out = ctypes.c_int64()
-    rc = capi.load().mpcasm_qp_solve_lds_bytes(int(no), int(nc), ctypes.byref(out))
-    capi.check(rc, "mpcasm_qp_solve_lds_bytes")
-    return int(out.value)
+    return _query("mpcasm_qp_solve_lds_bytes", (no, nc), ctypes.c_int64)[0]
 
 
 def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3, eps_rel=1e-3, eps_prim_inf=1e-4,
@@ -606,24 +594,16 @@ def solve_qp_wide(P, q, G, h, x=None, y=None, z=None, rho=OSQP_RHO, eps_abs=1e-3
     ``polish``: :func:`polish_qp_wide` with OSQP's defaults after the solve, on the solved instances, as
     :func:`solve_qp` does with :func:`polish_qp`: a :class:`PolishedQpSolution`.
     ``soft``: as for :func:`solve_qp`, through ``mpcasm_qp_solve_wide_soft``."""
-    if polish and soft is not None:
-        raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
-    sol = _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
-                    eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
-                    stream, out, workspace=True, warm_out=warm, soft=soft)
-    if not polish:
-        return sol
-    verdict = polish_qp_wide(P, q, G, h, sol, status=sol.status, stream=stream)[3]
-    return PolishedQpSolution(*sol, verdict)
+    return _solve_qp("mpcasm_qp_solve_wide", P, q, G, h, x, y, z, rho, eps_abs, eps_rel, eps_prim_inf,
+                     eps_dual_inf, max_iter, check_every, adaptive_rho_interval, sigma, alpha, kinv, kinv_valid,
+                     stream, out, workspace=True, warm_out=warm, soft=soft, polish=polish_qp_wide if polish else None)
 
 
 def qp_solve_wide_info(no, nc):
     """``(lds_bytes, kinv_on_chip)`` of one instance of :func:`solve_qp_wide`; ``MpcasmError`` with ``ERR_LIMIT``
     past its size limit (``mpcasm_qp_solve_wide_info``)."""
-    lds, on = ctypes.c_int64(), ctypes.c_int32()
-    rc = capi.load().mpcasm_qp_solve_wide_info(int(no), int(nc), ctypes.byref(lds), ctypes.byref(on))
-    capi.check(rc, "mpcasm_qp_solve_wide_info")
-    return int(lds.value), bool(on.value)
+    lds, on = _query("mpcasm_qp_solve_wide_info", (no, nc), ctypes.c_int64, ctypes.c_int32)
+    return lds, bool(on)
 
 
 # --------------------------------------------------------------------------
@@ -666,11 +646,8 @@ class WarmStore:
 
 
 def _warm_tensor(torch, t, dtype, shape, device, what):
-    if not (isinstance(t, torch.Tensor) and t.device == device and t.dtype == dtype and t.is_contiguous()
-            and tuple(t.shape) == tuple(shape)):
-        raise ValueError("%s: a contiguous %s tensor of shape %s on the store's device"
-                         % (what, str(dtype).replace("torch.", ""), tuple(shape)))
-    return t
+    return _tensor(torch, t, dtype, shape, device, "%s: a contiguous %s tensor of shape %s on the store's device"
+                   % (what, str(dtype).replace("torch.", ""), tuple(shape)))
 
 
 def _warm_index(torch, store, index, count):
@@ -1053,8 +1030,7 @@ def _ltv_sequences(torch, A_seq, B_seq):
     """``n, m, T, batch (None: both shared), device`` of a pair of sequences ``(T, n, n)`` / ``(B, T, n, n)`` and
     ``(T, n, m)`` / ``(B, T, n, m)``, checked as :meth:`Assembler.bind_ltv_window` checks them."""
     for what, seq in (("A_seq", A_seq), ("B_seq", B_seq)):
-        if not (torch.is_tensor(seq) and seq.dtype == torch.float64 and seq.is_cuda and seq.is_contiguous()
-                and seq.dim() in (3, 4)):
+        if _tensor(torch, seq, torch.float64, None, None, None) is None or seq.dim() not in (3, 4):
             raise ValueError("%s: a contiguous float64 device tensor of 3 or 4 dimensions" % what)
     n, m, T = A_seq.shape[-1], B_seq.shape[-1], A_seq.shape[-3]
     if A_seq.shape[-2] != n or tuple(B_seq.shape[-3:-1]) != (T, n) or B_seq.device != A_seq.device:
@@ -1076,7 +1052,7 @@ def _seq_stride(seq):
 def _ltv_gain(torch, K, n, m, T, batch, device):
     """``batch (None: everything shared), k_stride, k_step_stride`` of a gain ``(m, n)``, ``(B, m, n)`` or ``(B, T,
     m, n)`` beside sequences of ``batch`` instances (:func:`_ltv_sequences`)."""
-    if not (torch.is_tensor(K) and K.dtype == torch.float64 and K.device == device and K.is_contiguous()
+    if not (_tensor(torch, K, torch.float64, None, device, None) is not None
             and K.dim() in (2, 3, 4) and tuple(K.shape[-2:]) == (m, n) and (K.dim() < 4 or K.shape[1] == T)
             and (K.dim() == 2 or batch in (None, K.shape[0]))):
         raise ValueError("K: a contiguous float64 tensor of shape (%d, %d), (B, %d, %d) or (B, %d, %d, %d) on %s, "
@@ -1196,12 +1172,8 @@ def plan_for_device(form, workspace="auto", batch=None, **kw):
 
 def _checked_out(torch, out, shape, device, what):
     """A caller's result buffer: float64, contiguous, on the assembler's device, at least ``shape``."""
-    if (not torch.is_tensor(out) or out.dtype != torch.float64 or not out.is_contiguous()
-            or out.device != device or out.dim() != len(shape) or out.shape[1:] != tuple(shape[1:])
-            or out.shape[0] < shape[0]):
-        raise ValueError("%s: out must be a contiguous float64 tensor on %s of shape (>= %d, %s)"
-                         % (what, device, shape[0], ", ".join(str(x) for x in shape[1:])))
-    return out
+    return _tensor(torch, out, torch.float64, shape, device, "%s: out must be a contiguous float64 tensor on %s of "
+                   "shape (>= %d, %s)" % (what, device, shape[0], ", ".join(str(x) for x in shape[1:])), at_least=True)
 
 
 class Assembler:
@@ -1441,8 +1413,8 @@ class Assembler:
         if not 0 <= t <= T - N:
             raise ValueError("the window [%d, %d) does not lie in the %d steps of the sequence" % (t, t + N, T))
         for slot, (seq, tail) in enumerate(((A_seq, (T, n, n)), (B_seq, (T, n, m)))):
-            if not (torch.is_tensor(seq) and seq.dtype == torch.float64 and seq.device == self.device
-                    and seq.is_contiguous() and tuple(seq.shape) in (tail, (self.batch,) + tail)):
+            if _tensor(torch, seq, torch.float64, None, self.device, None) is None \
+                    or tuple(seq.shape) not in (tail, (self.batch,) + tail):
                 raise ValueError("%s_seq of %r: a contiguous float64 tensor of shape %s or %s on %s"
                                  % ("AB"[slot], name, tail, (self.batch,) + tail, self.device))
             i = g["ids"][slot]
@@ -1528,8 +1500,7 @@ class Assembler:
         if not 0 <= n_run <= B:
             raise ValueError("count must lie in [0, %d]" % B)
         if index is not None:
-            if (not torch.is_tensor(index) or index.dtype != torch.int32 or index.device != self.device
-                    or not index.is_contiguous() or index.numel() < n_run or not ng):
+            if _tensor(torch, index, torch.int32, None, self.device, None) is None or index.numel() < n_run or not ng:
                 raise ValueError("index: a contiguous int32 tensor of %d entries on %s" % (n_run, self.device))
             g = _as_device(torch, given, self.device).reshape(-1, ng)
         elif ng:
@@ -1540,10 +1511,7 @@ class Assembler:
                 raise ValueError("given must have %d rows, got %d" % (n_run, g.shape[0]))
         else:
             g = None
-        if params is not None and (tuple(params.shape) != tuple(self.params.shape) or params.dtype != torch.float64
-                                   or params.device != self.device or not params.is_contiguous()):
-            raise ValueError("params: a contiguous float64 tensor of shape %s on %s"
-                             % (tuple(self.params.shape), self.device))
+        self._params_arg(params)
         if out is None:
             if self._out is None:
                 f = dict(dtype=torch.float64, device=self.device)
@@ -1677,12 +1645,9 @@ class Assembler:
         """:attr:`params`, or the caller's tensor in their place, checked as :meth:`assemble` checks it."""
         if params is None:
             return self.params
-        torch = self._torch
-        if (not torch.is_tensor(params) or tuple(params.shape) != tuple(self.params.shape)
-                or params.dtype != torch.float64 or params.device != self.device or not params.is_contiguous()):
-            raise ValueError("params: a contiguous float64 tensor of shape %s on %s"
-                             % (tuple(self.params.shape), self.device))
-        return params
+        return _tensor(self._torch, params, self._torch.float64, self.params.shape, self.device,
+                       "params: a contiguous float64 tensor of shape %s on %s"
+                       % (tuple(self.params.shape), self.device))
 
     def given_jvp(self, d, out=None, count=None, stream=None, params=None):
         """How ``q`` and ``h`` of :meth:`assemble` move along a change ``d (B, ng)`` of ``given``:
@@ -1755,8 +1720,7 @@ class Assembler:
                               (w, "w", self.nc)):
             if need and t is None:
                 raise ValueError("params_vjp: %s is missing" % name)
-        if verdict is not None and (not torch.is_tensor(verdict) or verdict.dtype != torch.int32
-                                    or verdict.device != self.device or not verdict.is_contiguous()
+        if verdict is not None and (_tensor(torch, verdict, torch.int32, None, self.device, None) is None
                                     or verdict.numel() < n):
             raise ValueError("params_vjp: verdict is a contiguous int32 tensor of %d entries on %s" % (n, self.device))
         width = int(self.params.shape[1])
@@ -1832,13 +1796,9 @@ class Assembler:
             raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
         if not isinstance(pmap, ParamMap) or pmap.plan is not self.plan:
             raise ValueError("pmap: a map this assembler's param_map built")
-        prm = self.params if params is None else params
-        if params is not None and (tuple(params.shape) != tuple(self.params.shape) or params.dtype != torch.float64
-                                   or params.device != self.device or not params.is_contiguous()):
-            raise ValueError("params: a contiguous float64 tensor of shape %s on %s"
-                             % (tuple(self.params.shape), self.device))
-        if not (torch.is_tensor(commands) and commands.dtype == torch.float64 and commands.device == self.device
-                and commands.is_contiguous() and commands.dim() in (1, 2) and commands.shape[-1] == pmap.ncmd):
+        prm = self._params_arg(params)
+        if _tensor(torch, commands, torch.float64, None, self.device, None) is None \
+                or commands.dim() not in (1, 2) or commands.shape[-1] != pmap.ncmd:
             raise ValueError("commands: a contiguous float64 (rows, %d) or (%d,) tensor on %s"
                              % (pmap.ncmd, pmap.ncmd, self.device))
         shared = commands.dim() == 1
@@ -1851,16 +1811,15 @@ class Assembler:
             if index.size and (index[:n].min() < 0 or index[:n].max() >= commands.shape[0]):
                 raise ValueError("index: entries in [0, %d)" % commands.shape[0])
             index = torch.as_tensor(index[:n].astype(np.int32), device=self.device)
-        if index is not None and not (index.dtype == torch.int32 and index.device == self.device
-                                      and index.is_contiguous() and index.dim() == 1 and index.numel() >= n):
-            raise ValueError("index: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
+        if index is not None:
+            _tensor(torch, index, torch.int32, (n,), self.device,
+                    "index: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device), at_least=True)
         if index is None and not shared and commands.shape[0] < n:
             raise ValueError("commands must have %d rows, got %d" % (n, commands.shape[0]))
         check_param_map_sign(pmap.host_recs, sign)
-        if sign is not None and not (torch.is_tensor(sign) and sign.dtype == torch.float64
-                                     and sign.device == self.device and sign.is_contiguous() and sign.dim() == 1
-                                     and sign.numel() >= n):
-            raise ValueError("sign: a contiguous float64 tensor of >= %d entries on %s" % (n, self.device))
+        if sign is not None:
+            _tensor(torch, sign, torch.float64, (n,), self.device,
+                    "sign: a contiguous float64 tensor of >= %d entries on %s" % (n, self.device), at_least=True)
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(self.device):
             rc = capi.load().mpcasm_params_map(
@@ -1902,22 +1861,19 @@ class Assembler:
             raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
         if not isinstance(gmap, GivenMap) or gmap.plan is not self.plan:
             raise ValueError("gmap: a map this assembler's given_map built")
-        if not (torch.is_tensor(given) and given.dtype == torch.float64 and given.device == self.device
-                and given.is_contiguous() and given.dim() == 2 and given.shape[1] == self.ng):
-            raise ValueError("given: a contiguous float64 (rows, %d) tensor on %s (updated in place)"
-                             % (self.ng, self.device))
-        if not (torch.is_tensor(optim) and optim.dtype == torch.float64 and optim.device == self.device
-                and optim.is_contiguous() and optim.dim() == 2 and optim.shape[1] == self.no and optim.shape[0] >= n):
-            raise ValueError("optim: a contiguous float64 (>= %d, %d) tensor on %s" % (n, self.no, self.device))
+        _tensor(torch, given, torch.float64, (None, self.ng), self.device,
+                "given: a contiguous float64 (rows, %d) tensor on %s (updated in place)" % (self.ng, self.device))
+        _tensor(torch, optim, torch.float64, (n, self.no), self.device,
+                "optim: a contiguous float64 (>= %d, %d) tensor on %s" % (n, self.no, self.device), at_least=True)
         if index is not None and not torch.is_tensor(index):
             index = np.asarray(index)
             if index.ndim != 1 or index.size < n:
                 raise ValueError("index: %d entries" % n)
             index = torch.as_tensor(checked_index(index[:n], given.shape[0]), device=self.device)
         for t, name in ((index, "index"), (status, "status")):
-            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.int32 and t.device == self.device
-                                      and t.is_contiguous() and t.dim() == 1 and t.numel() >= n):
-                raise ValueError("%s: a contiguous int32 tensor of >= %d entries on %s" % (name, n, self.device))
+            if t is not None:
+                _tensor(torch, t, torch.int32, (n,), self.device,
+                        "%s: a contiguous int32 tensor of >= %d entries on %s" % (name, n, self.device), at_least=True)
         if index is None and given.shape[0] < n:
             raise ValueError("given must have %d rows, got %d" % (n, given.shape[0]))
         ptr = lambda t: t.data_ptr() if t is not None else None
@@ -1946,13 +1902,11 @@ class Assembler:
         torch = self._torch
         if not 0 <= n <= self.batch:         # (per-instance sources are sized for the batch)
             raise ValueError("count must lie in 0 .. %d, got %d" % (self.batch, n))
-        if not (torch.is_tensor(given) and given.dtype == torch.float64 and given.device == self.device
-                and given.is_contiguous() and given.dim() == 2 and given.shape[1] == self.ng):
-            raise ValueError("given: a contiguous float64 (rows, %d) tensor on %s%s"
-                             % (self.ng, self.device, " (updated in place)" if writes else ""))
-        if not (torch.is_tensor(optim) and optim.dtype == torch.float64 and optim.device == self.device
-                and optim.is_contiguous() and optim.dim() == 2 and optim.shape[1] == self.no and optim.shape[0] >= n):
-            raise ValueError("optim: a contiguous float64 (>= %d, %d) tensor on %s" % (n, self.no, self.device))
+        _tensor(torch, given, torch.float64, (None, self.ng), self.device,
+                "given: a contiguous float64 (rows, %d) tensor on %s%s"
+                % (self.ng, self.device, " (updated in place)" if writes else ""))
+        _tensor(torch, optim, torch.float64, (n, self.no), self.device,
+                "optim: a contiguous float64 (>= %d, %d) tensor on %s" % (n, self.no, self.device), at_least=True)
         if index is not None and not torch.is_tensor(index):
             index = np.asarray(index)
             if index.ndim != 1 or index.size < n:
@@ -1963,9 +1917,9 @@ class Assembler:
             elif index.size and (index.min() < 0 or index.max() >= given.shape[0]):
                 raise ValueError("an index of rows must hold entries in [0, %d)" % given.shape[0])
             index = torch.as_tensor(index.astype(np.int32), device=self.device)
-        if index is not None and not (index.dtype == torch.int32 and index.device == self.device
-                                      and index.is_contiguous() and index.dim() == 1 and index.numel() >= n):
-            raise ValueError("index: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
+        if index is not None:
+            _tensor(torch, index, torch.int32, (n,), self.device,
+                    "index: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device), at_least=True)
         if index is None and given.shape[0] < n:
             raise ValueError("given must have %d rows, got %d" % (n, given.shape[0]))
         return index
@@ -2005,10 +1959,9 @@ class Assembler:
         table = self._rollout_table()
         n = self.batch if count is None else int(count)
         index = self._rollout_args(given, optim, index, n, True)
-        if status is not None and not (torch.is_tensor(status) and status.dtype == torch.int32
-                                       and status.device == self.device and status.is_contiguous()
-                                       and status.dim() == 1 and status.numel() >= n):
-            raise ValueError("status: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device))
+        if status is not None:
+            _tensor(torch, status, torch.int32, (n,), self.device,
+                    "status: a contiguous int32 tensor of >= %d entries on %s" % (n, self.device), at_least=True)
         ptr = lambda t: t.data_ptr() if t is not None else None
         self._call("mpcasm_ltv_advance", given.data_ptr(), given.shape[0], optim.data_ptr(), ptr(index), ptr(status),
                    int(apply_mask) & 0xFFFFFFFF, table.data_ptr(), table.numel(), n, stream=stream)
@@ -2032,8 +1985,8 @@ class Assembler:
         if not 0 <= t <= T - N:
             raise ValueError("the window [%d, %d) does not lie in the %d steps of the gains" % (t, t + N, T))
         tail = (T, m, n)
-        if not (K_seq.dtype == torch.float64 and K_seq.device == self.device and K_seq.is_contiguous()
-                and tuple(K_seq.shape) in (tail, (self.batch,) + tail)):
+        if _tensor(torch, K_seq, torch.float64, None, self.device, None) is None \
+                or tuple(K_seq.shape) not in (tail, (self.batch,) + tail):
             raise ValueError("K_seq: a contiguous float64 tensor of shape %s or %s on %s"
                              % (tail, (self.batch,) + tail, self.device))
         cnt = self.batch if count is None else int(count)

@@ -13,13 +13,13 @@ formulation compiled with ``ltv=``:
     given <- x_1 = A_t x_0 + B_t u_0                   Assembler.advance           (csrc/rollout.hip)
 
 -- the reference's tick (biped_mpc_loop.py:50-95: assemble, ``osqp_solve_qp``, ``preview_all`` +
-``update_given_collector``) with per-step dynamics, nothing read back to the host.  The loop runs launch by
+``update_given_collector``) with per-step dynamics, nothing read back to the host.  The four rows from the warm start
+to the warm store are the loop's solve stage (:class:`mpcasm.solve_stage.SolveStage`).  The loop runs launch by
 launch: the window's address changes every tick, which a captured graph would not follow."""
 import numpy as np
 
-from .engine import (APPLY_ALL, APPLY_SOLVED, OSQP_RHO, WARM_SOLVED, Assembler, WarmStore, _ltv_sequences, ltv_augment,
-                     ltv_close, ltv_lqr, polish_qp_wide, qp_polish_wide_info, qp_solve_wide_info,
-                     qp_solve_wide_soft_info, soft_pair, solve_qp_wide, warm_start_qp, warm_store_qp)
+from .engine import Assembler, _ltv_sequences, ltv_augment, ltv_close, ltv_lqr
+from .solve_stage import SolveStage, stage_options
 
 
 class LtvLoop:
@@ -77,16 +77,10 @@ class LtvLoop:
         feedback = solver_kwargs.pop("feedback", None)
         self.true_input = bool(solver_kwargs.pop("true_input", False))
         soft = solver_kwargs.pop("soft", None)
-        if soft is not None and polish:
-            raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
-        if soft is not None and not callable(soft) and not (isinstance(soft, (tuple, list)) and len(soft) == 2):
-            raise ValueError("soft: a pair (lin, quad) or a callable that takes an Assembler and returns one")
+        self._apply_mask = stage_options(on_unsolved, polish, soft)
         if self.true_input:               # (decided on the host, from the formulation: before anything is compiled)
             self._check_true_input(form, name, A_seq, B_seq, feedback)
-        if on_unsolved not in ("hold", "apply"):
-            raise ValueError("on_unsolved: 'hold' or 'apply', got %r" % (on_unsolved,))
         self.on_unsolved = on_unsolved
-        self._apply_mask = APPLY_SOLVED if on_unsolved == "hold" else APPLY_ALL
         self.name, self.batch = name, int(batch)
         self.asm = asm = Assembler(form, batch=self.batch, ltv=[name])
         torch = self._torch = asm._torch
@@ -102,35 +96,18 @@ class LtvLoop:
                 self._close(feedback)
         self.ticks_possible = A_seq.shape[-3] - self.horizon + 1
         self.t = 0
-        f, i32 = dict(dtype=torch.float64, device=asm.device), dict(dtype=torch.int32, device=asm.device)
-        B = self.batch
-        self.given = torch.zeros((B, asm.ng), **f)
-        # the solver's buffers, at fixed addresses for every tick
-        self._qp = dict(x=torch.zeros((B, asm.no), **f), y=torch.zeros((B, asm.nc), **f),
-                        z=torch.zeros((B, asm.nc), **f), status=torch.zeros(B, **i32), iters=torch.zeros(B, **i32),
-                        res=torch.zeros((B, 2), **f), rho=torch.full((B,), OSQP_RHO, **f))
-        self._solver_kwargs = dict(solver_kwargs)
-        # the penalties: one pair of rows for every instance and tick, at a fixed address
-        if soft is not None:
-            self._solver_kwargs["soft"] = soft_pair(soft(asm) if callable(soft) else soft, asm.nc, asm.device)
-        info = qp_solve_wide_info if soft is None else qp_solve_wide_soft_info
-        # where K^-1 does not fit on chip it is the solver's workspace: allocated once, unless the caller brings one
-        if "kinv" not in solver_kwargs and not info(asm.no, asm.nc)[1]:
-            self._solver_kwargs["kinv"] = torch.empty((B, asm.no, asm.no), **f)
-        # the polish's workspace and verdicts, allocated once
-        self.polish = bool(polish)
-        if self.polish:
-            self._polish_work = torch.empty((max(qp_polish_wide_info(asm.no, asm.nc, B)[1], 16) // 8,), **f)
-            self._polish_verdict = torch.zeros(B, **i32)
-        # the warm store (a record per instance, no index) and the one shift map, built once
-        self.warm = bool(warm)
-        if self.warm:
+        self.given = torch.zeros((self.batch, asm.ng), dtype=torch.float64, device=asm.device)
+        # the solve stage (mpcasm.solve_stage): the wide solver's buffers, workspaces and warm store (a record per
+        # instance, no index), at fixed addresses for every tick
+        self.polish, self.warm = bool(polish), bool(warm)
+        self.stage = SolveStage(asm, self.batch, wide=True, on_unsolved=on_unsolved, polish=polish, warm=warm,
+                                soft=soft, **solver_kwargs)
+        self._groups = ()
+        if self.warm:                       # (the one shift map, built once: every instance is one group)
             from .warm import shift_map
             rows = [n for _, n in asm.plan.limit_rows]
             col, row = shift_map(form, form, False, horizon=self.horizon, prev_rows=rows, new_rows=rows)
-            self._col_src, self._row_src = (torch.as_tensor(v, device=asm.device) for v in (col, row))
-            self._store = WarmStore(B, asm.no, asm.nc, asm.device)
-            self._warm_flags = torch.zeros(B, **i32)
+            self._groups = [(0, self.batch) + tuple(torch.as_tensor(v, device=asm.device) for v in (col, row))]
 
     @staticmethod
     def _check_true_input(form, name, A_seq, B_seq, feedback):
@@ -218,41 +195,24 @@ class LtvLoop:
         if self.t >= self.ticks_possible:
             raise ValueError("the sequences hold %d steps: no window of %d steps starts at tick %d"
                              % (self.A_seq.shape[-3], self.horizon, self.t))
-        asm, qp = self.asm, self._qp
+        asm = self.asm
         asm.bind_ltv_window(self.name, self._win[0], self._win[1], self.t)
         P, q, G, h = asm.assemble(self.given)
         if G is None:                      # (a plan without limits: the solver takes G and h of no rows)
             G, h = P.new_empty((self.batch, 0, asm.no)), P.new_empty((self.batch, 0))
-        if self.warm:                      # (the tag is the tick + 1: a record is one tick old or not warm)
-            warm_start_qp(self._store, G, h, self._col_src, self._row_src, self.t, warm_mask=WARM_SOLVED,
-                          rho_cold=OSQP_RHO, out=(qp["x"], qp["y"], qp["z"], qp["rho"], self._warm_flags))
-        else:
-            qp["rho"].fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
-        sol = solve_qp_wide(P, q, G, h, rho=qp["rho"], out=tuple(qp[k] for k in ("x", "y", "z", "status", "iters",
-                                                                                  "res")), warm=self.warm,
-                            **self._solver_kwargs)
-        if self.polish:
-            polish_qp_wide(P, q, G, h, sol, status=sol.status, out=(self._polish_verdict, sol.res),
-                           work=self._polish_work)
-        if self.warm:
-            warm_store_qp(self._store, sol, self.t + 1)
+        # (the tag is the tick + 1: a record is one tick old or not warm)
+        out = self.stage.run(P, q, G, h, groups=self._groups, expect_tag=self.t, tag=self.t + 1)
         if self.K_seq is not None:         # (from the tick's initial states: before they advance)
-            asm.true_inputs(self._gain_seq, self.t, self.given, sol.x, out=self._u)
-        asm.advance(self.given, sol.x, status=sol.status, apply_mask=self._apply_mask)
+            asm.true_inputs(self._gain_seq, self.t, self.given, out["x"], out=self._u)
+            out["u"] = self._u
+        asm.advance(self.given, out["x"], status=out["status"], apply_mask=self._apply_mask)
         if self.true_input:
             # the advance's own K x_0 + v_0 sums the same products in another order (its last bit may differ):
             # an applied instance's slots get the very numbers the results report
-            applied = self._applies[sol.status.abs().clamp_(max=32).long()]
+            applied = self._applies[out["status"].abs().clamp_(max=32).long()]
             self.given[:, self._slots] = self._torch.where(applied[:, None], self._u[:, :, 0].reshape(self.batch, -1),
                                                            self.given[:, self._slots])
         self.t += 1
-        out = {"x": sol.x, "status": sol.status, "iters": sol.iters}
-        if self.K_seq is not None:
-            out["u"] = self._u
-        if self.polish:
-            out["polish"] = self._polish_verdict
-        if self.warm:
-            out["warm"] = self._warm_flags
         return out
 
     def run(self, ticks, record=False):

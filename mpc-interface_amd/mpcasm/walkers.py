@@ -161,24 +161,18 @@ class WalkerFleet:
 
     def __init__(self, batch, phases=None, conf=None, api=None, device=None, graphs=False, side_by_side=False,
                  on_unsolved="hold", polish=False, warm=False, commands=False, command_rules=None, soft=None):
-        from .engine import APPLY_ALL, APPLY_SOLVED, Assembler, require_device
+        from .engine import Assembler, require_device
+        from .solve_stage import stage_options
 
-        if on_unsolved not in ("hold", "apply"):
-            raise ValueError("on_unsolved: 'hold' or 'apply', got %r" % (on_unsolved,))
+        stage_options(on_unsolved, polish, soft)
         self.on_unsolved = on_unsolved
-        # polish=True: every solved QP is polished (engine.polish_qp, OSQP's defaults) before its solution
-        # becomes the walker's next `given`
-        self._polish = bool(polish)
+        # what every bucket's solve stage (mpcasm.solve_stage) is built with, the first time the bucket steps.
+        # polish=True: every solved QP is polished before its solution becomes the walker's next `given`;
         # soft=: the penalties of the solve, a pair or what makes one from a bucket's assembler
-        if soft is not None and self._polish:
-            raise ValueError("polish= with soft=: the polish's active-set model is the hard problem's")
-        if soft is not None and not callable(soft) and not (isinstance(soft, (tuple, list)) and len(soft) == 2):
-            raise ValueError("soft: a pair (lin, quad) or a callable that takes an Assembler and returns one")
-        self._soft = soft
+        self._stage_options = dict(on_unsolved=on_unsolved, polish=bool(polish), warm=bool(warm), soft=soft)
         # warm=True: one warm store for the fleet (a record per walker, sized by the widest bucket), built with
-        # the buckets' solver buffers; per place of the step cycle the shift maps are kept with its other inputs
+        # the first stage; per place of the step cycle the shift maps are kept with its other inputs
         self._warm, self._warm_store = bool(warm), None
-        self._apply_mask = APPLY_SOLVED if on_unsolved == "hold" else APPLY_ALL
         self._step_graphs = {}
         self._torch = require_device()
         self.conf = conf or problems.BipedConfig()
@@ -449,64 +443,30 @@ class WalkerFleet:
         return given
 
     def _closed_bucket(self, item, entry, stream):
-        """After a bucket's assembly, on its stream: a cold solve with OSQP's defaults into the bucket's own
-        solver buffers, then its walkers' next ``given`` from the solution, by the fleet's rule.  A warm fleet:
-        the start from the store (tag: the place before), the solve from it, the store (tag: this place) after
-        the polish when there is one."""
-        from .engine import (OSQP_RHO, WARM_SOLVED, WarmStore, polish_qp, soft_pair, solve_qp, warm_start_qp,
-                             warm_store_qp)
+        """After a bucket's assembly, on its stream: the bucket's solve stage (:class:`mpcasm.solve_stage.SolveStage`,
+        the narrow solver, made the first time the bucket steps; a warm fleet: one launch of the start per bucket
+        of the tick before, the tag to expect the place before, the tag to store this place), then its walkers'
+        next ``given`` from the solution, by the fleet's rule."""
+        from .engine import WarmStore
+        from .solve_stage import SolveStage
 
         bucket = self.buckets[item["p"]]
         asm, n = bucket["asm"], item["idx"].size
-        qp = bucket.get("qp")
-        if qp is None:   # (once per bucket, at fixed addresses for every place of the cycle and every graph)
-            torch, f = self._torch, dict(dtype=self._torch.float64, device=asm.device)
-            i32 = dict(dtype=torch.int32, device=asm.device)
-            B = self.batch
-            qp = bucket["qp"] = dict(x=torch.zeros((B, asm.no), **f), y=torch.zeros((B, asm.nc), **f),
-                                     z=torch.zeros((B, asm.nc), **f), status=torch.zeros(B, **i32),
-                                     iters=torch.zeros(B, **i32), res=torch.zeros((B, 2), **f),
-                                     rho=torch.full((B,), OSQP_RHO, **f))
+        stage = bucket.get("stage")
+        if stage is None:   # (once per bucket, at fixed addresses for every place of the cycle and every graph)
+            if self._warm and self._warm_store is None:
+                self._warm_store = WarmStore(self.batch, max(b["asm"].no for b in self.buckets.values()),
+                                             max(b["asm"].nc for b in self.buckets.values()), asm.device)
+            stage = bucket["stage"] = SolveStage(asm, self.batch, store=self._warm_store, **self._stage_options)
             bucket["gmap"] = asm.given_map(biped_given_rules(bucket["form"]))
-            if self._polish:
-                qp["polish"] = torch.zeros(B, **i32)
-            if self._soft is not None:   # (one pair of rows for the bucket, at a fixed address)
-                bucket["soft"] = soft_pair(self._soft(asm) if callable(self._soft) else self._soft, asm.nc,
-                                           asm.device)
-            if self._warm:
-                qp["warm"] = torch.zeros(B, **i32)
-                if self._warm_store is None:
-                    self._warm_store = WarmStore(B, max(b["asm"].no for b in self.buckets.values()),
-                                                 max(b["asm"].nc for b in self.buckets.values()), asm.device)
-        cur = self._torch.cuda.current_stream(asm.device) if stream is None else stream
-        with self._torch.cuda.stream(cur):
-            rho = qp["rho"][:n]
-            if self._warm:
-                period = 2 * self.conf.step_samples
-                for a, b, col_src, row_src in item["groups"]:   # (one launch per bucket of the tick before)
-                    warm_start_qp(self._warm_store, entry["G"][a:b], entry["h"][a:b], col_src, row_src,
-                                  (item["key"] - 1) % period, index=item["index"][a:b], warm_mask=WARM_SOLVED,
-                                  rho_cold=OSQP_RHO, stream=stream,
-                                  out=tuple(qp[k][a:b] for k in ("x", "y", "z", "rho", "warm")))
-            else:
-                rho.fill_(OSQP_RHO)      # (the reference builds a fresh solver every tick)
-            sol = solve_qp(entry["P"], entry["q"], entry["G"], entry["h"], rho=rho, stream=stream, warm=self._warm,
-                           out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")),
-                           soft=bucket.get("soft"))
-            if self._polish:
-                polish_qp(entry["P"], entry["q"], entry["G"], entry["h"], sol, status=sol.status, stream=stream,
-                          out=(qp["polish"][:n], sol.res))
-            if self._warm:
-                warm_store_qp(self._warm_store, sol, item["key"], index=item["index"], stream=stream)
-            asm.next_given(self.given_buffer(), sol.x, bucket["gmap"], index=item["index"], status=sol.status,
-                           apply_mask=self._apply_mask, count=n, stream=stream)
-        out = {"p": item["p"], "index": item["index"], "index_long": item["index_long"], "x": sol.x,
-               "status": sol.status, "iters": sol.iters}
-        if self._polish:
-            out["polish"] = qp["polish"][:n]
-        if self._warm:
-            out["warm"] = qp["warm"][:n]
-        return out
+            if "soft" in stage.solver_kwargs:      # (the bucket's pair of rows, under the name it always had)
+                bucket["soft"] = stage.solver_kwargs["soft"]
+        out = stage.run(entry["P"], entry["q"], entry["G"], entry["h"], groups=item.get("groups", ()),
+                        expect_tag=(item["key"] - 1) % (2 * self.conf.step_samples), tag=item["key"],
+                        index=item["index"], count=n, stream=stream)
+        asm.next_given(self.given_buffer(), out["x"], bucket["gmap"], index=item["index"], status=out["status"],
+                       apply_mask=stage.apply_mask, count=n, stream=stream)
+        return dict(out, p=item["p"], index=item["index"], index_long=item["index_long"])
 
     def step(self):
         """One closed tick of the walking loop on :meth:`given_buffer` (biped_mpc_loop.py:50-95 for every
@@ -556,9 +516,9 @@ class WalkerFleet:
             self.step()
             items = self._cache[key]
             for item in items:
-                qp, n = self.buckets[item["p"]]["qp"], item["idx"].size
-                status[t].index_copy_(0, item["index_long"], qp["status"][:n])
-                iters[t].index_copy_(0, item["index_long"], qp["iters"][:n])
+                buf, n = self.buckets[item["p"]]["stage"].buffers, item["idx"].size
+                status[t].index_copy_(0, item["index_long"], buf["status"][:n])
+                iters[t].index_copy_(0, item["index_long"], buf["iters"][:n])
             if record:
                 trail[t + 1].copy_(given)
         out = {"status": status, "iters": iters}

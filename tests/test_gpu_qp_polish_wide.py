@@ -340,11 +340,12 @@ def test_the_ltv_loop_polishes(gpu_api, torch_gpu):
     ref = build()
     P, q, G, h = (t.clone() for t in ref.asm.assemble(ref.given))
     ref.step()
-    before = tuple(ref._qp[k].cpu().numpy().copy() for k in ("x", "y", "z", "res", "status"))
+    seen, polished = ref.stage.buffers, on.stage.buffers      # (the loops' solver buffers, by name)
+    before = tuple(seen[k].cpu().numpy().copy() for k in ("x", "y", "z", "res", "status"))
     out = on.step()
     assert set(out) == {"x", "status", "iters", "polish"}
-    assert torch.equal(out["status"], ref._qp["status"]) and torch.equal(out["iters"], ref._qp["iters"])
-    after = tuple(t.cpu().numpy().copy() for t in (on._qp["x"], on._qp["y"], on._qp["z"], on._qp["res"], out["polish"]))
+    assert torch.equal(out["status"], seen["status"]) and torch.equal(out["iters"], seen["iters"])
+    after = tuple(t.cpu().numpy().copy() for t in (polished["x"], polished["y"], polished["z"], polished["res"], out["polish"]))
     solved, judged, done, worst = judge_solved(tuple(t.cpu().numpy() for t in (P, q, G, h)), before, after, "ltv tick 0")
     assert done > 0, (solved, judged, done)
     record("ltv-loop-tick0", "primal %.3f  dual %.3f  (%d solved, %d judged, %d DONE)" % (worst[0], worst[1], solved, judged, done))

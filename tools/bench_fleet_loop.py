@@ -58,7 +58,7 @@ def summary(ms):
 
 
 def split_cycle(fleet, ticks):
-    """``ticks`` closed ticks made of the same calls as WalkerFleet.step, with events between the pieces:
+    """``ticks`` closed ticks made of the steps of WalkerFleet.step (each bucket's solve stage), with events between:
     per-tick ms of assembly, solve and next_given (summed over the buckets)."""
     parts = {"assemble": [], "solve": [], "next_given": []}
     for _ in range(ticks):
@@ -66,18 +66,17 @@ def split_cycle(fleet, ticks):
         given = fleet.given_buffer()
         for item in fleet._bucket_inputs():
             bucket = fleet.buckets[item["p"]]
-            asm, qp, n = bucket["asm"], bucket["qp"], item["idx"].size
+            asm, stage, n = bucket["asm"], bucket["stage"], item["idx"].size
             e = [ev() for _ in range(4)]
             asm.bind_source(("steps", 0), item["E"])
             e[0].record()
             P, q, G, h = asm.assemble(given, count=n, index=item["index"], params=item["params"])
             e[1].record()
-            qp["rho"][:n].fill_(engine.OSQP_RHO)
-            sol = engine.solve_qp(P[:n], q[:n], G[:n], h[:n], rho=qp["rho"][:n],
-                                  out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")))
+            stage.start(G[:n], h[:n], (), 0, count=n)
+            sol = stage.solve(P[:n], q[:n], G[:n], h[:n], count=n)
             e[2].record()
             asm.next_given(given, sol.x, bucket["gmap"], index=item["index"], status=sol.status,
-                           apply_mask=fleet._apply_mask, count=n)
+                           apply_mask=stage.apply_mask, count=n)
             e[3].record()
             marks.append(e)
         fleet.clock.tick()

@@ -67,39 +67,31 @@ def window_summary(windows):
 
 
 def split_cycle(fleet, ticks):
-    """``ticks`` closed ticks made of the same calls as WalkerFleet.step, with events between the pieces:
+    """``ticks`` closed ticks made of the steps of WalkerFleet.step (each bucket's solve stage), with events between:
     per-tick ms of every piece (summed over the buckets)."""
     names = ["assemble", "warm_start", "solve", "store", "next_given"]
     parts = {k: [] for k in names}
-    warm = fleet._warm
     period = 2 * fleet.conf.step_samples
     for _ in range(ticks):
         marks = []
         given = fleet.given_buffer()
         for item in fleet._bucket_inputs():
             bucket = fleet.buckets[item["p"]]
-            asm, qp, n = bucket["asm"], bucket["qp"], item["idx"].size
+            asm, stage, n = bucket["asm"], bucket["stage"], item["idx"].size
             e = [ev() for _ in range(6)]
             asm.bind_source(("steps", 0), item["E"])
             e[0].record()
             P, q, G, h = asm.assemble(given, count=n, index=item["index"], params=item["params"])
             e[1].record()
-            if warm:
-                for a, b, col_src, row_src in item["groups"]:
-                    engine.warm_start_qp(fleet.warm_store, G[a:b], h[a:b], col_src, row_src,
-                                         (item["key"] - 1) % period, index=item["index"][a:b],
-                                         out=tuple(qp[k][a:b] for k in ("x", "y", "z", "rho", "warm")))
-            else:
-                qp["rho"][:n].fill_(engine.OSQP_RHO)
+            stage.start(G[:n], h[:n], item.get("groups", ()), (item["key"] - 1) % period, index=item["index"], count=n)
             e[2].record()
-            sol = engine.solve_qp(P[:n], q[:n], G[:n], h[:n], rho=qp["rho"][:n], warm=warm,
-                                  out=tuple(qp[k][:n] for k in ("x", "y", "z", "status", "iters", "res")))
+            sol = stage.solve(P[:n], q[:n], G[:n], h[:n], count=n)
             e[3].record()
-            if warm:
-                engine.warm_store_qp(fleet.warm_store, sol, item["key"], index=item["index"])
+            if stage.warm:
+                stage.store(sol, item["key"], index=item["index"])
             e[4].record()
             asm.next_given(given, sol.x, bucket["gmap"], index=item["index"], status=sol.status,
-                           apply_mask=fleet._apply_mask, count=n)
+                           apply_mask=stage.apply_mask, count=n)
             e[5].record()
             marks.append(e)
         fleet.clock.tick()

@@ -86,16 +86,15 @@ def one_batch(api, form, batch, a):
 
     reps, runs = (2, a.runs) if batch <= 4096 else (1, a.runs)
     lp["step"] = spread(event_ms(step, reps, runs, warm=1))
-    lasm, qp = loop.asm, loop._qp
+    lasm, stage = loop.asm, loop.stage
     lasm.bind_ltv_window("LIP", loop.A_cl_seq, B_seq, 0)
     P, q, G, h = lasm.assemble(start)
     lp["assemble"] = spread(event_ms(lambda: lasm.assemble(start), 5, a.runs))
-    buf = tuple(qp[k] for k in ("x", "y", "z", "status", "iters", "res"))
-    kw = loop._solver_kwargs
+    qp = stage.buffers
 
     def solve():
-        qp["rho"].fill_(engine.OSQP_RHO)
-        engine.solve_qp_wide(P, q, G, h, rho=qp["rho"], out=buf, **kw)
+        stage.start(G, h, (), 0)
+        stage.solve(P, q, G, h)
 
     lp["solve_qp_wide_cold"] = spread(event_ms(solve, reps, runs, warm=1))
     u = torch.empty((batch, axes, N, m), dtype=torch.float64, device="cuda")

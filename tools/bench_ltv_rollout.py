@@ -141,16 +141,15 @@ def one_batch(api, form, batch, a, with_parent):
               "iters_mean": round(float(iters.mean()), 1), "iters_max": int(iters.max())}
         reps, runs = (2, 2) if batch <= 4096 else (1, 1)
         lp["step"] = spread(event_ms(step, reps, runs, warm=0))
-        lasm, qp = loop.asm, loop._qp
+        lasm, stage = loop.asm, loop.stage
         lasm.bind_ltv_window("LIP", A_seq, B_seq, 0)
         P, q, G, h = lasm.assemble(start)
         lp["assemble"] = spread(event_ms(lambda: lasm.assemble(start), 5, 3))
-        buf = tuple(qp[k] for k in ("x", "y", "z", "status", "iters", "res"))
-        kw = loop._solver_kwargs
+        qp = stage.buffers
 
         def solve():
-            qp["rho"].fill_(engine.OSQP_RHO)
-            engine.solve_qp_wide(P, q, G, h, rho=qp["rho"], out=buf, **kw)
+            stage.start(G, h, (), 0)
+            stage.solve(P, q, G, h)
 
         lp["solve_qp_wide_cold"] = spread(event_ms(solve, reps, runs, warm=0))
         lp["advance"] = spread(event_ms(lambda: lasm.advance(scratch, qp["x"], status=qp["status"]), a.reps, a.runs))
