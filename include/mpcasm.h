@@ -361,8 +361,9 @@ int mpcasm_sweep_route(const int32_t* h_itab, size_t n_itab, const double* h_dta
  * with nontemporal stores); out[3]: systems per wavefront (QUAD, TINY; else 0); out[4]: QUAD: log2 of the
  * lanes that share a short row (rows per store instruction = 64 >> out[4]); out[5]: workgroups; out[6]:
  * dynamic LDS bytes of a workgroup; out[7]: 1 when that is more than 64 KB.  MPCASM_ERR_LIMIT exactly where
- * the launch returns it (out is zeroed): one system's tables beyond a CU's LDS, or per-step systems of more
- * than 256 states.  MPCASM_ERR_ARG as mpcasm_fill_su (batch < 1 here: an empty batch launches nothing). */
+ * the launch returns it (out is zeroed): one system's tables beyond the 156 KB of LDS a workgroup is granted
+ * (a quad-kernel shape beyond them goes to the kernels behind it), or per-step systems of more than 256 states.
+ * MPCASM_ERR_ARG as mpcasm_fill_su (batch < 1 here: an empty batch launches nothing). */
 enum { MPCASM_FILL_QUAD = 1 /* n <= 4: recurrence in registers, several systems per wavefront */,
        MPCASM_FILL_TINY = 2 /* n (m + n) <= 32: several systems per wavefront, recurrence in LDS */,
        MPCASM_FILL_LTI = 3, MPCASM_FILL_LTV_ROW = 4 /* per-step, n <= 4: a wavefront per system */,
@@ -385,7 +386,9 @@ int mpcasm_fill_route(int batch, int N, int n, int m, int ltv, int aligned16, in
  * the horizon tables, MPCASM_TILED_TABLES_*; out[9]: TG of the shared-model form's kernel for P (4 .. 32; 0: P
  * not wanted or no weight); out[10]: 1 when only the lower block pairs of P are multiplied (Toeplitz, general
  * and shared form); out[11 .. 15]: 0.  MPCASM_ERR_LIMIT exactly where the launch returns it (out is zeroed):
- * a generated system beyond 64 states or n (m + n) > 2048 that the fused scan form does not take.
+ * a generated system beyond 64 states or n (m + n) > 2048, or one whose horizon tables the per-system pre-pass
+ * (MPCASM_TILED_TABLES_SYSTEM) would make with more than 64 KB of dynamic LDS, (n n + 2 n (m + n) + 16 n m) 8
+ * bytes -- nothing is launched -- that the fused scan form does not take.
  * MPCASM_ERR_ARG for a plan that does not run on the tiled path -- the persistent kernel takes a plan that
  * fits on chip first (input alignment, a property of the launch's pointers, is taken as given). */
 enum { MPCASM_TILED_SCAN = 1, MPCASM_TILED_TOEPLITZ = 2, MPCASM_TILED_SHARED = 3, MPCASM_TILED_GENERAL = 4 };

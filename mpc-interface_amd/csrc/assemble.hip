@@ -625,25 +625,21 @@ int launch_assemble_staged(const PlanDev& p, const AssembleCall& c) {
   double* V = static_cast<double*>(c.work);
   const int batch = c.batch;
   StagedChoice s;
-  const int rc = staged_choose(p, c.P != nullptr, c.G != nullptr, batch, &s);
-  if (rc != MPCASM_OK) return rc;
-  if (s.grid_k2)
-    hipLaunchKernelGGL(compose_rowsets_kernel, dim3(s.grid_k2), dim3(BLOCK), 0, c.stream, p, c.src, c.given, V,
-                       s.k2_nrb);
-  if (s.hessian == MPCASM_STAGED_GEMM) {
-    hipLaunchKernelGGL(hessian_gemm_kernel, dim3(s.grid_k3), dim3(BLOCK), 0, c.stream, p, c.params, V, c.P, s.nb,
-                       s.npairs, s.sym);
-    hipLaunchKernelGGL(gradient_kernel, dim3(s.grid_gradient), dim3(BLOCK), 0, c.stream, p, c.params, V, c.q,
-                       s.ncb);
-  } else if (s.hessian == MPCASM_STAGED_BLOCK) {
-    hipLaunchKernelGGL(hessian_kernel, dim3(s.grid_k3), dim3(BLOCK), 0, c.stream, p, c.params, V, c.P, c.q,
-                       s.k3_nrb, 0);
+  int rc = staged_choose(p, c.P != nullptr, c.G != nullptr, batch, &s);
+  if (rc == MPCASM_OK && s.grid_k2)
+    rc = launch_with_lds(compose_rowsets_kernel, s.grid_k2, BLOCK, 0, c.stream, c.err, p, c.src, c.given, V, s.k2_nrb);
+  if (rc == MPCASM_OK && s.hessian == MPCASM_STAGED_GEMM) {
+    rc = launch_with_lds(hessian_gemm_kernel, s.grid_k3, BLOCK, 0, c.stream, c.err, p, c.params, V, c.P, s.nb, s.npairs,
+                         s.sym);
+    if (rc == MPCASM_OK)
+      rc = launch_with_lds(gradient_kernel, s.grid_gradient, BLOCK, 0, c.stream, c.err, p, c.params, V, c.q, s.ncb);
+  } else if (rc == MPCASM_OK && s.hessian == MPCASM_STAGED_BLOCK) {
+    rc = launch_with_lds(hessian_kernel, s.grid_k3, BLOCK, 0, c.stream, c.err, p, c.params, V, c.P, c.q, s.k3_nrb, 0);
   }
-  if (s.grid_k4)
-    hipLaunchKernelGGL(constraints_kernel, dim3(s.grid_k4), dim3(BLOCK), 0, c.stream, p, c.params, V, c.G, c.h,
-                       s.k4_nrb, batch);
-  *c.err = hipGetLastError();
-  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  if (rc == MPCASM_OK && s.grid_k4)
+    rc = launch_with_lds(constraints_kernel, s.grid_k4, BLOCK, 0, c.stream, c.err, p, c.params, V, c.G, c.h, s.k4_nrb,
+                         batch);
+  return rc;
 }
 
 int launch_preview_matrices(const PlanDev& p, const SrcTable& src, double* PM, int batch,
@@ -651,25 +647,20 @@ int launch_preview_matrices(const PlanDev& p, const SrcTable& src, double* PM, i
   *err = hipSuccess;
   if (p.pmrows > 0 && p.pm_nfd > 0) {
     const unsigned chunks = ceil_div((unsigned)(p.pmrows * (p.ng + p.no)), (unsigned)PM_CHUNK);
-    hipLaunchKernelGGL(preview_elements_kernel, dim3(chunks * batch), dim3(BLOCK), 0, stream, p, src,
-                       PM, (int)chunks);
-    *err = hipGetLastError();
-  } else if (p.pmrows > 0) {
-    const unsigned nrb = ceil_div(p.pmrows, WAVES * K2_ROWS_PER_WAVE);
-    hipLaunchKernelGGL(compose_preview_kernel, dim3(nrb * batch), dim3(BLOCK), 0, stream, p, src,
-                       PM, (int)nrb);
-    *err = hipGetLastError();
+    return launch_with_lds(preview_elements_kernel, chunks * batch, BLOCK, 0, stream, err, p, src, PM, (int)chunks);
   }
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  if (p.pmrows > 0) {
+    const unsigned nrb = ceil_div(p.pmrows, WAVES * K2_ROWS_PER_WAVE);
+    return launch_with_lds(compose_preview_kernel, nrb * batch, BLOCK, 0, stream, err, p, src, PM, (int)nrb);
+  }
+  return MPCASM_OK;
 }
 
 int launch_preview(const double* PM, const double* given, const double* optim, double* out,
                    int batch, int rows, int ng, int no, hipStream_t stream, hipError_t* err) {
   const unsigned nrb = ceil_div(rows, WAVES);
-  hipLaunchKernelGGL(preview_kernel, dim3(nrb * batch), dim3(BLOCK), 0, stream, PM, given, optim,
-                     out, rows, ng, no, (int)nrb);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(preview_kernel, nrb * batch, BLOCK, 0, stream, err, PM, given, optim, out, rows, ng, no,
+                         (int)nrb);
 }
 
 // f3: values of a fixed sparsity pattern out of a batch of dense matrices
@@ -698,10 +689,8 @@ int launch_gather(const double* src, long long src_stride, const int32_t* index,
   while (per_block < 64 && (long)per_block * nnz < 4096 && batch / (per_block * 2) >= 2048)
     per_block *= 2;
   const unsigned blocks = (unsigned)((batch + per_block - 1) / per_block);
-  hipLaunchKernelGGL(gather_kernel, dim3(blocks), dim3(BLOCK), 0, stream, src, src_stride, index,
-                     nnz, dst, per_block, batch);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(gather_kernel, blocks, BLOCK, 0, stream, err, src, src_stride, index, nnz, dst, per_block,
+                         batch);
 }
 
 // f4: the geometry updates of a Box (restrictions.py:380-486) on the facets' parameters of
@@ -784,21 +773,16 @@ int launch_box_transform_ss(double* params, long long nparams, int batch, const 
                             const double* arg, long long arg_stride, hipStream_t stream,
                             hipError_t* err) {
   const long total = (long)batch * nfacets;
-  hipLaunchKernelGGL(box_transform_ss_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)),
-                     dim3(BLOCK), 0, stream, params, nparams, batch, facets, nfacets, op, L, lrows,
-                     ss_dim, arg, arg_stride);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(box_transform_ss_kernel, (unsigned)((total + BLOCK - 1) / BLOCK), BLOCK, 0, stream, err,
+                         params, nparams, batch, facets, nfacets, op, L, lrows, ss_dim, arg, arg_stride);
 }
 
 int launch_box_transform(double* params, long long nparams, int batch, const int32_t* facets,
                          int nfacets, int op, const double* arg, long long arg_stride,
                          hipStream_t stream, hipError_t* err) {
   const long total = (long)batch * nfacets;
-  hipLaunchKernelGGL(box_transform_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK),
-                     0, stream, params, nparams, batch, facets, nfacets, op, arg, arg_stride);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(box_transform_kernel, (unsigned)((total + BLOCK - 1) / BLOCK), BLOCK, 0, stream, err, params,
+                         nparams, batch, facets, nfacets, op, arg, arg_stride);
 }
 
 }  // namespace mpcasm

@@ -191,8 +191,10 @@ int stride_table(const PlanDev& d, const int64_t* h_src_stride, SrcTable* out) {
 // launched (for an entry that builds an index between the two)
 int lti_prepass(const mpcasm_plan* plan, const SrcTable& src, void* d_work, int n, void* stream, SrcTable* eff) {
   if (plan->dev.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;
-  return launch_lti_tables(plan->dev, src, static_cast<double*>(d_work), n, plan->h_itab.data(), eff,
-                           static_cast<hipStream_t>(stream));
+  hipError_t err;
+  const int rc = launch_lti_tables(plan->dev, src, static_cast<double*>(d_work), n, plan->h_itab.data(), eff,
+                                   static_cast<hipStream_t>(stream), &err);
+  return launched(rc, err);
 }
 int lti_refusals(const mpcasm_plan* plan, const SrcTable& src, void* d_work, SrcTable* eff) {
   if (plan->dev.t_nlti != 0 && !d_work) return MPCASM_ERR_ARG;

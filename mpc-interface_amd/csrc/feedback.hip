@@ -380,9 +380,17 @@ __global__ __launch_bounds__(FB_BLOCK) void ltv_true_inputs_kernel(PlanDev p, Tr
   }
 }
 
-#define MPCASM_FB_CASES(X)                                                                            \
-  X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(3, 1) X(3, 2) X(3, 3) X(3, 4) X(4, 1) \
-  X(4, 2) X(4, 3) X(4, 4)
+// every (states, inputs) instantiation of a kernel family, [n - 1][m - 1]
+#define MPCASM_FB_TABLE(K)                                \
+  {{K<1, 1>, K<1, 2>, K<1, 3>, K<1, 4>},                  \
+   {K<2, 1>, K<2, 2>, K<2, 3>, K<2, 4>},                  \
+   {K<3, 1>, K<3, 2>, K<3, 3>, K<3, 4>},                  \
+   {K<4, 1>, K<4, 2>, K<4, 3>, K<4, 4>}}
+using LqrKernel = void (*)(LqrArgs);
+using TrueInputsKernel = void (*)(PlanDev, TrueArgs);
+constexpr LqrKernel lqr_kernels[SW_NMAX][SW_MMAX] = MPCASM_FB_TABLE(ltv_lqr_kernel);
+constexpr TrueInputsKernel true_inputs_kernels[SW_NMAX][SW_MMAX] = MPCASM_FB_TABLE(ltv_true_inputs_kernel);
+#undef MPCASM_FB_TABLE
 
 }  // namespace
 
@@ -397,17 +405,8 @@ int launch_ltv_lqr(int n, int m, int T, int batch, const double* A, long long st
     return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
   }
   const LqrArgs a{A, strideA, B, strideB, Q, R, PT, K, Acl, info, T, batch};
-  const dim3 grid((unsigned)((batch + FB_BLOCK - 1) / FB_BLOCK));
-  switch (n * 8 + m) {
-#define MPCASM_X(NS, MS)                                                                  \
-  case NS * 8 + MS:                                                                       \
-    hipLaunchKernelGGL((ltv_lqr_kernel<NS, MS>), grid, dim3(FB_BLOCK), 0, stream, a);     \
-    break;
-    MPCASM_FB_CASES(MPCASM_X)
-#undef MPCASM_X
-  }
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(lqr_kernels[n - 1][m - 1], (unsigned)((batch + FB_BLOCK - 1) / FB_BLOCK), FB_BLOCK, 0, stream,
+                       err, a);
 }
 
 int launch_ltv_close(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
@@ -420,9 +419,7 @@ int launch_ltv_close(int n, int m, int T, int batch, const double* A, long long 
   const long long blocks = (total + FB_CLOSE_BLOCK - 1) / FB_CLOSE_BLOCK;
   if (blocks > 0x7FFFFFFFLL) return MPCASM_ERR_LIMIT;
   const CloseArgs a{A, strideA, B, strideB, K, strideK, stepK, Acl, n, m, T, total};
-  hipLaunchKernelGGL(ltv_close_kernel, dim3((unsigned)blocks), dim3(FB_CLOSE_BLOCK), 0, stream, a);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(ltv_close_kernel, (unsigned)blocks, FB_CLOSE_BLOCK, 0, stream, err, a);
 }
 
 int launch_ltv_augment(int n, int m, int T, int batch, const double* A, long long strideA, const double* B,
@@ -439,10 +436,7 @@ int launch_ltv_augment(int n, int m, int T, int batch, const double* A, long lon
   if (blocksA + blocksB + blocksK > 0x7FFFFFFFLL) return MPCASM_ERR_LIMIT;
   const AugmentArgs a{A, strideA, B, strideB, K, strideK, stepK, At, Bt, Kt, n, m, T, totalA, totalB, totalK,
                       (unsigned)blocksA, (unsigned)blocksB};
-  hipLaunchKernelGGL(ltv_augment_kernel, dim3((unsigned)(blocksA + blocksB + blocksK)), dim3(FB_CLOSE_BLOCK), 0,
-                     stream, a);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(ltv_augment_kernel, (unsigned)(blocksA + blocksB + blocksK), FB_CLOSE_BLOCK, 0, stream, err, a);
 }
 
 int launch_ltv_true_inputs(const PlanDev& p, const SrcTable& src, const double* K, long long strideK,
@@ -456,17 +450,8 @@ int launch_ltv_true_inputs(const PlanDev& p, const SrcTable& src, const double* 
   const TrueArgs a{src.ptr[p.sw_src_a], src.stride[p.sw_src_a], src.ptr[p.sw_src_b], src.stride[p.sw_src_b],
                    K, strideK, given, rows, optim, index, out, count};
   const long lanes = (long)count * p.sw_naxes;
-  const dim3 grid((unsigned)((lanes + FB_BLOCK - 1) / FB_BLOCK));
-  switch (n * 8 + m) {
-#define MPCASM_X(NS, MS)                                                                           \
-  case NS * 8 + MS:                                                                                \
-    hipLaunchKernelGGL((ltv_true_inputs_kernel<NS, MS>), grid, dim3(FB_BLOCK), 0, stream, p, a);   \
-    break;
-    MPCASM_FB_CASES(MPCASM_X)
-#undef MPCASM_X
-  }
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(true_inputs_kernels[n - 1][m - 1], (unsigned)((lanes + FB_BLOCK - 1) / FB_BLOCK), FB_BLOCK, 0,
+                       stream, err, p, a);
 }
 
 }  // namespace mpcasm

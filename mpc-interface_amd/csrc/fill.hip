@@ -1019,10 +1019,49 @@ __global__ __launch_bounds__(64) void fill_ltv_row_kernel(const double* __restri
   stream_row(Row + (cur ^ 1) * rstep, N - 1);
 }
 
-template <typename K>
-hipError_t allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return allow_whole_lds(reinterpret_cast<const void*>(kernel));
+// The instantiations of each kernel with more than one: what fill_choose picks from and launch_fill_su launches.
+// A row: the template arguments as FillChoice names them (arg; generic, pad: fill_lti_kernel's) and the kernel.
+template <class Kernel>
+struct FillRow {
+  int arg, generic, pad;
+  Kernel kernel;
+  size_t (*lds_doubles)(int N, int m) = nullptr;   // (the ltv-row kernel: its dynamic LDS depends on NS)
+};
+constexpr FillRow<decltype(&fill_lti_quad_kernel<1>)> quad_rows[] = {{1, 0, 0, fill_lti_quad_kernel<1>},
+                                                                     {2, 0, 0, fill_lti_quad_kernel<2>},
+                                                                     {3, 0, 0, fill_lti_quad_kernel<3>},
+                                                                     {4, 0, 0, fill_lti_quad_kernel<4>}};
+constexpr FillRow<decltype(&fill_lti_kernel<64, false>)> lti_rows[] = {{64, 0, 0, fill_lti_kernel<64, false>},
+                                                                       {BLOCK, 0, 1, fill_lti_kernel<BLOCK, false, true>},
+                                                                       {BLOCK, 0, 0, fill_lti_kernel<BLOCK, false>},
+                                                                       {BLOCK, 1, 0, fill_lti_kernel<BLOCK, true>}};
+constexpr FillRow<decltype(&fill_ltv_row_kernel<1>)> ltv_row_rows[] = {
+    {1, 0, 0, fill_ltv_row_kernel<1>, LtvRow<1>::lds_doubles},
+    {2, 0, 0, fill_ltv_row_kernel<2>, LtvRow<2>::lds_doubles},
+    {3, 0, 0, fill_ltv_row_kernel<3>, LtvRow<3>::lds_doubles},
+    {4, 0, 0, fill_ltv_row_kernel<4>, LtvRow<4>::lds_doubles}};
+constexpr FillRow<decltype(&fill_ltv_block_kernel<0>)> ltv_block_rows[] = {{2, 0, 0, fill_ltv_block_kernel<2>},
+                                                                           {3, 0, 0, fill_ltv_block_kernel<3>},
+                                                                           {4, 0, 0, fill_ltv_block_kernel<4>},
+                                                                           {0, 0, 0, fill_ltv_block_kernel<0>}};
+constexpr FillRow<decltype(&fill_ltv_kernel<64>)> ltv_rows[] = {{64, 0, 0, fill_ltv_kernel<64>},
+                                                                {BLOCK, 0, 0, fill_ltv_kernel<BLOCK>}};
+template <class Row, size_t R>
+int fill_row(const Row (&rows)[R], int arg, int generic = 0, int pad = 0) {
+  for (size_t r = 0; r < R; ++r)
+    if (rows[r].arg == arg && rows[r].generic == generic && rows[r].pad == pad) return (int)r;
+  return -1;
+}
+// the row of a choice in the table of its kernel (0: the tiny and the ltv-wave kernel are one instantiation each)
+int fill_row_of(const FillChoice& c) {
+  switch (c.kernel) {
+    case MPCASM_FILL_QUAD: return fill_row(quad_rows, c.arg);
+    case MPCASM_FILL_LTI: return fill_row(lti_rows, c.arg, c.generic, c.pad);
+    case MPCASM_FILL_LTV_ROW: return fill_row(ltv_row_rows, c.arg);
+    case MPCASM_FILL_LTV_BLOCK: return fill_row(ltv_block_rows, c.arg);
+    case MPCASM_FILL_LTV: return fill_row(ltv_rows, c.arg);
+    default: return 0;
+  }
 }
 
 // MPCASM_FILL_MIN_WAVES (tuning aid), read once per process: the route and the launch see the same value
@@ -1037,7 +1076,14 @@ int fill_min_waves() {
 int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillChoice* out) {
   *out = FillChoice{};
   FillChoice c{};
-  constexpr size_t LDS_MAX = CU_LDS_BYTES;
+  // (a combination with no row in its kernel's table is refused here: the launch has no list of its own)
+  auto chosen = [&] {
+    c.row = fill_row_of(c);
+    if (c.row < 0) return (int)MPCASM_ERR_LIMIT;
+    *out = c;
+    return (int)MPCASM_OK;
+  };
+  constexpr size_t LDS_MAX = RESIDENT_LDS_LIMIT;   // (what launch_with_lds grants)
   const bool pairs = ((N * n) & 1) == 0 && aligned16;   // rows of U are whole 16-byte words
   const int by4 = (batch + 3) / 4;
   if (!ltv && n <= 4 && m + n <= 16 && pairs && ((N * n * n) & 1) == 0) {
@@ -1058,22 +1104,17 @@ int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillCho
       c.whole_lines = (N * n) % 16 == 0 ? 1 : 0;
       c.grid = (batch + spw - 1) / spw;
       c.lds = bytes;
-      *out = c;
-      return MPCASM_OK;
+      return chosen();
     }
   }
   if (ltv && n <= 4 && n * m <= 64 && pairs) {
-    const size_t bytes = (n == 1   ? LtvRow<1>::lds_doubles(N, m)
-                          : n == 2 ? LtvRow<2>::lds_doubles(N, m)
-                          : n == 3 ? LtvRow<3>::lds_doubles(N, m)
-                                   : LtvRow<4>::lds_doubles(N, m)) * sizeof(double);
+    const size_t bytes = ltv_row_rows[fill_row(ltv_row_rows, n)].lds_doubles(N, m) * sizeof(double);
     if (bytes <= 64 * 1024) {
       c.kernel = MPCASM_FILL_LTV_ROW;
       c.arg = n;
       c.grid = batch;
       c.lds = bytes;
-      *out = c;
-      return MPCASM_OK;
+      return chosen();
     }
   }
   if (!ltv) {
@@ -1143,8 +1184,7 @@ int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillCho
       c.lds = per;
     }
   }
-  *out = c;
-  return MPCASM_OK;
+  return chosen();
 }
 
 int launch_fill_su(const double* A, const double* B, double* S, double* U, int batch, int N, int n,
@@ -1153,64 +1193,23 @@ int launch_fill_su(const double* A, const double* B, double* S, double* U, int b
   FillChoice c;
   const int rc = fill_choose(batch, N, n, m, ltv, (((uintptr_t)S | (uintptr_t)U) & 15) == 0, &c);
   if (rc != MPCASM_OK) return rc;
-  // (kernels whose dynamic LDS can pass 64 KB get the whole-LDS attribute first)
-#define MPCASM_FILL_LAUNCH(KERNEL, THREADS, ...)                                                   \
-  do {                                                                                             \
-    if ((*err = allow_lds(KERNEL, c.lds)) != hipSuccess) return MPCASM_ERR_HIP;                    \
-    hipLaunchKernelGGL(KERNEL, dim3(c.grid), dim3(THREADS), c.lds, stream, A, B, S, U,             \
-                       __VA_ARGS__);                                                               \
-  } while (0)
   switch (c.kernel) {
-    case MPCASM_FILL_QUAD: {
-      auto kernel = c.arg == 1   ? fill_lti_quad_kernel<1>
-                    : c.arg == 2 ? fill_lti_quad_kernel<2>
-                    : c.arg == 3 ? fill_lti_quad_kernel<3>
-                                 : fill_lti_quad_kernel<4>;
-      MPCASM_FILL_LAUNCH(kernel, 64, batch, N, m, c.spw, c.lshift, c.whole_lines);
-      break;
-    }
+    case MPCASM_FILL_QUAD:
+      return launch_with_lds(quad_rows[c.row].kernel, c.grid, 64, c.lds, stream, err, A, B, S, U, batch, N, m, c.spw,
+                             c.lshift, c.whole_lines);
     case MPCASM_FILL_TINY:
-      MPCASM_FILL_LAUNCH(fill_lti_tiny_kernel, BLOCK, batch, N, n, m, c.spw);
-      break;
+      return launch_with_lds(fill_lti_tiny_kernel, c.grid, BLOCK, c.lds, stream, err, A, B, S, U, batch, N, n, m, c.spw);
     case MPCASM_FILL_LTI:
-      if (c.arg == 64)
-        MPCASM_FILL_LAUNCH((fill_lti_kernel<64, false>), BLOCK, batch, N, n, m);
-      else if (c.pad)
-        MPCASM_FILL_LAUNCH((fill_lti_kernel<BLOCK, false, true>), BLOCK, batch, N, n, m);
-      else if (!c.generic)
-        MPCASM_FILL_LAUNCH((fill_lti_kernel<BLOCK, false>), BLOCK, batch, N, n, m);
-      else
-        MPCASM_FILL_LAUNCH((fill_lti_kernel<BLOCK, true>), BLOCK, batch, N, n, m);
-      break;
-    case MPCASM_FILL_LTV_ROW: {
-      auto kernel = c.arg == 1   ? fill_ltv_row_kernel<1>
-                    : c.arg == 2 ? fill_ltv_row_kernel<2>
-                    : c.arg == 3 ? fill_ltv_row_kernel<3>
-                                 : fill_ltv_row_kernel<4>;
-      MPCASM_FILL_LAUNCH(kernel, 64, N, m);
-      break;
-    }
-    case MPCASM_FILL_LTV_BLOCK: {
-      auto kernel = c.arg == 2   ? fill_ltv_block_kernel<2>
-                    : c.arg == 3 ? fill_ltv_block_kernel<3>
-                    : c.arg == 4 ? fill_ltv_block_kernel<4>
-                                 : fill_ltv_block_kernel<0>;
-      MPCASM_FILL_LAUNCH(kernel, BLOCK, N, n, m);
-      break;
-    }
+      return launch_with_lds(lti_rows[c.row].kernel, c.grid, BLOCK, c.lds, stream, err, A, B, S, U, batch, N, n, m);
+    case MPCASM_FILL_LTV_ROW:
+      return launch_with_lds(ltv_row_rows[c.row].kernel, c.grid, 64, c.lds, stream, err, A, B, S, U, N, m);
+    case MPCASM_FILL_LTV_BLOCK:
+      return launch_with_lds(ltv_block_rows[c.row].kernel, c.grid, BLOCK, c.lds, stream, err, A, B, S, U, N, n, m);
     case MPCASM_FILL_LTV_WAVE:
-      MPCASM_FILL_LAUNCH(fill_ltv_wave_kernel, BLOCK, batch, N, n, m);
-      break;
+      return launch_with_lds(fill_ltv_wave_kernel, c.grid, BLOCK, c.lds, stream, err, A, B, S, U, batch, N, n, m);
     default:
-      if (c.arg == 64)
-        MPCASM_FILL_LAUNCH(fill_ltv_kernel<64>, BLOCK, batch, N, n, m);
-      else
-        MPCASM_FILL_LAUNCH(fill_ltv_kernel<BLOCK>, BLOCK, batch, N, n, m);
-      break;
+      return launch_with_lds(ltv_rows[c.row].kernel, c.grid, BLOCK, c.lds, stream, err, A, B, S, U, batch, N, n, m);
   }
-#undef MPCASM_FILL_LAUNCH
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
 }  // namespace mpcasm

@@ -321,15 +321,8 @@ size_t fused_lds_bytes(const PlanDev& p, int nw) {
 
 int launch_assemble_fused(const PlanDev& p, const AssembleCall& c, size_t lds_bytes) {
   constexpr int NW = 4;
-  auto kernel = fused_assemble_kernel<NW>;
-  if (lds_bytes > 64 * 1024) {
-    *c.err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
-    if (*c.err != hipSuccess) return MPCASM_ERR_HIP;
-  }
-  hipLaunchKernelGGL(kernel, dim3(c.batch), dim3(NW * 64), lds_bytes, c.stream, p, c.src, c.params, c.given,
-                     c.P, c.q, c.G, c.h, c.batch, c.opt.phase_mask);
-  *c.err = hipGetLastError();
-  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(fused_assemble_kernel<NW>, (unsigned)c.batch, NW * 64, lds_bytes, c.stream, c.err, p, c.src,
+                         c.params, c.given, c.P, c.q, c.G, c.h, c.batch, c.opt.phase_mask);
 }
 
 }  // namespace mpcasm

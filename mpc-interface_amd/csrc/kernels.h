@@ -27,11 +27,12 @@ int launch_fill_su(const double* A, const double* B, double* S, double* U, int b
 // host only: what launch_fill_su launches (mpcasm_fill_route).  `kernel`: MPCASM_FILL_*; `arg`: the kernel's
 // integer template argument (NS of the quad, ltv-row and ltv-block kernels, TPI of the lti and ltv kernels, else
 // 0); `generic`, `pad`: fill_lti_kernel's GENERIC and PAD; `spw`: systems per wavefront (quad and tiny kernels);
-// `lshift`, `whole_lines`: the quad kernel's; `grid`: workgroups; `lds`: dynamic LDS of a workgroup.  What the
-// decision depends on beside the sizes: whether S and U are both 16-byte aligned, and MPCASM_FILL_MIN_WAVES.
-// MPCASM_ERR_LIMIT where nothing is launched.
+// `lshift`, `whole_lines`: the quad kernel's; `grid`: workgroups; `lds`: dynamic LDS of a workgroup;
+// `row`: the row of that kernel's table of instantiations.  What the decision depends on beside the sizes: whether
+// S and U are both 16-byte aligned, and MPCASM_FILL_MIN_WAVES.  MPCASM_ERR_LIMIT where nothing is launched: one
+// system's LDS is more than a workgroup is granted (RESIDENT_LDS_LIMIT), or no instantiation takes the sizes.
 struct FillChoice {
-  int kernel, arg, generic, pad, spw, lshift, whole_lines, grid;
+  int kernel, arg, generic, pad, spw, lshift, whole_lines, grid, row;
   size_t lds;
 };
 int fill_choose(int batch, int N, int n, int m, int ltv, bool aligned16, FillChoice* out);
@@ -108,7 +109,7 @@ bool tiled_eligible(const PlanDev& p);
 size_t tiled_workspace_bytes(const PlanDev& p, int batch);
 int launch_assemble_tiled(const PlanDev& p, const AssembleCall& call);
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* work, int batch,
-                      const int32_t* h_itab, SrcTable* eff, hipStream_t stream);
+                      const int32_t* h_itab, SrcTable* eff, hipStream_t stream, hipError_t* err);
 // (toeplitz_zero_pad, the zeros toeplitz_assemble_kernel keeps in LDS behind the group's table: plan_check.h, beside
 // the checker that holds the stages to it)
 // host only: what launch_assemble_tiled launches for a plan (mpcasm_tiled_route).  `form`: MPCASM_TILED_*;
@@ -118,9 +119,10 @@ int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* work, int b
 // tables (MPCASM_TILED_TABLES_*); `tg`: shared_p_kernel<tg> (0: P not wanted, or no weight); `sym`: only the
 // lower block pairs of P (Toeplitz, general and the K_g of the shared form).  What the decision depends on
 // beside the plan: the sources' strides, the batch, which halves are wanted, MPCASM_OPT_PATH, and whether the
-// launch has `given` and a workspace.
+// launch has `given` and a workspace.  `row`: the row of the scan form's or of shared_p_kernel's table of
+// instantiations that kp, cb or tg were read from (-1: none of either is launched).
 struct TiledChoice {
-  int form, fused, kp, cb, rows_in_lds, whole_lines, tables, tg, sym;
+  int form, fused, kp, cb, rows_in_lds, whole_lines, tables, tg, sym, row;
   int dlen;     // (scan form: doubles of d in LDS)
   size_t lds;
 };
@@ -133,9 +135,10 @@ int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* work, c
 bool sweep_eligible(const PlanDev& p);
 // host only: what launch_assemble_sweep launches for a plan (mpcasm_sweep_route) -- the instantiation
 // ltv_sweep_kernel<cpt, NS, MS, AS, pair> (specialised: NS, MS, AS = 3, 1, 2, else 0, 0, 0), how the lines of G
-// are walked (per_line, reg_lines) and the dynamic LDS of a workgroup; MPCASM_ERR_LIMIT where nothing is launched
+// are walked (per_line, reg_lines), the dynamic LDS of a workgroup and the row of the table of instantiations;
+// MPCASM_ERR_LIMIT where nothing is launched
 struct SweepChoice {
-  int cpt, specialised, pair, per_line, reg_lines;
+  int cpt, specialised, pair, per_line, reg_lines, row;
   size_t lds;
 };
 int sweep_choose(const PlanDev& p, const int32_t* h_itab, SweepChoice* out);
@@ -324,17 +327,18 @@ struct QpSens {
   double* lres;
 };
 
-// the launch of a kernel with dynamic LDS: more than a workgroup may have -> MPCASM_ERR_LIMIT; more than 64 KiB ->
-// allow_whole_lds first; *err is the runtime's word where MPCASM_ERR_HIP comes back
+// the launch of a kernel, the only one outside resident.hip's launch_jc and jit.hip (`lds`: its dynamic LDS, 0 for
+// none): more than a workgroup may have -> MPCASM_ERR_LIMIT; more than 64 KiB -> allow_whole_lds first; *err is the
+// runtime's word where MPCASM_ERR_HIP comes back.  A sequence of launches returns at the first not MPCASM_OK.
 template <typename... Params, typename... Args>
-int launch_with_lds(void (*kernel)(Params...), unsigned grid, int block, size_t lds, hipStream_t stream,
-                    hipError_t* err, Args... args) {
+int launch_with_lds(void (*kernel)(Params...), dim3 grid, int block, size_t lds, hipStream_t stream, hipError_t* err,
+                    Args... args) {
   if (lds > (size_t)RESIDENT_LDS_LIMIT) return MPCASM_ERR_LIMIT;
   if (lds > 64 * 1024) {
     *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
     if (*err != hipSuccess) return MPCASM_ERR_HIP;
   }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3((unsigned)block), lds, stream, args...);
+  hipLaunchKernelGGL(kernel, grid, dim3((unsigned)block), lds, stream, args...);
   *err = hipGetLastError();
   return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }

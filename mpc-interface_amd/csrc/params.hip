@@ -62,10 +62,8 @@ int launch_params_map(double* params, int64_t n_params, const int32_t* recs, con
   const long total = (long)batch * nrecs;
   const long blocks = (total + PM_BLOCK - 1) / PM_BLOCK;
   const unsigned grid = (unsigned)(blocks < (long)PM_MAX_GRID ? blocks : (long)PM_MAX_GRID);
-  hipLaunchKernelGGL(params_map_kernel, dim3(grid), dim3(PM_BLOCK), 0, stream, params, (long)n_params, recs, coef,
-                     nrecs, cmd, (long)cmd_stride, ncmd, index, sign, total);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(params_map_kernel, grid, PM_BLOCK, 0, stream, err, params, (long)n_params, recs, coef, nrecs,
+                         cmd, (long)cmd_stride, ncmd, index, sign, total);
 }
 
 }  // namespace mpcasm

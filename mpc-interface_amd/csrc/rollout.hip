@@ -352,16 +352,10 @@ int launch_ltv_rollout(const PlanDev& p, const SrcTable& src, const int32_t* tab
   RolloutGeometry geo;
   const int rc = ltv_rollout_geometry(p, table_words, out != nullptr, count, &geo);
   if (rc != MPCASM_OK) return rc;
-  if (geo.lds > 64 * 1024) {
-    *err = allow_whole_lds(reinterpret_cast<const void*>(ltv_rollout_kernel));
-    if (*err != hipSuccess) return MPCASM_ERR_HIP;
-  }
   const RollArgs a{src.ptr[p.sw_src_a], src.stride[p.sw_src_a], src.ptr[p.sw_src_b], src.stride[p.sw_src_b],
                    table, table_words, given, rows, optim, index, status, apply_mask, out, write_given, count,
                    geo.group};
-  hipLaunchKernelGGL(ltv_rollout_kernel, dim3(geo.grid), dim3(RO_BLOCK), geo.lds, stream, p, a);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(ltv_rollout_kernel, geo.grid, RO_BLOCK, geo.lds, stream, err, p, a);
 }
 
 }  // namespace mpcasm

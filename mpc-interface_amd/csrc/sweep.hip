@@ -703,6 +703,18 @@ __global__ __launch_bounds__(SW_BLOCK) void ltv_sweep_kernel(
   }
 }
 
+// the instantiations, in the order they are tried: what sweep_choose picks from and launch_assemble_sweep launches
+using SweepKernel = decltype(&ltv_sweep_kernel<1, 0, 0, 0>);
+struct SweepRow {
+  int cpt, specialised, pair;
+  SweepKernel kernel;
+};
+constexpr SweepRow sweep_rows[] = {
+    {2, 1, 1, ltv_sweep_kernel<2, 3, 1, 2, true>},  {1, 1, 0, ltv_sweep_kernel<1, 3, 1, 2, false>},
+    {2, 0, 1, ltv_sweep_kernel<2, 0, 0, 0, true>},  {1, 0, 0, ltv_sweep_kernel<1, 0, 0, 0, false>},
+    {2, 0, 0, ltv_sweep_kernel<2, 0, 0, 0, false>}, {4, 0, 0, ltv_sweep_kernel<4, 0, 0, 0, false>},
+};
+
 }  // namespace
 
 bool sweep_eligible(const PlanDev& p) { return p.sw_ok != 0; }
@@ -758,42 +770,25 @@ int sweep_choose(const PlanDev& p, const int32_t* h_itab, SweepChoice* out) {
   c.pair = even && p.no <= SW_BLOCK * 2;
   c.cpt = c.pair ? 2 : (p.no <= SW_BLOCK ? 1 : (p.no <= SW_BLOCK * 2 ? 2 : 4));
   c.specialised = lipm && (c.pair || c.cpt == 1);
-  *out = c;
-  return MPCASM_OK;
+  for (c.row = 0; c.row < (int)std::size(sweep_rows); ++c.row) {
+    const SweepRow& r = sweep_rows[c.row];
+    if (r.cpt == c.cpt && r.specialised == c.specialised && r.pair == c.pair) {
+      *out = c;
+      return MPCASM_OK;
+    }
+  }
+  return MPCASM_ERR_LIMIT;
 }
 
 int launch_assemble_sweep(const PlanDev& p, const AssembleCall& call) {
   SweepChoice c;
   const int rc = sweep_choose(p, call.h_itab, &c);
   if (rc != MPCASM_OK) return rc;
-  const int per_line = c.per_line, reg_lines = c.reg_lines;
-  const size_t lds = c.lds;
   const SrcTable& src = call.src;
-  hipError_t* const err = call.err;
-  const double* A = src.ptr[p.sw_src_a];
-  const double* Bm = src.ptr[p.sw_src_b];
-  const long long sa = src.stride[p.sw_src_a], sb = src.stride[p.sw_src_b];
-#define MPCASM_SWEEP_CASE(CPT, NS, MS, AS, PAIR)                                                       \
-  if (c.cpt == CPT && c.specialised == (NS != 0) && c.pair == (int)PAIR) {                             \
-    auto kernel = ltv_sweep_kernel<CPT, NS, MS, AS, PAIR>;                                             \
-    if (lds > 64 * 1024) {                                                                             \
-      *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));                                   \
-      if (*err != hipSuccess) return MPCASM_ERR_HIP;                                                   \
-    }                                                                                                  \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)call.batch), dim3(SW_BLOCK), lds, call.stream, p, A, sa, \
-                       Bm, sb, call.params, call.given, call.P, call.q, call.G, call.h, call.batch,    \
-                       per_line, reg_lines);                                                           \
-    *err = hipGetLastError();                                                                          \
-    return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;                                            \
-  }
-  MPCASM_SWEEP_CASE(2, 3, 1, 2, true)
-  MPCASM_SWEEP_CASE(1, 3, 1, 2, false)
-  MPCASM_SWEEP_CASE(2, 0, 0, 0, true)
-  MPCASM_SWEEP_CASE(1, 0, 0, 0, false)
-  MPCASM_SWEEP_CASE(2, 0, 0, 0, false)
-  MPCASM_SWEEP_CASE(4, 0, 0, 0, false)
-#undef MPCASM_SWEEP_CASE
-  return MPCASM_ERR_LIMIT;
+  return launch_with_lds(sweep_rows[c.row].kernel, (unsigned)call.batch, SW_BLOCK, c.lds, call.stream, call.err, p,
+                         src.ptr[p.sw_src_a], src.stride[p.sw_src_a], src.ptr[p.sw_src_b], src.stride[p.sw_src_b],
+                         call.params, call.given, call.P, call.q, call.G, call.h, call.batch, c.per_line,
+                         c.reg_lines);
 }
 
 }  // namespace mpcasm

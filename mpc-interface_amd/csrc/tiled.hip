@@ -1745,6 +1745,47 @@ size_t tiled_workspace_bytes(const PlanDev& p, int batch) {
   return ((size_t)batch * p.t_work + (shared_form_plan(p) ? shared_scratch(p).total : 0)) * sizeof(double);
 }
 
+namespace {
+
+// the pre-pass that makes the generated groups' horizon tables: a wavefront per `systems` systems while every
+// group is small, else a workgroup per system
+struct LtiTablesChoice {
+  int kind;             // MPCASM_TILED_TABLES_*
+  size_t lds, small;    // per-system kernel: its dynamic LDS; small kernel: doubles of one system
+  int lanes, systems;
+};
+
+// MPCASM_ERR_LIMIT: the per-system kernel would need more than 64 KB of dynamic LDS (it has never run so)
+int lti_tables_choose(const PlanDev& p, const int32_t* h_itab, LtiTablesChoice* out) {
+  LtiTablesChoice& c = *out;
+  c = LtiTablesChoice{MPCASM_TILED_TABLES_NONE, 0, 0, 1, 1};
+  if (p.t_nlti == 0) return MPCASM_OK;
+  bool all_small = true;
+  for (int g = 0; g < p.t_nlti; ++g) {
+    const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
+    const size_t n = rec[TL_N], m = rec[TL_M], N = rec[TL_HORIZON];
+    c.lds = std::max(c.lds, (n * n + 2 * n * (m + n) + n * m * LTI_HIST) * sizeof(double));
+    const size_t tables = N * n * n + n * m * 2 * N;
+    all_small = all_small && n * (m + n) <= 64 && tables <= 1800;  // (four wavefronts: under 64 KB of LDS)
+    c.small = std::max(c.small, 192 + tables + (tables & 1));
+  }
+  c.kind = all_small ? MPCASM_TILED_TABLES_SMALL : MPCASM_TILED_TABLES_SYSTEM;
+  if (!all_small && c.lds > 64 * 1024) return MPCASM_ERR_LIMIT;
+  if (all_small) {  // a wavefront per `systems` systems
+    size_t elems = 0;
+    for (int g = 0; g < p.t_nlti; ++g) {
+      const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
+      elems = std::max<size_t>(elems, (size_t)rec[TL_N] * (rec[TL_M] + rec[TL_N]));
+    }
+    while ((size_t)c.lanes < elems) c.lanes *= 2;
+    // (as many systems per wavefront as lanes and 64 KB of LDS per workgroup allow)
+    c.systems = (int)std::max<size_t>(1, std::min<size_t>(64 / c.lanes, (64 * 1024 / sizeof(double) / (BLOCK / 64)) / c.small));
+  }
+  return MPCASM_OK;
+}
+
+}  // namespace
+
 // The horizon tables of the plan's generated groups, from the (A, B) in the slots of each group's
 // first two sources, into the scratch (t_work doubles per instance); `eff`: the launch's sources
 // with those tables in the places of the groups' U_j and S -- what the column tables address.
@@ -1769,70 +1810,28 @@ int lti_effective_sources(const PlanDev& p, const SrcTable& src, double* w, cons
     eff->ptr[ids[m]] = w ? w + rec[TL_TA] : nullptr;
     eff->stride[ids[m]] = stride;
   }
-  return MPCASM_OK;
+  LtiTablesChoice tables;
+  return lti_tables_choose(p, h_itab, &tables);
 }
-
-namespace {
-
-// the pre-pass that makes the generated groups' horizon tables: a wavefront per `systems` systems while every
-// group is small, else a workgroup per system
-struct LtiTablesChoice {
-  int kind;             // MPCASM_TILED_TABLES_*
-  size_t lds, small;    // per-system kernel: its dynamic LDS; small kernel: doubles of one system
-  int lanes, systems;
-};
-
-LtiTablesChoice lti_tables_choose(const PlanDev& p, const int32_t* h_itab) {
-  LtiTablesChoice c{MPCASM_TILED_TABLES_NONE, 0, 0, 1, 1};
-  if (p.t_nlti == 0) return c;
-  bool all_small = true;
-  for (int g = 0; g < p.t_nlti; ++g) {
-    const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
-    const size_t n = rec[TL_N], m = rec[TL_M], N = rec[TL_HORIZON];
-    c.lds = std::max(c.lds, (n * n + 2 * n * (m + n) + n * m * LTI_HIST) * sizeof(double));
-    const size_t tables = N * n * n + n * m * 2 * N;
-    all_small = all_small && n * (m + n) <= 64 && tables <= 1800;  // (four wavefronts: under 64 KB of LDS)
-    c.small = std::max(c.small, 192 + tables + (tables & 1));
-  }
-  c.kind = all_small ? MPCASM_TILED_TABLES_SMALL : MPCASM_TILED_TABLES_SYSTEM;
-  if (all_small) {  // a wavefront per `systems` systems
-    size_t elems = 0;
-    for (int g = 0; g < p.t_nlti; ++g) {
-      const int32_t* rec = h_itab + p.off_t_lti + g * T_LTI_WORDS;
-      elems = std::max<size_t>(elems, (size_t)rec[TL_N] * (rec[TL_M] + rec[TL_N]));
-    }
-    while ((size_t)c.lanes < elems) c.lanes *= 2;
-    // (as many systems per wavefront as lanes and 64 KB of LDS per workgroup allow)
-    c.systems = (int)std::max<size_t>(1, std::min<size_t>(64 / c.lanes, (64 * 1024 / sizeof(double) / (BLOCK / 64)) / c.small));
-  }
-  return c;
-}
-
-}  // namespace
 
 int launch_lti_tables(const PlanDev& p, const SrcTable& src, double* w, int batch,
-                      const int32_t* h_itab, SrcTable* eff, hipStream_t stream) {
+                      const int32_t* h_itab, SrcTable* eff, hipStream_t stream, hipError_t* err) {
   *eff = src;
   if (p.t_nlti == 0) return MPCASM_OK;
   if (h_itab == nullptr || w == nullptr) return MPCASM_ERR_ARG;
   const long long stride = p.t_work;
-  {
-    const int rc = lti_effective_sources(p, src, w, h_itab, eff);
-    if (rc != MPCASM_OK) return rc;
-  }
-  const LtiTablesChoice c = lti_tables_choose(p, h_itab);
+  LtiTablesChoice c;
+  int rc = lti_effective_sources(p, src, w, h_itab, eff);
+  if (rc == MPCASM_OK) rc = lti_tables_choose(p, h_itab, &c);
+  if (rc != MPCASM_OK) return rc;
   if (c.kind == MPCASM_TILED_TABLES_SMALL) {
     const long jobs = (long)batch * p.t_nlti;
     const long per_wg = (long)(BLOCK / 64) * c.systems;
     const unsigned grid = (unsigned)std::min<long>((jobs + per_wg - 1) / per_wg, 256L * 8);
-    hipLaunchKernelGGL(lti_tables_small_kernel, dim3(grid), dim3(BLOCK),
-                       c.small * c.systems * (BLOCK / 64) * sizeof(double), stream, p, src, w, stride, jobs,
-                       (int)c.small, c.lanes, c.systems);
-    return MPCASM_OK;
+    return launch_with_lds(lti_tables_small_kernel, grid, BLOCK, c.small * c.systems * (BLOCK / 64) * sizeof(double),
+                           stream, err, p, src, w, stride, jobs, (int)c.small, c.lanes, c.systems);
   }
-  hipLaunchKernelGGL(lti_tables_kernel, dim3((unsigned)batch * p.t_nlti), dim3(BLOCK), c.lds, stream, p,
-                     src, w, stride);
-  return MPCASM_OK;
+  return launch_with_lds(lti_tables_kernel, (unsigned)batch * p.t_nlti, BLOCK, c.lds, stream, err, p, src, w, stride);
 }
 
 namespace {
@@ -1873,26 +1872,35 @@ int shared_form_choose(const PlanDev& p, const SrcTable& eff, const int32_t* h_i
   return MPCASM_OK;
 }
 
-// (the kernel multiplies by every one of its TG matrices, the ones behind the last being zeros: the
-// instantiation just above the number of weights -- at 32 for C4's 18 the kernel was bound by its FMAs)
-int shared_tg(int weights) {
-  return weights > 24 ? 32 : weights > 20 ? 24 : weights > 16 ? 20 : weights > 12 ? 16 : weights > 8 ? 12
-         : weights > 4 ? 8 : weights > 0 ? 4 : 0;
+// shared_p_kernel<tg>, from the widest down.  (The kernel multiplies by every one of its TG matrices, the ones
+// behind the last being zeros: the instantiation just above the number of weights -- at 32 for C4's 18 the kernel
+// was bound by its FMAs.)
+using SharedPKernel = decltype(&shared_p_kernel<4>);
+struct SharedPRow {
+  int tg;
+  SharedPKernel kernel;
+};
+constexpr SharedPRow shared_p_rows[] = {{32, shared_p_kernel<32>}, {24, shared_p_kernel<24>}, {20, shared_p_kernel<20>},
+                                        {16, shared_p_kernel<16>}, {12, shared_p_kernel<12>}, {8, shared_p_kernel<8>},
+                                        {4, shared_p_kernel<4>}};
+// the last row that still holds `weights` >= 1 matrices; -1: none does
+int shared_p_row(int weights) {
+  int row = -1;
+  while (row + 1 < (int)std::size(shared_p_rows) && shared_p_rows[row + 1].tg >= weights) ++row;
+  return row;
 }
 
-// The shared-model form, for a launch tiled_choose found to be one
+// The shared-model form, for a launch tiled_choose found to be one (`row`: of shared_p_rows, -1 for no weight)
 int launch_shared_form(const PlanDev& p, const AssembleCall& c, const SrcTable& eff, double* w, long long stride,
-                       int nb, int npairs, int sym, int tg) {
+                       int nb, int npairs, int sym, int row) {
   double *const P = c.P, *const q = c.q, *const G = c.G, *const h = c.h;
   const double* const params = c.params;
   const int batch = c.batch;
   const hipStream_t stream = c.stream;
   SharedSlots sl;
   size_t qh_lds = 0;
-  {
-    const int rc = shared_form_choose(p, eff, c.h_itab, batch, G != nullptr, w != nullptr, &sl, &qh_lds);
-    if (rc != MPCASM_OK) return rc;
-  }
+  int rc = shared_form_choose(p, eff, c.h_itab, batch, G != nullptr, w != nullptr, &sl, &qh_lds);
+  if (rc != MPCASM_OK) return rc;
   const int nrho = p.t_nstage * TK;
   const SharedScratch S = shared_scratch(p);
   double* base = w + (size_t)batch * stride;
@@ -1902,79 +1910,48 @@ int launch_shared_form(const PlanDev& p, const AssembleCall& c, const SrcTable& 
   double* zero = base + S.zero;
   double* qdummy = base + S.qdummy;
   const long pairs = (long)p.rtot * (p.t_nop / 2);
-  hipLaunchKernelGGL(shared_rows_kernel, dim3((unsigned)ceil_div(pairs, (long)BLOCK)), dim3(BLOCK), 0, stream, p,
-                     eff, V);
+  rc = launch_with_lds(shared_rows_kernel, (unsigned)ceil_div(pairs, (long)BLOCK), BLOCK, 0, stream, c.err, p, eff, V);
   const long nn = (long)p.no * p.no;
-  if (P != nullptr && sl.n > 0) {
+  if (rc == MPCASM_OK && P != nullptr && sl.n > 0) {
     const int fill = std::max(sl.n * p.nparams, p.rtot);
-    hipLaunchKernelGGL(shared_pseudo_kernel, dim3((unsigned)ceil_div(fill, BLOCK)), dim3(BLOCK), 0, stream, sl,
-                       p.nparams, p.rtot, pseudo, zero);
+    rc = launch_with_lds(shared_pseudo_kernel, (unsigned)ceil_div(fill, BLOCK), BLOCK, 0, stream, c.err, sl, p.nparams,
+                         p.rtot, pseudo, zero);
     // K_g: the Hessian of pseudo-instance g, by the general kernel (d = 0, no constraints)
     const unsigned groups = ceil_div((unsigned)sl.n, 8u);
-    hipLaunchKernelGGL(tiled_assemble_kernel, dim3(groups * 8 * (unsigned)npairs), dim3(BLOCK), 0, stream, p,
-                       eff, pseudo, zero, 0ll, K, qdummy, static_cast<double*>(nullptr),
-                       static_cast<double*>(nullptr), nb, npairs, sym, sl.n);
+    if (rc == MPCASM_OK)
+      rc = launch_with_lds(tiled_assemble_kernel, groups * 8 * (unsigned)npairs, BLOCK, 0, stream, c.err, p, eff, pseudo,
+                           zero, 0ll, K, qdummy, static_cast<double*>(nullptr), static_cast<double*>(nullptr), nb,
+                           npairs, sym, sl.n);
   }
-  if (P != nullptr) {
+  if (rc == MPCASM_OK && P != nullptr && row >= 0) {
     const dim3 pgrid((unsigned)ceil_div(nn, (long)SH_PRANGE), (unsigned)ceil_div(batch, SH_PIB));
-#define MPCASM_SHARED_P(TG)                                                                                \
-  case TG:                                                                                                 \
-    hipLaunchKernelGGL((shared_p_kernel<TG>), pgrid, dim3(BLOCK), 0, stream, sl, nn, K, params, p.nparams, P, \
-                       batch);                                                                             \
-    break;
-    switch (tg) {
-      MPCASM_SHARED_P(32)
-      MPCASM_SHARED_P(24)
-      MPCASM_SHARED_P(20)
-      MPCASM_SHARED_P(16)
-      MPCASM_SHARED_P(12)
-      MPCASM_SHARED_P(8)
-      MPCASM_SHARED_P(4)
-#undef MPCASM_SHARED_P
-      case 0:
-        (void)hipMemsetAsync(P, 0, sizeof(double) * (size_t)batch * nn, stream);
-        break;
-      default:
-        return MPCASM_ERR_LIMIT;   // (tiled_choose and this list have come apart)
-    }
+    rc = launch_with_lds(shared_p_rows[row].kernel, pgrid, BLOCK, 0, stream, c.err, sl, nn, K, params, p.nparams, P,
+                         batch);
+  } else if (rc == MPCASM_OK && P != nullptr) {
+    *c.err = hipMemsetAsync(P, 0, sizeof(double) * (size_t)batch * nn, stream);
+    if (*c.err != hipSuccess) rc = MPCASM_ERR_HIP;
   }
-  if (G != nullptr && p.nc > 0)
-    hipLaunchKernelGGL(shared_g_kernel,
-                       dim3((unsigned)ceil_div((long)p.nc * p.no, (long)SH_GRANGE), (unsigned)ceil_div(batch, SH_GIB)),
-                       dim3(BLOCK), 0, stream, p, V, params, G, batch);
-  if (P != nullptr || (G != nullptr && p.nc > 0))
-    hipLaunchKernelGGL(shared_qh_kernel, dim3((unsigned)ceil_div(batch, SH_QB)), dim3(BLOCK), qh_lds, stream, p,
-                       V, params, w, stride, P != nullptr ? q : nullptr,
-                       (G != nullptr && p.nc > 0) ? h : nullptr, batch, nrho);
-  *c.err = hipGetLastError();
-  *c.kernel = MPCASM_KERNEL_TILED_SHARED;
-  return *c.err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  if (rc == MPCASM_OK && G != nullptr && p.nc > 0) {
+    const dim3 ggrid((unsigned)ceil_div((long)p.nc * p.no, (long)SH_GRANGE), (unsigned)ceil_div(batch, SH_GIB));
+    rc = launch_with_lds(shared_g_kernel, ggrid, BLOCK, 0, stream, c.err, p, V, params, G, batch);
+  }
+  if (rc == MPCASM_OK && (P != nullptr || (G != nullptr && p.nc > 0)))
+    rc = launch_with_lds(shared_qh_kernel, (unsigned)ceil_div(batch, SH_QB), BLOCK, qh_lds, stream, c.err, p, V, params,
+                         w, stride, P != nullptr ? q : nullptr, (G != nullptr && p.nc > 0) ? h : nullptr, batch, nrho);
+  if (rc == MPCASM_OK) *c.kernel = MPCASM_KERNEL_TILED_SHARED;
+  return rc;
 }
 
-template <int KP, int CB>
-int launch_scan_as(const PlanDev& p, const AssembleCall& call, const SrcTable& eff, const double* A,
-                   long long strideA, const double* Bm, long long strideB, const double* w, long long stride,
-                   const TiledChoice& c, const double* given) {
-  hipError_t* const err = call.err;
-  auto kernel = toeplitz_scan_kernel<KP, CB>;
-  if (c.lds > 64 * 1024) {
-    *err = allow_whole_lds(reinterpret_cast<const void*>(kernel));
-    if (*err != hipSuccess) return MPCASM_ERR_HIP;
-  }
-  // rows of G per ticket (tuning aid MPCASM_SCAN_GROUP; tools/ab_scan.sh): fewer = the wavefronts of a
-  // workgroup write closer together, more = fewer tickets
-  static const int group = [] {
-    const char* e = getenv("MPCASM_SCAN_GROUP");
-    const int v = e ? atoi(e) : SCAN_GROUP;   // (r04: 8 rows per ticket 8.6 ms per 8192 C4 instances, 4: 9.3, 1: 9.7)
-    return v < 1 ? 1 : (v > SCAN_GROUP ? SCAN_GROUP : v);
-  }();
-  hipLaunchKernelGGL(kernel, dim3((unsigned)call.batch), dim3(BLOCK), c.lds, call.stream, p, eff, A, strideA, Bm,
-                     strideB, call.params, w, stride, call.P, call.q, call.G, call.h, call.batch, c.dlen,
-                     c.whole_lines, group, c.rows_in_lds, call.opt.phase_mask, given, c.fused);
-  *err = hipGetLastError();
-  if (*err == hipSuccess) *call.kernel = MPCASM_KERNEL_TILED_SCAN;
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
-}
+// toeplitz_scan_kernel<kp, cb>, in the order the rows are tried
+using ScanKernel = decltype(&toeplitz_scan_kernel<4, 4>);
+struct ScanRow {
+  int kp, cb;
+  ScanKernel kernel;
+};
+constexpr ScanRow scan_rows[] = {{4, 4, toeplitz_scan_kernel<4, 4>},   {8, 4, toeplitz_scan_kernel<8, 4>},
+                                 {4, 8, toeplitz_scan_kernel<4, 8>},   {8, 8, toeplitz_scan_kernel<8, 8>},
+                                 {12, 4, toeplitz_scan_kernel<12, 4>}, {12, 6, toeplitz_scan_kernel<12, 6>},
+                                 {16, 4, toeplitz_scan_kernel<16, 4>}};
 
 // the scan form for this plan, or MPCASM_ERR_LIMIT: no instantiation holds its K terms and column
 // blocks in registers, or an instance does not fit in LDS (the Toeplitz form takes it then).
@@ -1994,13 +1971,12 @@ int scan_choose(const PlanDev& p, const int32_t* h_itab, bool fused, bool have_g
   int whole = p.no % 16 == 0 && N % 16 == 0;
   const int32_t* blk = h_itab + p.off_t_scan_blk;
   for (int b = 0; b < nblk; ++b) whole = whole && blk[2 * b] % 16 == 0;
-  // the instantiations, in the order they are tried
-  static const int inst[][2] = {{4, 4}, {8, 4}, {4, 8}, {8, 8}, {12, 4}, {12, 6}, {16, 4}};
-  for (const auto& kc : inst)
-    if (K <= kc[0] && nblk <= kc[1]) {
+  for (int row = 0; row < (int)std::size(scan_rows); ++row)
+    if (K <= scan_rows[row].kp && nblk <= scan_rows[row].cb) {
       c->fused = fused;
-      c->kp = kc[0];
-      c->cb = kc[1];
+      c->row = row;
+      c->kp = scan_rows[row].kp;
+      c->cb = scan_rows[row].cb;
       c->rows_in_lds = rows_in_lds;
       c->whole_lines = whole;
       c->dlen = dlen;
@@ -2017,19 +1993,19 @@ int launch_scan(const PlanDev& p, const AssembleCall& call, const SrcTable& eff,
   const SrcTable& src = call.src;
   const int32_t* rec = call.h_itab + p.off_t_lti;
   const int32_t* ids = call.h_itab + p.off_t_lti_ids + rec[TL_IDS];
-#define MPCASM_SCAN_CASE(KP, CB)                                                                          \
-  if (c.kp == KP && c.cb == CB)                                                                          \
-    return launch_scan_as<KP, CB>(p, call, eff, src.ptr[ids[0]], src.stride[ids[0]], src.ptr[ids[1]],     \
-                                  src.stride[ids[1]], w, stride, c, given);
-  MPCASM_SCAN_CASE(4, 4)
-  MPCASM_SCAN_CASE(8, 4)
-  MPCASM_SCAN_CASE(4, 8)
-  MPCASM_SCAN_CASE(8, 8)
-  MPCASM_SCAN_CASE(12, 4)
-  MPCASM_SCAN_CASE(12, 6)
-  MPCASM_SCAN_CASE(16, 4)
-#undef MPCASM_SCAN_CASE
-  return MPCASM_ERR_LIMIT;   // (scan_choose and this list have come apart)
+  // rows of G per ticket (tuning aid MPCASM_SCAN_GROUP; tools/ab_scan.sh): fewer = the wavefronts of a
+  // workgroup write closer together, more = fewer tickets
+  static const int group = [] {
+    const char* e = getenv("MPCASM_SCAN_GROUP");
+    const int v = e ? atoi(e) : SCAN_GROUP;   // (r04: 8 rows per ticket 8.6 ms per 8192 C4 instances, 4: 9.3, 1: 9.7)
+    return v < 1 ? 1 : (v > SCAN_GROUP ? SCAN_GROUP : v);
+  }();
+  const int rc = launch_with_lds(scan_rows[c.row].kernel, (unsigned)call.batch, BLOCK, c.lds, call.stream, call.err, p,
+                                 eff, src.ptr[ids[0]], src.stride[ids[0]], src.ptr[ids[1]], src.stride[ids[1]],
+                                 call.params, w, stride, call.P, call.q, call.G, call.h, call.batch, c.dlen,
+                                 c.whole_lines, group, c.rows_in_lds, call.opt.phase_mask, given, c.fused);
+  if (rc == MPCASM_OK) *call.kernel = MPCASM_KERNEL_TILED_SCAN;
+  return rc;
 }
 
 // the Toeplitz kernel's dynamic LDS (behind the table and the zeros: d, and at the end of a diagonal block the
@@ -2053,6 +2029,7 @@ ToeplitzLds toeplitz_lds(const PlanDev& p, const int32_t* rec) {
 int tiled_choose(const PlanDev& p, const SrcTable& src, const int32_t* h_itab, int path, int batch,
                  bool want_cost, bool want_constraints, bool have_given, bool have_work, TiledChoice* out) {
   TiledChoice c{};
+  c.row = -1;
   *out = c;
   c.sym = p.rs_sym_any;
   // the scan form with its set-up fused (H_T_SCAN_FUSED): one kernel, no scratch (MPCASM_OPT_PATH 1 keeps the
@@ -2072,9 +2049,11 @@ int tiled_choose(const PlanDev& p, const SrcTable& src, const int32_t* h_itab, i
   SrcTable eff = src;
   if (p.t_nlti != 0) {
     if (h_itab == nullptr || !have_work) return MPCASM_ERR_ARG;
-    const int rc = lti_effective_sources(p, src, nullptr, h_itab, &eff);
+    LtiTablesChoice tables;
+    int rc = lti_effective_sources(p, src, nullptr, h_itab, &eff);
+    if (rc == MPCASM_OK) rc = lti_tables_choose(p, h_itab, &tables);
     if (rc != MPCASM_OK) return rc;
-    c.tables = lti_tables_choose(p, h_itab).kind;
+    c.tables = tables.kind;
   }
   if (p.rtot > 0 && (size_t)p.ng * sizeof(double) > 48 * 1024) return MPCASM_ERR_LIMIT;
   const long long stride = p.t_work;
@@ -2110,7 +2089,11 @@ int tiled_choose(const PlanDev& p, const SrcTable& src, const int32_t* h_itab, i
     const int rc = shared_form_choose(p, eff, h_itab, batch, want_constraints, have_work, &sl, &qh_lds);
     if (rc == MPCASM_OK) {
       c.form = MPCASM_TILED_SHARED;
-      c.tg = want_cost ? shared_tg(sl.n) : 0;
+      if (want_cost && sl.n > 0) {
+        c.row = shared_p_row(sl.n);
+        if (c.row < 0) return MPCASM_ERR_LIMIT;
+        c.tg = shared_p_rows[c.row].tg;
+      }
       *out = c;
       return MPCASM_OK;
     }
@@ -2129,22 +2112,18 @@ int launch_assemble_tiled(const PlanDev& p, const AssembleCall& call) {
   double* w = static_cast<double*>(call.work);
   const long long stride = p.t_work;
   TiledChoice c;
-  {
-    const int rc = tiled_choose(p, src, h_itab, call.opt.path, batch, call.P != nullptr, call.G != nullptr,
-                                call.given != nullptr, w != nullptr, &c);
-    if (rc != MPCASM_OK) return rc;
-  }
+  int rc = tiled_choose(p, src, h_itab, call.opt.path, batch, call.P != nullptr, call.G != nullptr,
+                        call.given != nullptr, w != nullptr, &c);
+  if (rc != MPCASM_OK) return rc;
   if (c.form == MPCASM_TILED_SCAN && c.fused) return launch_scan(p, call, src, nullptr, 0, c, call.given);
   SrcTable eff;
-  {
-    const int rc = launch_lti_tables(p, src, w, batch, h_itab, &eff, call.stream);
-    if (rc != MPCASM_OK) return rc;
-  }
-  if (p.rtot > 0) {
+  rc = launch_lti_tables(p, src, w, batch, h_itab, &eff, call.stream, err);
+  if (rc == MPCASM_OK && p.rtot > 0) {
     const unsigned nrb = ceil_div(p.rtot, BLOCK);
-    hipLaunchKernelGGL(compose_d_kernel, dim3(nrb * batch), dim3(BLOCK), (size_t)p.ng * sizeof(double),
-                       call.stream, p, eff, call.given, w, stride, (int)nrb);
+    rc = launch_with_lds(compose_d_kernel, nrb * batch, BLOCK, (size_t)p.ng * sizeof(double), call.stream, err, p, eff,
+                         call.given, w, stride, (int)nrb);
   }
+  if (rc != MPCASM_OK) return rc;
   const int nb = (int)ceil_div(p.no, T_BLOCK);
   const int sym = p.rs_sym_any;
   const int npairs = sym ? nb * (nb + 1) / 2 : nb * nb;
@@ -2154,23 +2133,16 @@ int launch_assemble_tiled(const PlanDev& p, const AssembleCall& call) {
       return launch_scan(p, call, eff, w, stride, c, nullptr);
     case MPCASM_TILED_TOEPLITZ: {
       const ToeplitzLds x = toeplitz_lds(p, h_itab + p.off_t_lti);
-      *err = allow_whole_lds(reinterpret_cast<const void*>(toeplitz_assemble_kernel));
-      if (*err != hipSuccess) return MPCASM_ERR_HIP;
-      hipLaunchKernelGGL(toeplitz_assemble_kernel, dim3((unsigned)batch), dim3(BLOCK), c.lds, call.stream, p, eff,
-                         call.params, w, stride, call.P, call.q, call.G, call.h, nb, npairs, sym, batch, x.tbn,
-                         x.nzero, call.opt.phase_mask);
-      *err = hipGetLastError();
-      return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+      return launch_with_lds(toeplitz_assemble_kernel, (unsigned)batch, BLOCK, c.lds, call.stream, err, p, eff,
+                             call.params, w, stride, call.P, call.q, call.G, call.h, nb, npairs, sym, batch, x.tbn,
+                             x.nzero, call.opt.phase_mask);
     }
     case MPCASM_TILED_SHARED:
-      return launch_shared_form(p, call, eff, w, stride, nb, npairs, sym, c.tg);
+      return launch_shared_form(p, call, eff, w, stride, nb, npairs, sym, c.row);
     default:
-      break;
+      return launch_with_lds(tiled_assemble_kernel, groups * 8 * (unsigned)npairs, BLOCK, 0, call.stream, err, p, eff,
+                             call.params, w, stride, call.P, call.q, call.G, call.h, nb, npairs, sym, batch);
   }
-  hipLaunchKernelGGL(tiled_assemble_kernel, dim3(groups * 8 * (unsigned)npairs), dim3(BLOCK), 0, call.stream, p,
-                     eff, call.params, w, stride, call.P, call.q, call.G, call.h, nb, npairs, sym, batch);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
 }
 
 }  // namespace mpcasm

@@ -190,16 +190,9 @@ int launch_qp_warm_start(int no, int nc, const double* G, const double* h, const
   const int per_lane = vec2 ? 2 : 1;
   const int lpr = no <= 16 * per_lane ? 16 : no <= 32 * per_lane ? 32 : 64;
   const unsigned grid = (unsigned)((count + ipw - 1) / ipw);
-  if (vec2)
-    hipLaunchKernelGGL(warm_start_kernel<2>, dim3(grid), dim3(WS_BLOCK), lds, stream, no, nc, G, h, sx, sy, srho,
-                       smeta, (long)store_rows, store_no, store_nc, index, col_src, row_src, expect_tag, warm_mask,
-                       rho_cold, x, y, z, rho, warm, count, ipw, lpr);
-  else
-    hipLaunchKernelGGL(warm_start_kernel<1>, dim3(grid), dim3(WS_BLOCK), lds, stream, no, nc, G, h, sx, sy, srho,
-                       smeta, (long)store_rows, store_no, store_nc, index, col_src, row_src, expect_tag, warm_mask,
-                       rho_cold, x, y, z, rho, warm, count, ipw, lpr);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(vec2 ? warm_start_kernel<2> : warm_start_kernel<1>, grid, WS_BLOCK, lds, stream, err, no, nc,
+                         G, h, sx, sy, srho, smeta, (long)store_rows, store_no, store_nc, index, col_src, row_src,
+                         expect_tag, warm_mask, rho_cold, x, y, z, rho, warm, count, ipw, lpr);
 }
 
 int launch_qp_warm_store(int no, int nc, const double* x, const double* y, const double* rho, const int32_t* status,
@@ -208,10 +201,8 @@ int launch_qp_warm_store(int no, int nc, const double* x, const double* y, const
                          hipError_t* err) {
   const int ipw = store_no + store_nc <= 256 ? 4 : 1;
   const unsigned grid = (unsigned)((count + ipw - 1) / ipw);
-  hipLaunchKernelGGL(warm_store_kernel, dim3(grid), dim3(WS_BLOCK), 0, stream, no, nc, x, y, rho, status, tag, sx,
-                     sy, srho, smeta, (long)store_rows, store_no, store_nc, index, count, ipw);
-  *err = hipGetLastError();
-  return *err == hipSuccess ? MPCASM_OK : MPCASM_ERR_HIP;
+  return launch_with_lds(warm_store_kernel, grid, WS_BLOCK, 0, stream, err, no, nc, x, y, rho, status, tag, sx, sy, srho,
+                         smeta, (long)store_rows, store_no, store_nc, index, count, ipw);
 }
 
 }  // namespace mpcasm

@@ -83,8 +83,10 @@ def _ev(x):
     return (x + 1) & ~1
 
 
-def earlier_launch(batch, N, n, m, ltv, aligned):
-    lds_max = 160 * 1024
+GRANTED = 156 * 1024     # the dynamic LDS a workgroup is granted; the earlier launch tried up to the CU's 160 KB
+
+
+def earlier_launch(batch, N, n, m, ltv, aligned, lds_max=GRANTED):
 
     def answer(kernel, arg, flags, spw, lshift, grid, lds):
         return (kernel, arg, flags, spw, lshift, grid, lds, int(lds > 64 * 1024))
@@ -203,18 +205,24 @@ def test_no_launch_changed_and_the_family_reaches_what_the_grid_reaches():
     condition, four times the block kernel's LDS within 80 KB, is the condition under which the block kernel in
     front of it has taken the launch -- which is why that instantiation is gone; every signature the grid meets is
     met by a case, and every instantiation is met by the grid."""
-    met, limits, count = set(), set(), 0
+    met, limits, count, over_granted = set(), set(), 0, 0
     out = (ctypes.c_int32 * 8)()
     for shape in grid():
         count += 1
         was = earlier_launch(*shape)
         assert _route(*shape, out) == was, shape
+        # the one difference from the launch as it was: what it sent off with more LDS than a workgroup is granted
+        # (the runtime refused that launch) goes to the next kernel that takes the shape, or is refused
+        before = earlier_launch(*shape, lds_max=160 * 1024)
+        if before != was:
+            assert before is not LIMIT and GRANTED < before[6] <= 160 * 1024, shape
+            over_granted += 1
         if was is LIMIT:
             limits.add(shape[4])
         else:
             assert was[0] != WAVE_ALL, shape
             met |= signatures(was, shape[1], shape[2])
-    assert count > 300000 and limits == {0, 1}
+    assert count > 300000 and limits == {0, 1} and 0 < over_granted < count // 200
     assert {s for s in met if s[0] == "instantiation"} == INSTANTIATIONS
     reached = set()
     for case in fc.RUN:

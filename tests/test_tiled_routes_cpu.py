@@ -205,6 +205,19 @@ def test_plans_of_other_kernels_are_refused(cpu_api):
         assert refusal.value.status == capi.ERR_ARG
 
 
+def test_generated_tables_past_64_kb_of_lds_are_refused(cpu_api):
+    """MPCASM_ERR_LIMIT before anything is launched: a generated group of 24 states and 24 inputs passes the limits
+    of the groups (n (m + n) = 1152 <= 2048, n <= 64), but the per-system pre-pass that would make its horizon
+    tables needs (n n + 2 n (m + n) + 16 n m) 8 = 96 768 bytes of dynamic LDS, and that kernel has never run with
+    more than 64 KB.  N = 6 is the shortest horizon at which the plan is the tiled path's (144 unknowns)."""
+    plan = compile_plan(problems.random_lti(cpu_api, np.random.default_rng(3), nx=24, nu=24, N=6), lti=["plant"])
+    assert plan.no == 144 and plan.resident["ok"] == 0
+    for path in (0, 1, 3, 4):
+        with pytest.raises(capi.MpcasmError) as refusal:
+            engine.tiled_route(plan, 19, [1] * len(plan.sources), path=path)
+        assert refusal.value.status == capi.ERR_LIMIT
+
+
 def test_the_shared_form_needs_every_source_shared(cpu_api):
     """One source of an instance's own, fewer than 8 instances: the general kernel."""
     case = tc.BY_NAME["shared-7"]
